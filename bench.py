@@ -4,7 +4,12 @@
 over the batch: U-Net on the 2B CFG batch -> CFG combine -> DPSScheduler.step (x0, VAE decode,
 HiFi-GAN, mask, log-mel, L2, hand-written backward sweep, fused update).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; --dump-outputs DIR also writes what the last
+timed step returned (latents.npy, loss.npy; float32) so that two builds can be compared output for output.  Everything else
+the benchmark measures -- the final decode + all-gather (`after_loop`), per-stage device times, the roofline leg, the
+whole 200-step trajectory and the CPU-oracle baseline -- runs only under --full (the --no-* switches thin that out).
 
 N > 1 without a launcher: this process starts N rank processes itself (fresh children, started before
 anything here touches the GPU), one per device, RCCL rendezvous on 127.0.0.1, and exits with the worst
@@ -13,8 +18,8 @@ ranks are the launcher's; a world size that differs from --gpus is an error (exi
 
 Prints ONE JSON line on rank 0.  Weights are seeded synthetic (no checkpoints offline), clips are
 synthetic sums of sinusoids; inputs are resident in HBM before the timed region.
-After the timed loop the final latents are decoded and the (B, 160000) waveforms of all ranks are
-all-gathered once (the path's only collective); its time is reported next to the loop's.
+With --full, after the timed loop the final latents are decoded and the (B, 160000) waveforms of all ranks
+are all-gathered once (the path's only collective); its time is reported next to the loop's.
 """
 import argparse
 import json
@@ -173,6 +178,14 @@ class Stepper:
         bad = self.runner.run(self.lanes, len(ts), unet_fn, step_fn, 1 if self.nan_check else 10 ** 9)
         loss = torch.cat([ln.losses[-1].reshape(-1) for ln in self.lanes])
         return loss, int(bad is not None)
+
+
+def dump_outputs(out_dir, arrays, suffix=""):
+    """--dump-outputs: each tensor as <out_dir>/<name><suffix>.npy in float32 (the step's outputs are fp32 latents and losses, ~1 MB)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), t.detach().float().cpu().numpy())
 
 
 def cpu_model_string():
@@ -380,7 +393,13 @@ def main():
                     "--gpus 1: the RCCL path at world size 1, in a fresh child process like every spawned rank")
     ap.add_argument("--workload", default="dps_inpainting", choices=sorted(WORKLOADS),
                     help="default = the headline config (BASELINE.json configs[1]); the others are the remaining GPU configs")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the other legs: final decode + all-gather (after_loop), "
+                    "per-stage device times, the roofline leg, the whole trajectory and the CPU-oracle baseline (--no-* switches skip single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (latents.npy: the next "
+                    "latents, loss.npy: the per-clip guidance loss; float32) to DIR; with several ranks each rank writes <name>_rank<r>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
     if (args.gpus > 1 or args.force_dist) and env_world == 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:], 1 if args.share_gpu else args.gpus))
@@ -477,28 +496,37 @@ def main():
     wall = float(tmax.item())
     latents = stepper.latents
     finite = bool(torch.isfinite(loss).all()) and bool(torch.isfinite(latents).all())
+    if args.dump_outputs:                    # what the last timed step returned, before any --full leg runs
+        dump_outputs(args.dump_outputs, {"latents": latents, "loss": loss}, "" if world == 1 else f"_rank{rank}")
 
+    # ---- --full only, everything below up to the result line: legs that the headline figure does not need
+    after_loop = stages = mel_path = roofline = full_traj = None
     # ---- after the loop: final decode of this rank's clips and the path's only collective, one all_gather of (B, L) waveforms
-    from diffmusic_amd import parallel
-    torch.cuda.synchronize()
-    e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-    e0.record()
-    mel = pipe.vae.decode(latents / pipe.vae.config.scaling_factor).sample
-    audio = pipe.vocoder(mel.squeeze(1))[:, :L].float().contiguous()
-    e1.record()
-    barrier()
-    tg = time.perf_counter()
-    gathered = parallel.gather_waveforms(audio, G)
-    torch.cuda.synchronize()
-    gather_ms = 1e3 * (time.perf_counter() - tg)
-    assert gathered.shape == (G, L)
-    gathered_equals_local = bool(torch.equal(gathered[parallel.shard_indices(G, rank, world)].to(audio.device), audio))   # this rank's rows came back bit-equal
-    finite = finite and bool(torch.isfinite(gathered).all())
-    final_decode_ms = e0.elapsed_time(e1)
+    if args.full:
+        from diffmusic_amd import parallel
+        torch.cuda.synchronize()
+        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        e0.record()
+        mel = pipe.vae.decode(latents / pipe.vae.config.scaling_factor).sample
+        audio = pipe.vocoder(mel.squeeze(1))[:, :L].float().contiguous()
+        e1.record()
+        barrier()
+        tg = time.perf_counter()
+        gathered = parallel.gather_waveforms(audio, G)
+        torch.cuda.synchronize()
+        gather_ms = 1e3 * (time.perf_counter() - tg)
+        assert gathered.shape == (G, L)
+        gathered_equals_local = bool(torch.equal(gathered[parallel.shard_indices(G, rank, world)].to(audio.device), audio))   # this rank's rows came back bit-equal
+        finite = finite and bool(torch.isfinite(gathered).all())
+        final_decode_ms = e0.elapsed_time(e1)
+        after_loop = {"final_decode_ms": round(final_decode_ms, 3), "gather_ms": round(gather_ms, 3) if use_dist else 0.0,
+                      "gather_bytes_per_rank": int(audio.numel() * 4), "gather_world_size": world,
+                      "collective": (f"all_gather of (clips_per_gpu, 160000) fp32 waveforms, once per call ({'RCCL' if args.backend == 'nccl' else 'gloo'}, world size {world})"
+                                     if use_dist else "none (single rank, torch.distributed not initialised)"),
+                      "gathered_equals_local": gathered_equals_local}
 
     # ---- per-stage device times (HIP events around each stage, 2 extra steps) + the STFT / mel sub-path's achieved HBM rate
-    stages = mel_path = None
-    if not args.no_stage_times:
+    if args.full and not args.no_stage_times:
         from diffmusic_amd import profiling
         profiling.enable(events=True)
         for _ in range(2):                  # the plain loop body on the whole batch: stage times without overlap between stages
@@ -514,41 +542,41 @@ def main():
                                 "stage; algorithmic bytes = fused-ideal 2.4 MB per clip-step (SURVEY.md section 8d); per-kernel times in profiles/"}
 
     # ---- roofline leg: one extra step with HIP events around every implicit-GEMM launch
-    import ctypes as C
-    from diffmusic_amd import _lib as Lb
-    Lb.lib().dmx_prof_begin()
-    stepper.advance([ts[k % n_sched]])       # as timed above: with clip lanes the launches have the lanes' shapes and run under overlap
-    ms, fl = C.c_double(), C.c_double()
-    n_launch = Lb.lib().dmx_prof_end(C.byref(ms), C.byref(fl))
-    # headline config: the analytic count of BASELINE.md; other workloads: the FLOPs the launches actually issued
-    algo_tflop_step = ALGO_TFLOP_PER_CLIP_STEP * B if wl == "dps_inpainting" else fl.value / 1e12
-    dms, dfl, dby = C.c_double(), C.c_double(), C.c_double()
-    n_dom = Lb.lib().dmx_prof_dominant(C.byref(dms), C.byref(dfl), C.byref(dby))
-    traffic, traffic_src = pmc_traffic("gemm_glds_kernel") if args.workload == "dps_inpainting" else (None, None)
-    # dominant kernel = gemm_glds_kernel (LDS-DMA tiles): its issued FLOPs, scaled DOWN by algorithmic/issued of the step where the launches
-    # issue more than the analytic count (channel / tile padding) and never up: where the build does the reference's arithmetic in fewer
-    # multiply-adds (the x2 upsampling folded into the VAE's 3x3 convolutions: 4/9 of the reference's) the kernel is credited with what it
-    # issued, and only `whole_step` (reference work per step / wall time) carries the saving
-    scale = min(1.0, algo_tflop_step / (fl.value / 1e12)) if fl.value > 0 else 1.0
-    dom_tflop = dfl.value / 1e12 * scale
-    achieved = dom_tflop / (dms.value * 1e-3) if dms.value > 0 else 0.0
-    all_rate = algo_tflop_step / (ms.value * 1e-3) if ms.value > 0 else 0.0
-    roofline = {"bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_TFLOPS_16BIT, "unit": "TFLOP/s",
-                "frac": round(achieved / PEAK_TFLOPS_16BIT, 4), "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": round(dby.value / max(n_dom, 1)),
-                "kernel": "gemm_glds_kernel (implicit-GEMM conv / batched NT GEMM on LDS-DMA tiles, fp16 MFMA)",
-                "launches_per_step": n_dom, "kernel_ms_per_step": round(dms.value, 3), "avg_launch_us": round(1e3 * dms.value / max(n_dom, 1), 1),
-                "algorithmic_tflop_per_step": round(dom_tflop, 2),
-                "all_gemm_kernels": {"launches_per_step": n_launch, "kernel_ms_per_step": round(ms.value, 3),
-                                     "algorithmic_tflop_per_step": round(algo_tflop_step, 2), "issued_tflop_per_step": round(fl.value / 1e12, 2),
-                                     "achieved": round(all_rate, 1), "frac": round(all_rate / PEAK_TFLOPS_16BIT, 4)},
-                "whole_step": {"achieved": round(algo_tflop_step / (wall / args.steps), 1), "frac": round(algo_tflop_step / (wall / args.steps) / PEAK_TFLOPS_16BIT, 4)},
-                "step_share": round(ms.value / (1e3 * wall / args.steps), 3)}
+    if args.full:
+        import ctypes as C
+        from diffmusic_amd import _lib as Lb
+        Lb.lib().dmx_prof_begin()
+        stepper.advance([ts[k % n_sched]])       # as timed above: with clip lanes the launches have the lanes' shapes and run under overlap
+        ms, fl = C.c_double(), C.c_double()
+        n_launch = Lb.lib().dmx_prof_end(C.byref(ms), C.byref(fl))
+        # headline config: the analytic count of BASELINE.md; other workloads: the FLOPs the launches actually issued
+        algo_tflop_step = ALGO_TFLOP_PER_CLIP_STEP * B if wl == "dps_inpainting" else fl.value / 1e12
+        dms, dfl, dby = C.c_double(), C.c_double(), C.c_double()
+        n_dom = Lb.lib().dmx_prof_dominant(C.byref(dms), C.byref(dfl), C.byref(dby))
+        traffic, traffic_src = pmc_traffic("gemm_glds_kernel") if args.workload == "dps_inpainting" else (None, None)
+        # dominant kernel = gemm_glds_kernel (LDS-DMA tiles): its issued FLOPs, scaled DOWN by algorithmic/issued of the step where the launches
+        # issue more than the analytic count (channel / tile padding) and never up: where the build does the reference's arithmetic in fewer
+        # multiply-adds (the x2 upsampling folded into the VAE's 3x3 convolutions: 4/9 of the reference's) the kernel is credited with what it
+        # issued, and only `whole_step` (reference work per step / wall time) carries the saving
+        scale = min(1.0, algo_tflop_step / (fl.value / 1e12)) if fl.value > 0 else 1.0
+        dom_tflop = dfl.value / 1e12 * scale
+        achieved = dom_tflop / (dms.value * 1e-3) if dms.value > 0 else 0.0
+        all_rate = algo_tflop_step / (ms.value * 1e-3) if ms.value > 0 else 0.0
+        roofline = {"bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_TFLOPS_16BIT, "unit": "TFLOP/s",
+                    "frac": round(achieved / PEAK_TFLOPS_16BIT, 4), "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
+                    "algorithmic_bytes_per_launch": round(dby.value / max(n_dom, 1)),
+                    "kernel": "gemm_glds_kernel (implicit-GEMM conv / batched NT GEMM on LDS-DMA tiles, fp16 MFMA)",
+                    "launches_per_step": n_dom, "kernel_ms_per_step": round(dms.value, 3), "avg_launch_us": round(1e3 * dms.value / max(n_dom, 1), 1),
+                    "algorithmic_tflop_per_step": round(dom_tflop, 2),
+                    "all_gemm_kernels": {"launches_per_step": n_launch, "kernel_ms_per_step": round(ms.value, 3),
+                                         "algorithmic_tflop_per_step": round(algo_tflop_step, 2), "issued_tflop_per_step": round(fl.value / 1e12, 2),
+                                         "achieved": round(all_rate, 1), "frac": round(all_rate / PEAK_TFLOPS_16BIT, 4)},
+                    "whole_step": {"achieved": round(algo_tflop_step / (wall / args.steps), 1), "frac": round(algo_tflop_step / (wall / args.steps) / PEAK_TFLOPS_16BIT, 4)},
+                    "step_share": round(ms.value / (1e3 * wall / args.steps), 3)}
 
     # ---- end-to-end leg: the whole trajectory (all n_sched steps of the loop body, NaN check included) + final decode, from fresh
     # latents -- what run.py:317-332 sees per call, and several seconds of GPU time that an outside sampler can see
-    full_traj = None
-    if not args.no_full_trajectory:
+    if args.full and not args.no_full_trajectory:
         stepper.set_latents(latents0.clone())
         barrier()
         tf = time.perf_counter()
@@ -596,14 +624,10 @@ def main():
                           "nan_check_per_step": not args.no_nan_check,
                           "settle_steps": len(settle_ms), "settle_first3_ms": [round(v, 2) for v in settle_ms[:3]], "settle_last3_ms": [round(v, 2) for v in settle_ms[-3:]], "final_loss_clip0": float(loss.reshape(-1)[0]),
                           "cached_reference_transform": bool(getattr(op, "cache_reference", False)),
-                          "launched_by": "bench.py spawn" if os.environ.get("DMX_BENCH_SPAWNED") else ("torch.distributed.run" if world > 1 else "single process")},
-               "after_loop": {"final_decode_ms": round(final_decode_ms, 3), "gather_ms": round(gather_ms, 3) if use_dist else 0.0,
-                              "gather_bytes_per_rank": int(audio.numel() * 4), "gather_world_size": world,
-                              "collective": (f"all_gather of (clips_per_gpu, 160000) fp32 waveforms, once per call ({'RCCL' if args.backend == 'nccl' else 'gloo'}, world size {world})"
-                                             if use_dist else "none (single rank, torch.distributed not initialised)"),
-                              "gathered_equals_local": gathered_equals_local},
-               "full_trajectory": full_traj, "stage_ms": stages, "mel_path": mel_path, "roofline": roofline}
-        if world == 1 and not args.no_cpu_baseline and wl == "dps_inpainting" and not strong:
+                          "launched_by": "bench.py spawn" if os.environ.get("DMX_BENCH_SPAWNED") else ("torch.distributed.run" if world > 1 else "single process")}}
+        if args.full:
+            res.update({"after_loop": after_loop, "full_trajectory": full_traj, "stage_ms": stages, "mel_path": mel_path, "roofline": roofline})
+        if args.full and world == 1 and not args.no_cpu_baseline and wl == "dps_inpainting" and not strong:
             host_cpus, affinity, quota = cpu_share()
             # the whole CPU share of this process: the cgroup quota where one is set; else the affinity set -- unless that is a whole
             # many-core host (> 32), where this pool's documented per-GPU share of 16 is assumed (see cpu_share)

@@ -8,7 +8,7 @@ for r in 1 2; do
   i=0
   for v in "" "$@"; do
     echo "=== env: ${v:-default} (round $r)"
-    env $v timeout -k 10 300 python bench.py --no-cpu-baseline > $out/bench_${i}_$r.json 2> $out/bench.err || tail -3 $out/bench.err
+    env $v timeout -k 10 300 python bench.py --full --no-cpu-baseline > $out/bench_${i}_$r.json 2> $out/bench.err || tail -3 $out/bench.err
     python -c "
 import json; d=json.load(open('$out/bench_${i}_$r.json')); print('bench', d['value'], d['ms_per_step'], {k: round(v, 2) for k, v in d['stage_ms'].items()})"
     i=$((i+1))

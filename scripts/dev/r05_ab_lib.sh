@@ -7,7 +7,7 @@ out=gpurun_out/r05_ab_$tag.log; : > $out
 for r in 1 2; do
   for v in A B; do
     lib=$A; [ $v = B ] && lib=$B
-    DMX_LIB_PATH=$GRAFT_REPO_ROOT/$lib timeout -k 10 300 python bench.py --no-cpu-baseline --no-full-trajectory --steps 20 --warmup 3 "$@" 2>/dev/null | python -c "
+    DMX_LIB_PATH=$PWD/$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-full-trajectory --steps 20 --warmup 3 "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('$v ($lib) round $r:', d['value'], d['ms_per_step'], 'roofline', d['roofline']['frac'], d['roofline']['kernel_ms_per_step'], {k: round(v, 2) for k, v in d['stage_ms'].items()})" >> $out

@@ -4,7 +4,7 @@ set -o pipefail
 out=gpurun_out/r05_lanes_ab.log
 mkdir -p gpurun_out
 : > $out
-common="--no-cpu-baseline --no-stage-times --no-full-trajectory --steps 20 --warmup 3"
+common="--full --no-cpu-baseline --no-stage-times --no-full-trajectory --steps 20 --warmup 3"
 run() {  # label, env, args
   echo "== $1" >> $out
   env $2 python bench.py $common $3 2>>gpurun_out/r05_lanes_ab.err | python -c "
@@ -23,6 +23,6 @@ for rnd in 0 1; do
   run "cfg3 (4 clips) lanes 2 (round $rnd)" "A=1" "--workload dsg_phase_audioldm2 --lanes 2"
 done
 echo "== cfg2 lanes 2 / lanes 1 with the 200-step trajectory" >> $out
-python bench.py --no-cpu-baseline --no-stage-times --steps 20 --warmup 3 --lanes 2 2>>gpurun_out/r05_lanes_ab.err | tee gpurun_out/r05_bench_lanes2.json | python -c "import sys, json; d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['value'], d['full_trajectory'])" >> $out
-python bench.py --no-cpu-baseline --no-stage-times --steps 20 --warmup 3 --lanes 1 2>>gpurun_out/r05_lanes_ab.err | tee gpurun_out/r05_bench_lanes1.json | python -c "import sys, json; d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['value'], d['full_trajectory'])" >> $out
+python bench.py --full --no-cpu-baseline --no-stage-times --steps 20 --warmup 3 --lanes 2 2>>${out%.log}.err | tee $(dirname $out)/r05_bench_lanes2.json | python -c "import sys, json; d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['value'], d['full_trajectory'])" >> $out
+python bench.py --full --no-cpu-baseline --no-stage-times --steps 20 --warmup 3 --lanes 1 2>>${out%.log}.err | tee $(dirname $out)/r05_bench_lanes1.json | python -c "import sys, json; d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['value'], d['full_trajectory'])" >> $out
 cat $out

@@ -64,6 +64,19 @@ def test_visible_gpus_counts_kfd_nodes_and_honours_visibility_lists(monkeypatch,
 def test_command_line_documents_both_scaling_modes():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--batch", "--global-batch", "--workload", "--cpu-threads"):
+    for flag in ("--gpus", "--steps", "--warmup", "--batch", "--global-batch", "--workload", "--cpu-threads", "--full", "--dump-outputs"):
         assert flag in out.stdout
     assert "--no-graph" not in out.stdout
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    import numpy as np
+    import torch
+    import bench
+    lat, loss = torch.randn(2, 8, 5, 4, dtype=torch.float32), torch.tensor([0.5, 0.25], dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "d"), {"latents": lat, "loss": loss})
+    got = np.load(tmp_path / "d" / "latents.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, lat.numpy())
+    assert np.load(tmp_path / "d" / "loss.npy").dtype == np.float32
+    bench.dump_outputs(str(tmp_path / "d"), {"loss": loss}, "_rank1")
+    assert (tmp_path / "d" / "loss_rank1.npy").exists()

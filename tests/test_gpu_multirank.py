@@ -25,7 +25,7 @@ def _free_port():
 
 def test_bench_two_rank_rehearsal_on_one_gpu():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--global-batch", "8",
-           "--steps", "2", "--warmup", "1", "--settle", "2", "--no-cpu-baseline", "--no-stage-times", "--no-full-trajectory"]
+           "--steps", "2", "--warmup", "1", "--settle", "2", "--full", "--no-cpu-baseline", "--no-stage-times", "--no-full-trajectory"]
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -87,7 +87,7 @@ def test_bench_rccl_path_at_world_size_one():
     """The RCCL ("nccl") code path the driver's multi-GPU run takes -- init_process_group(device_id=...), device barrier, max-over-ranks
     all_reduce, device all_gather of the waveforms -- executed on the one GPU of this box at world size 1 (`--force-dist`)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--backend", "nccl", "--steps", "2", "--warmup", "1",
-           "--settle", "2", "--no-cpu-baseline", "--no-stage-times", "--no-full-trajectory"]
+           "--settle", "2", "--full", "--no-cpu-baseline", "--no-stage-times", "--no-full-trajectory"]
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
