@@ -1,0 +1,253 @@
+"""The ctypes spelling of the op surface: one function per op registered in csrc_torch/torch_ops.cpp, with the op's name, positional
+parameters, return values, dtypes and shapes, over the same `extern "C"` launchers of libdiffmusic_hip.so (`_lib.py`).  Outputs come
+from torch's caching allocator, launches go to torch's current HIP stream, model / audio handles arrive as Python ints.
+
+`ops.hip.<name>` resolves here when the op library is switched off or unavailable (ops.py); `ops.ctypes_hip` is this module.  Where
+a C entry point takes more than the op schema expresses (caller-owned outputs, row strides, prediction type and clip range, a mel
+width other than 64, a U-Net whose output channels differ from its input's) the function takes it as trailing keyword-only
+parameters; tests/test_abi.py holds the positional signatures equal to the schemas."""
+import ctypes as C
+
+import torch
+
+from . import _lib
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def abi_version():
+    return _lib.lib().dmx_abi_version()
+
+
+# ---- scheduler arithmetic
+def sched_pred_x0(x, eps, alpha_t, *, ptype=0, clip_r=0.0):
+    """ptype / clip_r: the DDIM parent's other branches (sample / v_prediction, clip_sample), the `_ex` entry point."""
+    x0 = torch.empty_like(x)
+    if ptype == 0 and clip_r == 0.0:
+        _lib.check(_lib.lib().dmx_sched_pred_x0(_p(x), _p(eps), _p(x0), x.numel(), alpha_t, _stream()), "pred_x0")
+    else:
+        _lib.check(_lib.lib().dmx_sched_pred_x0_ex(_p(x), _p(eps), _p(x0), x.numel(), alpha_t, ptype, clip_r, _stream()), "pred_x0_ex")
+    return x0
+
+
+def cfg_combine(eps2, scale):
+    out = torch.empty_like(eps2[:eps2.shape[0] // 2])           # the [uncond | text] halves of the CFG batch -> one half
+    _lib.check(_lib.lib().dmx_sched_cfg_combine(_p(eps2), _p(out), out.numel(), scale, _stream()), "cfg_combine")
+    return out
+
+
+def sched_update(mode, x, eps, x0, g0, inv_scale, noise, alpha_t, alpha_prev, sigma, rate, eps_small, global_norm, *,
+                 ptype=0, clip_r=0.0, grad_out=None):
+    """-> (prev_sample, MPGD's guided x0 or None).  grad_out: caller-owned tensor like x that receives the applied gradient."""
+    B, n = x.shape[0], x[0].numel()
+    prev = torch.empty_like(x)
+    x0_out = torch.empty_like(x) if mode == 2 else None
+    if ptype == 0 and clip_r == 0.0:
+        _lib.check(_lib.lib().dmx_sched_step(mode, _p(x), _p(eps), _p(x0), _p(g0), _p(inv_scale), _p(noise), _p(prev), _p(x0_out),
+                                             _p(grad_out), B, n, alpha_t, alpha_prev, sigma, rate, eps_small, int(global_norm),
+                                             _stream()), "sched_step")
+    else:
+        _lib.check(_lib.lib().dmx_sched_step_ex(mode, _p(x), _p(eps), _p(x0), _p(g0), _p(inv_scale), _p(noise), _p(prev), _p(x0_out),
+                                                _p(grad_out), B, n, alpha_t, alpha_prev, sigma, rate, eps_small, int(global_norm),
+                                                ptype, clip_r, _stream()), "sched_step_ex")
+    return prev, x0_out
+
+
+def randn_philox(shape, seeds, offset, device):
+    """Seeds are taken modulo 2^64 (the op's int[] holds signed 64-bit values only)."""
+    B = int(shape[0])
+    n = 1
+    for d in shape[1:]:
+        n *= int(d)
+    out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+    arr = (C.c_ulonglong * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds])
+    _lib.check(_lib.lib().dmx_randn_philox(_p(out), B, n, arr, int(offset) & 0xFFFFFFFFFFFFFFFF, _stream()), "randn_philox")
+    return out
+
+
+# ---- measurement operators and the loss
+def mask_mul(x, mask, L, Ly):
+    """y[:, :L] = x[:, :L] * mask (None: copy), zeros up to Ly; x (B, >= L) with any row stride."""
+    B = x.shape[0]
+    y = torch.empty(B, Ly, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_mask_apply(_p(x), x.stride(0), _p(mask), _p(y), Ly, B, L, Ly, _stream()), "mask_mul")
+    return y
+
+
+def l2norm(ref, pred, gscale, *, want_grad=True):
+    """-> (loss (B), dpred like pred, or None when want_grad is False)."""
+    B = pred.shape[0]
+    n = pred[0].numel()
+    loss = torch.empty(B, dtype=torch.float32, device=pred.device)
+    dpred = torch.empty_like(pred) if want_grad else None
+    _lib.check(_lib.lib().dmx_l2_loss(_p(ref), 0 if ref.shape[0] == 1 and B > 1 else n, _p(pred), _p(loss), _p(dpred), B, n, gscale,
+                                      _stream()), "l2_loss")
+    return loss, dpred
+
+
+def resample_fwd(x, h, Lin, Lout, orig, new_, off):
+    B = x.shape[0]
+    y = torch.empty(B, Lout, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_fir_fwd(_p(x), x.stride(0), _p(h), _p(y), Lout, B, Lin, Lout, h.shape[-1], orig, new_, off, _stream()),
+               "fir_fwd")
+    return y
+
+
+def resample_bwd(dy, h, h_rev, Lin, Lfull, orig, new_, off):
+    B, out_len = dy.shape
+    d = torch.zeros(B, Lfull, dtype=torch.float32, device=dy.device)
+    _lib.check(_lib.lib().dmx_fir_bwd(_p(dy), out_len, _p(h), _p(h_rev), _p(d), Lfull, B, Lin, out_len, h.shape[-1], orig, new_, off,
+                                      _stream()), "fir_bwd")
+    return d
+
+
+def logmel_fwd(audio, wav, state, L, power2, to_db, lo, hi, *, out=None, n_mels=64):
+    """out: caller-owned (B, frames, n_mels) result; n_mels: the handle's mel width (the op allocates 64 columns)."""
+    lib = _lib.lib()
+    B = wav.shape[0]
+    mel = out if out is not None else torch.empty(B, lib.dmx_audio_num_frames(audio, L), n_mels, dtype=torch.float32, device=wav.device)
+    _lib.check(lib.dmx_audio_transform_fwd(audio, _p(wav), wav.stride(0), _p(mel), _p(state), B, L, int(power2), int(to_db), lo, hi,
+                                           _stream()), "audio_transform_fwd")
+    return mel
+
+
+def logmel_bwd(audio, dmel, state, L, power2, to_db, lo, hi, *, dwav=None):
+    """dwav: caller-owned (B, >= L) result with any row stride (overwritten up to L)."""
+    B = dmel.shape[0]
+    if dwav is None:
+        dwav = torch.empty(B, L, dtype=torch.float32, device=dmel.device)
+    _lib.check(_lib.lib().dmx_audio_transform_bwd(audio, _p(dmel), _p(dwav), dwav.stride(0), _p(state), B, L, int(power2), int(to_db),
+                                                  lo, hi, 0, _stream()), "audio_transform_bwd")
+    return dwav
+
+
+def mel_guidance(audio, wav, mask, ref, state, L, Lfull, power2, to_db, lo, hi, gscale):
+    lib = _lib.lib()
+    B = wav.shape[0]
+    T = lib.dmx_audio_num_frames(audio, L)
+    assert ref.numel() in (T * 64, B * T * 64), (ref.shape, B, T)
+    rs = 0 if (ref.numel() == T * 64 and B > 1) else T * 64
+    loss = torch.empty(B, dtype=torch.float32, device=wav.device)
+    dwav = torch.empty(B, Lfull, dtype=torch.float32, device=wav.device)
+    _lib.check(lib.dmx_audio_guidance_fwd(audio, _p(wav), wav.stride(0), _p(mask), _p(ref), rs, None, _p(state), B, L, int(power2),
+                                          int(to_db), lo, hi, _stream()), "audio_guidance_fwd")
+    _lib.check(lib.dmx_audio_guidance_bwd(audio, _p(wav), wav.stride(0), _p(mask), _p(ref), rs, gscale, _p(loss), _p(dwav), Lfull, Lfull,
+                                          _p(state), B, L, int(power2), int(to_db), lo, hi, _stream()), "audio_guidance_bwd")
+    return loss, dwav
+
+
+def stft_mag_fwd(audio, wav, state, L):
+    lib = _lib.lib()
+    B = wav.shape[0]
+    mag = torch.empty(B, lib.dmx_audio_num_bins(audio), lib.dmx_audio_num_frames(audio, L), dtype=torch.float32, device=wav.device)
+    _lib.check(lib.dmx_audio_stft_mag(audio, _p(wav), wav.stride(0), _p(mag), _p(state), B, L, _stream()), "stft_mag")
+    return mag
+
+
+def stft_mag_bwd(audio, dmag, state, L, Lfull, *, dwav=None):
+    """dwav: caller-owned (B, >= L) result with any row stride (overwritten up to L; the op returns zeros past L)."""
+    B = dmag.shape[0]
+    if dwav is None:
+        dwav = torch.zeros(B, Lfull, dtype=torch.float32, device=dmag.device)
+    _lib.check(_lib.lib().dmx_audio_stft_mag_bwd(audio, _p(dmag), _p(dwav), dwav.stride(0), _p(state), B, L, 0, _stream()), "stft_mag_bwd")
+    return dwav
+
+
+def melscale_fwd(audio, mag, lo, hi, *, n_mels=64):
+    B, _, T = mag.shape
+    mel = torch.empty(B, T, n_mels, dtype=torch.float32, device=mag.device)
+    _lib.check(_lib.lib().dmx_audio_melscale(audio, _p(mag), _p(mel), B, T, lo, hi, _stream()), "melscale")
+    return mel
+
+
+# ---- networks (workspaces are caller-owned byte tensors sized by *_workspace_bytes)
+def unet_fwd(model, x, t, class_labels, ws, *, out_channels=None):
+    """out_channels: of the U-Net when they differ from x's (the op returns eps shaped like x)."""
+    B, Cin, h, w = x.shape
+    eps = torch.empty(B, out_channels or Cin, h, w, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_unet_fwd(model, _p(x), _p(t), _p(class_labels), _p(eps), B, h, w, _p(ws), ws.numel(), _stream()), "unet_fwd")
+    return eps
+
+
+def unet_fwd_ctx(model, x, t, class_labels, c0, c1, bias1, ws, *, out_channels=None):
+    B, Cin, h, w = x.shape
+    eps = torch.empty(B, out_channels or Cin, h, w, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_unet_fwd_ctx(model, _p(x), _p(t), _p(class_labels), _p(c0), c0.shape[1], _p(c1), c1.shape[1], _p(bias1),
+                                           _p(eps), B, h, w, _p(ws), ws.numel(), _stream()), "unet_fwd_ctx")
+    return eps
+
+
+def vae_dec_fwd(model, z, z_scale, keep_state, want_f32, scale_factor, ws):
+    """-> (mel 16-bit, mel fp32 or None)."""
+    B, _, h, w = z.shape
+    s = scale_factor
+    mel = torch.empty(B, h * s, w * s, dtype=_lib.act_dtype(), device=z.device)
+    mel32 = torch.empty(B, h * s, w * s, dtype=torch.float32, device=z.device) if want_f32 else None
+    _lib.check(_lib.lib().dmx_vae_decode_fwd(model, _p(z), z_scale, _p(mel), _p(mel32), B, h, w, int(keep_state), _p(ws), ws.numel(),
+                                             _stream()), "vae_decode_fwd")
+    return mel, mel32
+
+
+def vae_dec_bwd(model, dmel, z_scale, latent_channels, scale_factor):
+    B, H, W = dmel.shape
+    dz = torch.empty(B, latent_channels, H // scale_factor, W // scale_factor, dtype=torch.float32, device=dmel.device)
+    _lib.check(_lib.lib().dmx_vae_decode_bwd(model, _p(dmel), z_scale, _p(dz), _stream()), "vae_decode_bwd")
+    return dz
+
+
+def grad_normalize_(dwav, target):
+    """In place on dwav (B, samples): max |g| -> target per clip; returns the factors that undo it."""
+    inv_scale = torch.empty(dwav.shape[0], dtype=torch.float32, device=dwav.device)
+    _lib.check(_lib.lib().dmx_grad_normalize(_p(dwav), _p(inv_scale), dwav.shape[0], dwav.shape[1], target, _stream()), "grad_normalize")
+    return inv_scale
+
+
+def hifigan_fwd(model, mel, ws):
+    lib = _lib.lib()
+    B, T, _ = mel.shape
+    wav = torch.empty(B, lib.dmx_hifigan_out_len(model, T), dtype=torch.float32, device=mel.device)
+    _lib.check(lib.dmx_hifigan_fwd(model, _p(mel), _p(wav), B, T, _p(ws), ws.numel(), _stream()), "hifigan_fwd")
+    return wav
+
+
+def hifigan_bwd(model, dwav, frames, model_in_dim):
+    dmel = torch.empty(dwav.shape[0], frames, model_in_dim, dtype=_lib.act_dtype(), device=dwav.device)
+    _lib.check(_lib.lib().dmx_hifigan_bwd(model, _p(dwav), _p(dmel), _stream()), "hifigan_bwd")
+    return dmel
+
+
+# ---- CLAP HTS-AT tower of the style-guidance operator and the Gram matrix of its token features
+def htsat_fwd(model, mel, keep_state, ws):
+    lib = _lib.lib()
+    B, frames, _ = mel.shape
+    tokens, channels = C.c_int(), C.c_int()
+    _lib.check(lib.dmx_htsat_feature_dims(model, C.byref(tokens), C.byref(channels)), "htsat dims")
+    feat = torch.empty(B, tokens.value, channels.value, dtype=torch.float32, device=mel.device)
+    _lib.check(lib.dmx_htsat_fwd(model, _p(mel), B, frames, _p(feat), int(keep_state), _p(ws), ws.numel(), _stream()), "htsat_fwd")
+    return feat
+
+
+def htsat_bwd(model, dfeat, scale, frames, bins):
+    dmel = torch.empty(dfeat.shape[0], frames, bins, dtype=torch.float32, device=dfeat.device)
+    _lib.check(_lib.lib().dmx_htsat_bwd(model, _p(dfeat), _p(scale), _p(dmel), _stream()), "htsat_bwd")
+    return dmel
+
+
+def gram_fwd(feat):
+    B, T, Cc = feat.shape
+    g = torch.empty(B, Cc, Cc, dtype=torch.float32, device=feat.device)
+    _lib.check(_lib.lib().dmx_gram_fwd(_p(feat), _p(g), B, T, Cc, _stream()), "gram_fwd")
+    return g
+
+
+def gram_bwd(feat, dgram):
+    B, T, Cc = feat.shape
+    d = torch.empty_like(feat)
+    _lib.check(_lib.lib().dmx_gram_bwd(_p(feat), _p(dgram), _p(d), B, T, Cc, _stream()), "gram_bwd")
+    return d

@@ -1,12 +1,13 @@
 """Python handles over the native network executors (HiFi-GAN, VAE decoder, U-Net).
 
-Only plumbing lives here: device buffers come from torch (caching allocator), launches go to the
-C ABI on torch's current HIP stream -- through the PyTorch custom ops `torch.ops.diffmusic_hip.*`
-(csrc_torch/torch_ops.cpp; default) or through ctypes (DMX_TORCH_OPS=0), the same `extern "C"` launchers either way."""
+Only plumbing lives here: handle life cycle, weights, workspace sizing and input preparation.  Every launch is one
+`ops.hip.<name>` call (diffmusic_amd/ops.py), which picks the binding of the C ABI: the PyTorch custom ops
+`torch.ops.diffmusic_hip.*` (default) or ctypes, the same `extern "C"` launchers on torch's current HIP stream either way."""
 import ctypes as C
 import torch
 from . import _lib as L
 from . import ops
+from ._ctypes_ops import _stream
 from .weights import synth_state_dict
 
 HIFIGAN_DEFAULT = dict(model_in_dim=64, upsample_initial_channel=1024, upsample_rates=[5, 4, 2, 2, 2],
@@ -19,14 +20,6 @@ UNET_MUSICLDM_DEFAULT = dict(in_channels=8, out_channels=8, block_out_channels=[
                              down_attn=[0, 1, 1, 1], up_attn=[1, 1, 1, 0], class_embed_dim=512, attn_cross_dims=[0])
 # AudioLDM2UNet2DConditionModel: three transformers per layer (self, GPT-2 states 768, T5 states 1024), no class embedding
 UNET_AUDIOLDM2_DEFAULT = dict(UNET_MUSICLDM_DEFAULT, class_embed_dim=0, attn_cross_dims=[0, 768, 1024])
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def _fill(arr, vals):
@@ -142,20 +135,12 @@ class HifiGanEngine(_Engine):
         lib = L.lib()
         ws = self._workspace(("h", B, T), lib.dmx_hifigan_workspace_bytes(self._h, B, T))
         self._shape = (B, T)
-        if ops.enabled():
-            return ops.hip.hifigan_fwd(self._h.value, mel, ws)
-        wav = torch.empty(B, self.out_len(T), dtype=torch.float32, device=mel.device)
-        L.check(lib.dmx_hifigan_fwd(self._h, _ptr(mel), _ptr(wav), B, T, _ptr(ws), ws.numel(), _stream()), "hifigan_fwd")
-        return wav
+        return ops.hip.hifigan_fwd(self._h.value, mel, ws)
 
     def backward(self, dwav):
-        B, T = self._shape
+        _, T = self._shape
         assert dwav.dtype == torch.float32 and dwav.is_contiguous()
-        if ops.enabled():
-            return ops.hip.hifigan_bwd(self._h.value, dwav, T, self.cfg["model_in_dim"])
-        dmel = torch.empty(B, T, self.cfg["model_in_dim"], dtype=L.act_dtype(), device=dwav.device)
-        L.check(L.lib().dmx_hifigan_bwd(self._h, _ptr(dwav), _ptr(dmel), _stream()), "hifigan_bwd")
-        return dmel
+        return ops.hip.hifigan_bwd(self._h.value, dwav, T, self.cfg["model_in_dim"])
 
 
 class VaeDecoderEngine(_Engine):
@@ -192,25 +177,13 @@ class VaeDecoderEngine(_Engine):
         B, _, h, w = z.shape
         lib = L.lib()
         ws = self._workspace(("v", B, h, w), lib.dmx_vae_workspace_bytes(self._h, B, h, w))
-        s = self.scale_factor
         self._shape = (B, h, w)
-        if ops.enabled():
-            mel, mel32 = ops.hip.vae_dec_fwd(self._h.value, z, float(z_scale), bool(keep_state), bool(want_f32), s, ws)
-            return (mel, mel32) if want_f32 else mel
-        mel = torch.empty(B, h * s, w * s, dtype=L.act_dtype(), device=z.device)
-        mel32 = torch.empty(B, h * s, w * s, dtype=torch.float32, device=z.device) if want_f32 else None
-        L.check(lib.dmx_vae_decode_fwd(self._h, _ptr(z), float(z_scale), _ptr(mel), _ptr(mel32), B, h, w, int(keep_state),
-                                       _ptr(ws), ws.numel(), _stream()), "vae_decode_fwd")
+        mel, mel32 = ops.hip.vae_dec_fwd(self._h.value, z, float(z_scale), bool(keep_state), bool(want_f32), self.scale_factor, ws)
         return (mel, mel32) if want_f32 else mel
 
     def backward(self, dmel, z_scale=1.0):
-        B, h, w = self._shape
         assert dmel.dtype == L.act_dtype() and dmel.is_contiguous()
-        if ops.enabled():
-            return ops.hip.vae_dec_bwd(self._h.value, dmel, float(z_scale), self.cfg["latent_channels"], self.scale_factor)
-        dz = torch.empty(B, self.cfg["latent_channels"], h, w, dtype=torch.float32, device=dmel.device)
-        L.check(L.lib().dmx_vae_decode_bwd(self._h, _ptr(dmel), float(z_scale), _ptr(dz), _stream()), "vae_decode_bwd")
-        return dz
+        return ops.hip.vae_dec_bwd(self._h.value, dmel, float(z_scale), self.cfg["latent_channels"], self.scale_factor)
 
 
 class UNetEngine(_Engine):
@@ -247,15 +220,13 @@ class UNetEngine(_Engine):
         if class_labels is not None:
             class_labels = class_labels.to(device=dev, dtype=torch.float32).contiguous()
         lib = L.lib()
-        use_ops = ops.enabled() and self.cfg["out_channels"] == self.cfg["in_channels"]
-        eps = None if use_ops else torch.empty(B, self.cfg["out_channels"], h, w, dtype=torch.float32, device=dev)
+        out_ch = self.cfg["out_channels"]
+        eps_like_x = out_ch == self.cfg["in_channels"]       # what the op schema returns; any other U-Net has the ctypes spelling only
         if self._n_ctx == 0:
             ws = self._workspace(("u", B, h, w), lib.dmx_unet_workspace_bytes(self._h, B, h, w))
-            if use_ops:
+            if eps_like_x:
                 return ops.hip.unet_fwd(self._h.value, x, t, class_labels, ws)
-            L.check(lib.dmx_unet_fwd(self._h, _ptr(x), _ptr(t), _ptr(class_labels), _ptr(eps), B, h, w, _ptr(ws), ws.numel(),
-                                     _stream()), "unet_fwd")
-            return eps
+            return ops.ctypes_hip.unet_fwd(self._h.value, x, t, class_labels, ws, out_channels=out_ch)
         c0 = encoder_hidden_states.to(device=dev, dtype=torch.float32).contiguous()
         c1 = encoder_hidden_states_1.to(device=dev, dtype=torch.float32)
         m1 = encoder_attention_mask_1
@@ -268,11 +239,9 @@ class UNetEngine(_Engine):
         bias1 = ((1.0 - m1) * -10000.0).contiguous()
         n0, n1 = c0.shape[1], c1.shape[1]
         ws = self._workspace(("u", B, h, w, n0, n1), lib.dmx_unet_workspace_bytes_ctx(self._h, B, h, w, n0, n1))
-        if use_ops:
+        if eps_like_x:
             return ops.hip.unet_fwd_ctx(self._h.value, x, t, class_labels, c0, c1, bias1, ws)
-        L.check(lib.dmx_unet_fwd_ctx(self._h, _ptr(x), _ptr(t), _ptr(class_labels), _ptr(c0), n0, _ptr(c1), n1, _ptr(bias1), _ptr(eps),
-                                     B, h, w, _ptr(ws), ws.numel(), _stream()), "unet_fwd_ctx")
-        return eps
+        return ops.ctypes_hip.unet_fwd_ctx(self._h.value, x, t, class_labels, c0, c1, bias1, ws, out_channels=out_ch)
 
 
 HTSAT_DEFAULT = dict(spec_size=256, num_mel_bins=64, patch_size=4, patch_embeds_hidden_size=96, window_size=8, depths=[2, 2, 6, 2],
@@ -325,40 +294,22 @@ class HtsatEngine(_Engine):
         ws = self._workspace(("t", B, frames), nbytes)
         self._shape = (B, frames, mel.shape[2])
         self._mel = mel                          # the backward pass re-reads the input (its stage is recomputed, not taped)
-        if ops.enabled():
-            return ops.hip.htsat_fwd(self._h.value, mel, bool(keep_state), ws)
-        feat = torch.empty(B, self.tokens, self.channels, dtype=torch.float32, device=mel.device)
-        L.check(lib.dmx_htsat_fwd(self._h, _ptr(mel), B, frames, _ptr(feat), int(keep_state), _ptr(ws), ws.numel(), _stream()), "htsat_fwd")
-        return feat
+        return ops.hip.htsat_fwd(self._h.value, mel, bool(keep_state), ws)
 
     def backward(self, dfeat, scale=None):
         """dfeat (B, tokens, channels) fp32 -> d mel (B, frames, bins) fp32, times scale[b] when given."""
         B, frames, bins = self._shape
         assert dfeat.dtype == torch.float32 and dfeat.is_contiguous() and dfeat.shape == (B, self.tokens, self.channels)
-        if ops.enabled():
-            return ops.hip.htsat_bwd(self._h.value, dfeat, scale, frames, bins)
-        dmel = torch.empty(B, frames, bins, dtype=torch.float32, device=dfeat.device)
-        L.check(L.lib().dmx_htsat_bwd(self._h, _ptr(dfeat), _ptr(scale), _ptr(dmel), _stream()), "htsat_bwd")
-        return dmel
+        return ops.hip.htsat_bwd(self._h.value, dfeat, scale, frames, bins)
 
 
 def gram(feat):
     """G[b] = F[b]^T F[b] / T for token features F (B, T, C) fp32 cuda -> (B, C, C)."""
     assert feat.dtype == torch.float32 and feat.is_cuda and feat.is_contiguous()
-    B, T, Cc = feat.shape
-    if ops.enabled():
-        return ops.hip.gram_fwd(feat)
-    g = torch.empty(B, Cc, Cc, dtype=torch.float32, device=feat.device)
-    L.check(L.lib().dmx_gram_fwd(_ptr(feat), _ptr(g), B, T, Cc, _stream()), "gram_fwd")
-    return g
+    return ops.hip.gram_fwd(feat)
 
 
 def gram_backward(feat, dgram):
     """dF = F (dG + dG^T) / T."""
     assert dgram.dtype == torch.float32 and dgram.is_contiguous() and feat.is_contiguous()
-    B, T, Cc = feat.shape
-    if ops.enabled():
-        return ops.hip.gram_bwd(feat, dgram)
-    d = torch.empty_like(feat)
-    L.check(L.lib().dmx_gram_bwd(_ptr(feat), _ptr(dgram), _ptr(d), B, T, Cc, _stream()), "gram_bwd")
-    return d
+    return ops.hip.gram_bwd(feat, dgram)

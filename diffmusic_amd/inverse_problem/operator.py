@@ -21,14 +21,6 @@ from . import dsp
 _NEG, _POS = -3.0e38, 3.0e38
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
 class SpectralFrontend:
     """dmx_audio handle: STFT(n_fft, hop) + mel filterbank, forward and hand-written backward.
     Equivalent of torchaudio MelSpectrogram(+AmplitudeToDB) / MelScale / torch.stft in the reference."""
@@ -69,23 +61,17 @@ class SpectralFrontend:
         B = wav.shape[0]
         st = self._get_state(B, length, wav.device)
         self._last = (B, length, power2, to_db, lo, hi)
-        if ops.enabled() and out is None and self.n_mels == 64:
-            return ops.hip.logmel_fwd(self._h.value, wav, st, int(length), bool(power2), bool(to_db), float(lo), float(hi))
-        mel = out if out is not None else torch.empty(B, self.frames(length), self.n_mels, dtype=torch.float32, device=wav.device)
-        L.check(L.lib().dmx_audio_transform_fwd(self._h, _p(wav), wav.stride(0), _p(mel), _p(st), B, length, int(power2), int(to_db),
-                                                lo, hi, _stream()), "audio_transform_fwd")
-        self._last = (B, length, power2, to_db, lo, hi)
-        return mel
+        args = (self._h.value, wav, st, int(length), bool(power2), bool(to_db), float(lo), float(hi))
+        if out is None and self.n_mels == 64:                # the op allocates its (B, frames, 64) result
+            return ops.hip.logmel_fwd(*args)
+        return ops.ctypes_hip.logmel_fwd(*args, out=out, n_mels=self.n_mels)
 
     def transform_bwd(self, dmel, dwav=None):
         B, length, power2, to_db, lo, hi = self._last
-        if dwav is None and ops.enabled():
-            return ops.hip.logmel_bwd(self._h.value, dmel.contiguous(), self._state, int(length), bool(power2), bool(to_db), float(lo), float(hi))
+        args = (self._h.value, dmel.contiguous(), self._state, int(length), bool(power2), bool(to_db), float(lo), float(hi))
         if dwav is None:
-            dwav = torch.empty(B, length, dtype=torch.float32, device=dmel.device)
-        L.check(L.lib().dmx_audio_transform_bwd(self._h, _p(dmel), _p(dwav), dwav.stride(0), _p(self._state), B, length, int(power2),
-                                                int(to_db), lo, hi, 0, _stream()), "audio_transform_bwd")
-        return dwav
+            return ops.hip.logmel_bwd(*args)
+        return ops.ctypes_hip.logmel_bwd(*args, dwav=dwav)   # caller-owned (B, >= length) gradient, any row stride
 
     def fused(self, length):
         """True when the fused STFT -> mel kernels (csrc/stft_mel.hip: n_fft = 1024) cover this handle and clip length."""
@@ -93,65 +79,36 @@ class SpectralFrontend:
 
     def guidance(self, wav, length, ref, mask=None, power2=True, to_db=True, lo=_NEG, hi=_POS, gscale=1.0):
         """Fused guidance pair: loss[b] = ||ref[b] - transform(wav[b, :length] * mask)||_2 and dwav = gscale * dloss/dwav, (B, wav.shape[1])
-        with zeros past `length` -- one forward and one backward launch, no spectrum in HBM (torch.ops.diffmusic_hip.mel_guidance or
-        the ctypes binding of dmx_audio_guidance_{fwd,bwd})."""
+        with zeros past `length` -- one forward and one backward launch, no spectrum in HBM (dmx_audio_guidance_{fwd,bwd})."""
         assert wav.dtype == torch.float32 and wav.is_cuda and wav.stride(1) == 1 and ref.dtype == torch.float32 and ref.is_contiguous()
         B, full = wav.shape
         st = self._get_state(B, length, wav.device)
-        if ops.enabled():
-            return ops.hip.mel_guidance(self._h.value, wav, mask, ref, st, int(length), int(full), bool(power2), bool(to_db), float(lo),
-                                        float(hi), float(gscale))
-        T = self.frames(length)
-        assert ref.numel() in (T * self.n_mels, B * T * self.n_mels), (ref.shape, B, T)
-        rs = 0 if (ref.numel() == T * self.n_mels and B > 1) else T * self.n_mels
-        loss = torch.empty(B, dtype=torch.float32, device=wav.device)
-        dwav = torch.empty(B, full, dtype=torch.float32, device=wav.device)
-        lib = L.lib()
-        L.check(lib.dmx_audio_guidance_fwd(self._h, _p(wav), wav.stride(0), _p(mask), _p(ref), rs, None, _p(st), B, length, int(power2),
-                                           int(to_db), lo, hi, _stream()), "audio_guidance_fwd")
-        L.check(lib.dmx_audio_guidance_bwd(self._h, _p(wav), wav.stride(0), _p(mask), _p(ref), rs, gscale, _p(loss), _p(dwav), full, full,
-                                           _p(st), B, length, int(power2), int(to_db), lo, hi, _stream()), "audio_guidance_bwd")
-        return loss, dwav
+        return ops.hip.mel_guidance(self._h.value, wav, mask, ref, st, int(length), int(full), bool(power2), bool(to_db), float(lo),
+                                    float(hi), float(gscale))
 
     def stft_mag(self, wav, length):
         B = wav.shape[0]
         st = self._get_state(B, length, wav.device)
-        if ops.enabled():
-            return ops.hip.stft_mag_fwd(self._h.value, wav, st, int(length))
-        mag = torch.empty(B, self.bins, self.frames(length), dtype=torch.float32, device=wav.device)
-        L.check(L.lib().dmx_audio_stft_mag(self._h, _p(wav), wav.stride(0), _p(mag), _p(st), B, length, _stream()), "stft_mag")
-        return mag
+        return ops.hip.stft_mag_fwd(self._h.value, wav, st, int(length))
 
     def stft_mag_bwd(self, dmag, length, dwav):
         """dmag (B, bins, frames) w.r.t. the magnitude of the last stft_mag call -> dwav (B, >=length) (overwritten)."""
-        B = dmag.shape[0]
-        L.check(L.lib().dmx_audio_stft_mag_bwd(self._h, _p(dmag), _p(dwav), dwav.stride(0), _p(self._state), B, length, 0, _stream()),
-                "stft_mag_bwd")
-        return dwav
+        return ops.ctypes_hip.stft_mag_bwd(self._h.value, dmag, self._state, int(length), dwav.shape[1], dwav=dwav)
 
     def melscale(self, mag, lo=_NEG, hi=_POS):
-        B, _, T = mag.shape
-        if ops.enabled() and self.n_mels == 64:
+        if self.n_mels == 64:                                # the op allocates its (B, frames, 64) result
             return ops.hip.melscale_fwd(self._h.value, mag.contiguous(), float(lo), float(hi))
-        mel = torch.empty(B, T, self.n_mels, dtype=torch.float32, device=mag.device)
-        L.check(L.lib().dmx_audio_melscale(self._h, _p(mag.contiguous()), _p(mel), B, T, lo, hi, _stream()), "melscale")
-        return mel
+        return ops.ctypes_hip.melscale_fwd(self._h.value, mag.contiguous(), float(lo), float(hi), n_mels=self.n_mels)
 
 
 def l2_loss(ref, pred, want_grad=True, gscale=1.0):
     """per-clip ||ref - pred||_2 over all trailing dims; ref may have batch 1 (broadcast)."""
-    B = pred.shape[0]
-    n = pred[0].numel()
     ref = ref.contiguous()
-    assert ref[0].numel() == n, (ref.shape, pred.shape)
-    if ops.enabled() and pred.is_contiguous():
+    assert ref[0].numel() == pred[0].numel(), (ref.shape, pred.shape)
+    if pred.is_contiguous():                                 # the op takes contiguous tensors and always returns the gradient
         loss, dpred = ops.hip.l2norm(ref, pred, float(gscale))
         return loss, (dpred if want_grad else None)
-    loss = torch.empty(B, dtype=torch.float32, device=pred.device)
-    dpred = torch.empty_like(pred) if want_grad else None
-    L.check(L.lib().dmx_l2_loss(_p(ref), 0 if ref.shape[0] == 1 and B > 1 else n, _p(pred), _p(loss), _p(dpred), B, n, gscale,
-                                _stream()), "l2_loss")
-    return loss, dpred
+    return ops.ctypes_hip.l2norm(ref, pred, float(gscale), want_grad=want_grad)
 
 
 def _as_f32_cuda(x):
@@ -265,15 +222,10 @@ class IdentityOperator(_MelOperator):                     # operator.py:17-45
         return data
 
     def _a_fwd(self, wav, length):
-        y = torch.empty(wav.shape[0], length, dtype=torch.float32, device=wav.device)
-        L.check(L.lib().dmx_mask_apply(_p(wav), wav.stride(0), None, _p(y), length, wav.shape[0], length, length, _stream()), "copy")
-        return y
+        return ops.ctypes_hip.mask_mul(wav, None, length, length)
 
     def _a_bwd(self, dy, full):
-        B, n = dy.shape
-        d = torch.empty(B, full, dtype=torch.float32, device=dy.device)
-        L.check(L.lib().dmx_mask_apply(_p(dy), n, None, _p(d), full, B, n, full, _stream()), "copy")
-        return d
+        return ops.ctypes_hip.mask_mul(dy, None, dy.shape[1], full)
 
 
 class MusicInpaintingOperator(_MelOperator):              # operator.py:48-133
@@ -321,24 +273,17 @@ class MusicInpaintingOperator(_MelOperator):              # operator.py:48-133
 
     def forward(self, data, **kwargs):
         data = _as_f32_cuda(data)
-        B, n = data.shape
-        y = torch.empty(B, n, dtype=torch.float32, device=data.device)
-        L.check(L.lib().dmx_mask_apply(_p(data), data.stride(0), _p(self._mask_on(data.device)), _p(y), n, B, n, n, _stream()), "mask")
+        n = data.shape[1]
+        y = ops.ctypes_hip.mask_mul(data, self._mask_on(data.device), n, n)
         return self.noiser(y) if self.noiser is not None else y
 
     def _a_fwd(self, wav, length):
         if length != self.mask.shape[1]:
             raise ValueError(f"mask length {self.mask.shape[1]} != waveform length {length}")
-        y = torch.empty(wav.shape[0], length, dtype=torch.float32, device=wav.device)
-        L.check(L.lib().dmx_mask_apply(_p(wav), wav.stride(0), _p(self._mask_on(wav.device)), _p(y), length, wav.shape[0], length,
-                                       length, _stream()), "mask")
-        return y
+        return ops.ctypes_hip.mask_mul(wav, self._mask_on(wav.device), length, length)
 
     def _a_bwd(self, dy, full):
-        B, n = dy.shape
-        d = torch.empty(B, full, dtype=torch.float32, device=dy.device)
-        L.check(L.lib().dmx_mask_apply(_p(dy), n, _p(self._mask_on(dy.device)), _p(d), full, B, n, full, _stream()), "mask_bwd")
-        return d
+        return ops.ctypes_hip.mask_mul(dy, self._mask_on(dy.device), dy.shape[1], full)
 
 
 class PhaseRetrievalOperator(BaseOperator):               # operator.py:136-171
@@ -378,24 +323,12 @@ class PhaseRetrievalOperator(BaseOperator):               # operator.py:136-171
 
 
 def _fir_fwd(x, x_len, h, out_len, orig, new, off):
-    B = x.shape[0]
-    if ops.enabled():
-        return ops.hip.resample_fwd(x, h, int(x_len), int(out_len), int(orig), int(new), int(off))
-    y = torch.empty(B, out_len, dtype=torch.float32, device=x.device)
-    L.check(L.lib().dmx_fir_fwd(_p(x), x.stride(0), _p(h), _p(y), out_len, B, x_len, out_len, h.shape[-1], orig, new, off, _stream()),
-            "fir_fwd")
-    return y
+    return ops.hip.resample_fwd(x, h, int(x_len), int(out_len), int(orig), int(new), int(off))
 
 
 def _fir_bwd(dy, h, h_rev, in_len, full_len, orig, new, off):
     """gradient w.r.t. the first in_len samples of a (B, full_len) input; the tail gets zero."""
-    B, out_len = dy.shape
-    if ops.enabled():
-        return ops.hip.resample_bwd(dy.contiguous(), h, h_rev, int(in_len), int(full_len), int(orig), int(new), int(off))
-    d = torch.zeros(B, full_len, dtype=torch.float32, device=dy.device)
-    L.check(L.lib().dmx_fir_bwd(_p(dy), out_len, _p(h), _p(h_rev), _p(d), full_len, B, in_len, out_len, h.shape[-1], orig, new, off,
-                                _stream()), "fir_bwd")
-    return d
+    return ops.hip.resample_bwd(dy.contiguous(), h, h_rev, int(in_len), int(full_len), int(orig), int(new), int(off))
 
 
 class SuperResolutionOperator(_MelOperator):              # operator.py:174-205
@@ -550,9 +483,7 @@ class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 
         B = g.shape[0]
         loss, dg = l2_loss(ref.reshape(ref.shape[0], -1), g.reshape(B, -1))
         df = gram_backward(f, dg.reshape(g.shape))
-        inv_scale = torch.empty(B, dtype=torch.float32, device=f.device)
-        dfl = df.reshape(B, -1)
-        L.check(L.lib().dmx_grad_normalize(_p(dfl), _p(inv_scale), B, dfl.shape[1], 64.0, _stream()), "grad_normalize")
+        inv_scale = ops.ctypes_hip.grad_normalize_(df.reshape(B, -1), 64.0)          # in place on df
         return loss, self.engine.backward(df, scale=inv_scale)[:, None]
 
     @torch.no_grad()
@@ -565,9 +496,7 @@ class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 
         y = wav                                                                    # forward = identity on the vocoder output
         if supervised_space == "wav_form":
             m32 = self._ref(measurement, "wav_form", lambda m: m.reshape(m.shape[0], -1).contiguous())
-            yl = torch.empty(wav.shape[0], length, dtype=torch.float32, device=wav.device)
-            L.check(L.lib().dmx_mask_apply(_p(wav), wav.stride(0), None, _p(yl), length, wav.shape[0], length, length, _stream()), "copy")
-            loss, dy = l2_loss(m32, yl)
+            loss, dy = l2_loss(m32, ops.ctypes_hip.mask_mul(wav, None, length, length))
             d = torch.zeros(wav.shape[0], wav.shape[1], dtype=torch.float32, device=wav.device)
             d[:, :length] = dy
             return loss, d

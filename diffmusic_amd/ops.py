@@ -4,26 +4,30 @@ compiled from csrc_torch/torch_ops.cpp into lib/libdiffmusic_torch_ops.so and lo
     from diffmusic_amd import ops
     prev, x0 = ops.hip.sched_update(1, x, eps, x0, g0, inv_scale, None, a_t, a_p, sigma, rate, 1e-8, False)
 
-The facades (`Scheduler.step`, `Pipeline.__call__`, the operators) may call either this layer or the ctypes binding of the
-same entry points (`_lib.py`); both end in the same `extern "C"` launchers on torch's current HIP stream.  By default the
-facade's per-step device work goes through this layer: the network stages (U-Net, VAE decode forward / backward, HiFi-GAN
-forward / backward: diffmusic_amd/engine.py), the gradient rescale and the scheduler arithmetic (x0 prediction, CFG combine,
-fused update).  DMX_TORCH_OPS=0 switches those calls to the ctypes binding; so does an op library that cannot be loaded
-(missing, or built against another torch): one warning, then ctypes -- the same HIP kernels either way.  Neither binding has a
+The facades (`Scheduler.step`, `Pipeline.__call__`, the operators, the engines) call `ops.hip.<name>` and nothing else: it resolves,
+per call, to `torch.ops.diffmusic_hip.<name>` (default) or to the ctypes function of the same name and positional signature
+(`_ctypes_ops.py`, also exposed as `ops.ctypes_hip`); both end in the same `extern "C"` launchers on torch's current HIP stream.
+DMX_TORCH_OPS=0 selects the ctypes binding; so does DMX_LIB_PATH (a dev build of libdiffmusic_hip.so: the op library links the
+in-tree one) and an op library that cannot be loaded (missing, or built against another torch): one warning, then ctypes -- the
+same HIP kernels either way.  This module is the only place that knows which binding carries a launch.  A facade names
+`ops.ctypes_hip.<name>` itself only where its inputs need what the op schema cannot express (the keyword-only parameters of
+`_ctypes_ops.py`: caller-owned or strided outputs, prediction type / clip range, 64-bit Philox seeds).  Neither binding has a
 CPU fallback: without libdiffmusic_hip.so everything raises."""
+import inspect
 import os
 import warnings
 
 import torch
+
+from . import _ctypes_ops as ctypes_hip
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libdiffmusic_torch_ops.so")
 USE_TORCH_OPS = os.environ.get("DMX_TORCH_OPS", "1") not in ("", "0")
 _loaded = False
 
-OP_NAMES = ("sched_pred_x0", "cfg_combine", "sched_update", "randn_philox", "mask_mul", "l2norm", "resample_fwd", "resample_bwd",
-            "logmel_fwd", "logmel_bwd", "stft_mag_fwd", "stft_mag_bwd", "melscale_fwd", "unet_fwd", "unet_fwd_ctx", "vae_dec_fwd",
-            "vae_dec_bwd", "hifigan_fwd", "hifigan_bwd", "grad_normalize_", "mel_guidance", "abi_version")
+# every registered op has a ctypes function of its name (tests/test_abi.py compares the two signatures)
+OP_NAMES = tuple(n for n, f in vars(ctypes_hip).items() if inspect.isfunction(f) and not n.startswith("_"))
 _usable = None
 
 
@@ -65,8 +69,10 @@ def enabled():
 
 
 class _Hip:
+    """`ops.hip.<name>`: the op of that name in the binding that is in force for this call."""
+
     def __getattr__(self, name):
-        return getattr(load(), name)
+        return getattr(load() if enabled() else ctypes_hip, name)
 
 
 hip = _Hip()

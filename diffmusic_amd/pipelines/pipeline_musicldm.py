@@ -15,22 +15,15 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from .. import _lib as L
 from .. import ops
 from ..engine import HifiGanEngine, UNetEngine, VaeDecoderEngine
 from ..torch_utils import randn_tensor
 from ..profiling import stage
 from .. import parallel
 
-import ctypes as C
-
 
 class AudioPipelineOutput(SimpleNamespace):
     pass
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class MusicLDMPipeline:
@@ -153,12 +146,7 @@ class MusicLDMPipeline:
                 return self.unet.forward(x, torch.full((B,), float(t_host), device=dev), **half)   # uncond + s*(text-uncond) == text
             x2 = torch.cat([x, x], dim=0)
             eps2 = self.unet.forward(x2, torch.full((2 * B,), float(t_host), device=dev), **cond)
-            if ops.enabled():
-                return ops.hip.cfg_combine(eps2, float(guidance_scale))          # torch.ops.diffmusic_hip.cfg_combine
-            out = torch.empty_like(x)
-            L.check(L.lib().dmx_sched_cfg_combine(C.c_void_p(eps2.data_ptr()), C.c_void_p(out.data_ptr()), out.numel(),
-                                                  float(guidance_scale), _stream()), "cfg_combine")
-            return out
+            return ops.hip.cfg_combine(eps2, float(guidance_scale))
 
     # ---- the call ---------------------------------------------------------------------------
     @torch.no_grad()

@@ -7,12 +7,10 @@ Host side = DDIM tables and per-step scalars (fp32, computed once; no device syn
 Device side = HIP: x0 prediction, VAE decode, HiFi-GAN, measurement operator, mel, L2 loss, the
 hand-written backward sweep and the fused update kernel (csrc/sched.hip).  There is no autograd and
 no CPU fallback."""
-import ctypes as C
 from types import SimpleNamespace
 import numpy as np
 import torch
 
-from .. import _lib as L
 from .. import ops
 from ..torch_utils import randn_tensor, randn_philox
 from ..profiling import stage
@@ -30,14 +28,6 @@ def rescale_zero_terminal_snr(betas):
     alphas_bar = alphas_bar_sqrt ** 2
     alphas = torch.cat([alphas_bar[0:1], alphas_bar[1:] / alphas_bar[:-1]])
     return 1.0 - alphas
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 class GuidedDDIMScheduler:
@@ -153,12 +143,7 @@ class GuidedDDIMScheduler:
                 total = torch.linalg.vector_norm(loss)
                 dwav.mul_((loss / total.clamp_min(1e-30))[:, None])
                 loss = total.reshape(1)
-            if ops.enabled():
-                inv_scale = ops.hip.grad_normalize_(dwav, float(self.grad_target))       # in place on dwav
-            else:
-                inv_scale = torch.empty(x0.shape[0], dtype=torch.float32, device=x0.device)
-                L.check(L.lib().dmx_grad_normalize(_p(dwav), _p(inv_scale), dwav.shape[0], dwav.shape[1], self.grad_target, _stream()),
-                        "grad_normalize")
+            inv_scale = ops.hip.grad_normalize_(dwav, float(self.grad_target))           # in place on dwav
         with stage("hifigan_bwd"):
             dmel = vocoder.backward(dwav)
         with stage("vae_bwd"):
@@ -184,18 +169,13 @@ class GuidedDDIMScheduler:
         t, a_t, a_p, sigma = self._scalars(timestep, eta)
         x = sample.detach().to(torch.float32).contiguous()
         e = model_output.detach().to(torch.float32).contiguous()
-        B, n = x.shape[0], x[0].numel()
-        lib = L.lib()
-        plain = self._ptype == 0 and self._clip_r == 0.0          # epsilon prediction, no clipping: the reference's configs
-        if not plain:
-            # the DDIM parent's other branches (sample / v_prediction, clip_sample); C-ABI entry points with the type and the clip range
-            x0 = torch.empty_like(x)
-            L.check(lib.dmx_sched_pred_x0_ex(_p(x), _p(e), _p(x0), x.numel(), a_t, self._ptype, self._clip_r, _stream()), "pred_x0_ex")
-        elif ops.enabled():
-            x0 = ops.hip.sched_pred_x0(x, e, a_t)                  # torch.ops.diffmusic_hip.* (csrc_torch/torch_ops.cpp)
+        # epsilon prediction, no clipping: the reference's configs, and what the op schemas express.  The DDIM parent's other branches
+        # (sample / v_prediction, clip_sample) are C-ABI entry points that take the type and the clip range: the ctypes spelling only.
+        plain = self._ptype == 0 and self._clip_r == 0.0
+        if plain:
+            x0 = ops.hip.sched_pred_x0(x, e, a_t)
         else:
-            x0 = torch.empty_like(x)
-            L.check(lib.dmx_sched_pred_x0(_p(x), _p(e), _p(x0), x.numel(), a_t, _stream()), "pred_x0")
+            x0 = ops.ctypes_hip.sched_pred_x0(x, e, a_t, ptype=self._ptype, clip_r=self._clip_r)
         mode = _MODE[self.mode]
         noise = None
         if self.mode in ("dps", "mpgd") and eta > 0:
@@ -219,25 +199,12 @@ class GuidedDDIMScheduler:
                     sn = randn_tensor(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
                 noise = sn.to(torch.float32).contiguous()
         grad_out = torch.empty_like(x) if self.debug_keep_grad and self.mode != "ddim" else None
-        if not plain:
-            prev = torch.empty_like(x)
-            x0_out = torch.empty_like(x) if self.mode == "mpgd" else None
-            with stage("sched_update"):
-                L.check(lib.dmx_sched_step_ex(mode, _p(x), _p(e), _p(x0), _p(g0), _p(inv_scale), _p(noise), _p(prev), _p(x0_out),
-                                              _p(grad_out), B, n, a_t, a_p, sigma, float(rate), float(eps), 0 if self.per_clip_norm else 1,
-                                              self._ptype, self._clip_r, _stream()), "sched_step_ex")
-        elif ops.enabled() and grad_out is None:
-            with stage("sched_update"):
-                prev, x0_u = ops.hip.sched_update(mode, x, e, x0, g0, inv_scale, noise, a_t, a_p, sigma, float(rate), float(eps),
-                                                  not self.per_clip_norm)
-            x0_out = x0_u if self.mode == "mpgd" else None
-        else:
-            prev = torch.empty_like(x)
-            x0_out = torch.empty_like(x) if self.mode == "mpgd" else None
-            with stage("sched_update"):
-                L.check(lib.dmx_sched_step(mode, _p(x), _p(e), _p(x0), _p(g0), _p(inv_scale), _p(noise), _p(prev), _p(x0_out),
-                                           _p(grad_out), B, n, a_t, a_p, sigma, float(rate), float(eps), 0 if self.per_clip_norm else 1,
-                                           _stream()), "sched_step")
+        upd = (mode, x, e, x0, g0, inv_scale, noise, a_t, a_p, sigma, float(rate), float(eps), not self.per_clip_norm)
+        with stage("sched_update"):
+            if plain and grad_out is None:
+                prev, x0_out = ops.hip.sched_update(*upd)          # x0_out: MPGD's guided x0, None for every other mode
+            else:
+                prev, x0_out = ops.ctypes_hip.sched_update(*upd, ptype=self._ptype, clip_r=self._clip_r, grad_out=grad_out)
         self.last_grad = grad_out
         if loss.numel() == 1 and self.mode != "ddim":
             loss = loss.reshape(())

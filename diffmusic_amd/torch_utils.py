@@ -28,16 +28,8 @@ def randn_philox(shape, seeds, offset=0, device="cuda"):
     `offset` counts Philox blocks (4 normals each) already consumed -- advance it by ceil(n / 4) per draw.  Opt-in
     replacement for `randn_tensor` on the per-step noise of DSG / DiffMusic (no host draw, no H2D copy); the values do not
     match torch's generators, but they depend only on (seed_b, offset, element), never on the batch or the GPU count."""
-    import ctypes as C
-    from . import _lib as L
-    B = int(shape[0])
-    n = 1
-    for d in shape[1:]:
-        n *= int(d)
-    if len(seeds) != B:
-        raise ValueError(f"need one seed per clip: got {len(seeds)} for batch {B}")
-    out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
-    arr = (C.c_ulonglong * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds])
-    L.check(L.lib().dmx_randn_philox(C.c_void_p(out.data_ptr()), B, n, arr, int(offset) & 0xFFFFFFFFFFFFFFFF,
-                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)), "randn_philox")
-    return out
+    from . import ops
+    if len(seeds) != int(shape[0]):
+        raise ValueError(f"need one seed per clip: got {len(seeds)} for batch {int(shape[0])}")
+    # the op's int[] seeds are signed 64-bit and its batch is capped at 64; the ctypes spelling takes any seed modulo 2^64
+    return ops.ctypes_hip.randn_philox(shape, seeds, offset, device)

@@ -75,3 +75,26 @@ def test_torch_op_library_loads_and_registers_every_stage_op(monkeypatch, tmp_pa
     monkeypatch.setattr(ops, "LIB_PATH", str(tmp_path / "nope.so"))
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         ops.load()
+
+
+def test_ctypes_ops_have_the_positional_signatures_of_the_registered_ops():
+    """The two bindings are one surface: every op registered in csrc_torch/torch_ops.cpp has a function of its name in
+    diffmusic_amd/_ctypes_ops.py whose positional parameters are the schema's arguments, in order and by name; whatever else the
+    ctypes function takes is keyword-only and has a default, so a call written for the op is a call of the function."""
+    import inspect
+    from diffmusic_amd.build import build_torch_ops
+    from diffmusic_amd import ops
+    assert os.path.exists(build_torch_ops())
+    h = ops.load()
+    src = open(os.path.join(ROOT, "diffmusic_amd", "csrc_torch", "torch_ops.cpp")).read()
+    registered = re.findall(r'm\.def\("([A-Za-z0-9_]+)\(', src)
+    assert len(registered) >= 26 and len(set(registered)) == len(registered)
+    assert sorted(registered) == sorted(ops.OP_NAMES)
+    P = inspect.Parameter
+    for name in ops.OP_NAMES:
+        want = [a.name for a in getattr(h, name).default._schema.arguments]
+        params = list(inspect.signature(getattr(ops.ctypes_hip, name)).parameters.values())
+        assert [p.name for p in params if p.kind == P.POSITIONAL_OR_KEYWORD] == want, name
+        assert all(p.default is P.empty for p in params if p.kind == P.POSITIONAL_OR_KEYWORD), name
+        extra = [p for p in params if p.kind != P.POSITIONAL_OR_KEYWORD]
+        assert all(p.kind == P.KEYWORD_ONLY and p.default is not P.empty for p in extra), name

@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 
 from tests.golden.cases import CASES, SCHED_CFG, L, SR            # noqa: E402
 from tests.golden.toy import ToyVae, ToyVocoder                   # noqa: E402
+from diffmusic_amd._ctypes_ops import _p                          # noqa: E402
 
 _MODE = dict(ddim=0, dps=1, mpgd=2, dsg=3, diffmusic=4)
 
@@ -27,10 +28,6 @@ def _oracle_op(task):
     if task == "phase_retrieval":
         return O.PhaseRetrievalOperator(noiser=n)
     return O.SuperResolutionOperator(SR, 2, noiser=n)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 @pytest.mark.parametrize("ci", range(len(CASES)))

@@ -6,11 +6,9 @@ import ctypes as C
 import pytest
 import torch
 
+from diffmusic_amd._ctypes_ops import _p
+
 pytestmark = pytest.mark.gpu
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def test_scheduler_ops_equal_ctypes_path():
