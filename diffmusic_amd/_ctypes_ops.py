@@ -142,6 +142,35 @@ def mel_guidance(audio, wav, mask, ref, state, L, Lfull, power2, to_db, lo, hi, 
     return loss, dwav
 
 
+def mel_guidance_noisy(audio, wav, mask, ref, state, L, Lfull, power2, to_db, lo, hi, gscale, noise, noise_mag, sigma):
+    """mel_guidance with the step's measurement noise: noise (B, >= L) in the sample domain (y = wav * mask + sigma * noise) and / or
+    noise_mag (B, bins, frames) on the magnitudes (power2 False only); standard-normal draws, either may be None."""
+    lib = _lib.lib()
+    B = wav.shape[0]
+    T = lib.dmx_audio_num_frames(audio, L)
+    assert ref.numel() in (T * 64, B * T * 64), (ref.shape, B, T)
+    assert noise is None or (noise.shape[0] == B and noise.shape[1] >= L and noise.stride(1) == 1), noise.shape
+    assert noise_mag is None or (noise_mag.is_contiguous() and noise_mag.numel() == B * lib.dmx_audio_num_bins(audio) * T), noise_mag.shape
+    rs = 0 if (ref.numel() == T * 64 and B > 1) else T * 64
+    ns = noise.stride(0) if noise is not None else 0
+    loss = torch.empty(B, dtype=torch.float32, device=wav.device)
+    dwav = torch.empty(B, Lfull, dtype=torch.float32, device=wav.device)
+    _lib.check(lib.dmx_audio_guidance_fwd_ex(audio, _p(wav), wav.stride(0), _p(mask), _p(ref), rs, None, _p(state), B, L, int(power2),
+                                             int(to_db), lo, hi, _p(noise), ns, _p(noise_mag), sigma, _stream()), "audio_guidance_fwd_ex")
+    _lib.check(lib.dmx_audio_guidance_bwd_ex(audio, _p(wav), wav.stride(0), _p(mask), _p(ref), rs, gscale, _p(loss), _p(dwav), Lfull, Lfull,
+                                             _p(state), B, L, int(power2), int(to_db), lo, hi, _p(noise), ns, _p(noise_mag), sigma, _stream()),
+               "audio_guidance_bwd_ex")
+    return loss, dwav
+
+
+def noise_add(y, noise, sigma):
+    """-> y + sigma * noise (new tensor; y and noise contiguous, same number of elements)."""
+    assert y.is_contiguous() and noise.is_contiguous() and y.numel() == noise.numel(), (y.shape, noise.shape)
+    out = torch.empty_like(y)
+    _lib.check(_lib.lib().dmx_noise_add(_p(y), _p(noise), _p(out), y.numel(), sigma, _stream()), "noise_add")
+    return out
+
+
 def stft_mag_fwd(audio, wav, state, L):
     lib = _lib.lib()
     B = wav.shape[0]

@@ -8,6 +8,17 @@
 //     (u0,u1,u2,u3) = philox4x32_10(counter = (lo32(blk), hi32(blk), 0, 0), key = (lo32(seed), hi32(seed)))
 //     n0 = r(u0) cos(2 pi v(u1)), n1 = r(u0) sin(2 pi v(u1)), n2, n3 likewise from (u2, u3)
 //     r(u) = sqrt(-2 ln((u + 1) / 2^32)),  v(u) = u / 2^32
+//
+// Two consumers draw from this kernel, possibly under the same generator seeds, and their streams are disjoint by KEY:
+//   sampler noise (schedulers, device_noise=True):      key = seed_b,                        offset = blocks consumed so far
+//   measurement noise (inverse_problem/noise.py):       key = seed_b ^ 0x6D6561735F6E6F69,   offset = step_index << 32   (stream="clip")
+//                                                       key = one draw from torch's global generator ^ the same constant,
+//                                                       offset = blocks consumed so far                                  (stream="global")
+// Philox is a keyed bijection of the counter: two different keys give unrelated sequences, so the measurement noise of clip b never
+// repeats values of its sampler noise whatever the offsets are.  Within the clip stream the step index sits in the high counter word
+// and the element block in the low one (a clip's A(x) has far fewer than 2^34 elements), so steps do not overlap either.
+// dmx_noise_add below applies a draw to a materialised measurement: out = y + sigma * z (the `self.noiser(...)` that ends every
+// operator's forward in the reference, diffmusic/inverse_problem/operator.py:132-133 and siblings, noise.py:13-18).
 #include "dmx_common.h"
 #include "kernels.h"
 
@@ -52,7 +63,33 @@ __global__ void randn_philox_kernel(float* __restrict__ out, long long n, Philox
   }
 }
 
+// out = y + scale * z, float4 body (when all three pointers allow it) and a scalar tail
+__global__ void noise_add_kernel(const float* __restrict__ y, const float* __restrict__ z, float* __restrict__ out, long long n, float scale,
+                                 int vec) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (vec) {
+    const long long n4 = n >> 2;
+    if (i < n4) {
+      const float4 a = reinterpret_cast<const float4*>(y)[i], b = reinterpret_cast<const float4*>(z)[i];
+      reinterpret_cast<float4*>(out)[i] = make_float4(__fmaf_rn(scale, b.x, a.x), __fmaf_rn(scale, b.y, a.y), __fmaf_rn(scale, b.z, a.z),
+                                                      __fmaf_rn(scale, b.w, a.w));
+    }
+    const long long t = (n4 << 2) + i;
+    if (i < 4 && t < n) out[t] = __fmaf_rn(scale, z[t], y[t]);
+  } else if (i < n) {
+    out[i] = __fmaf_rn(scale, z[i], y[i]);
+  }
+}
+
 }  // namespace
+
+extern "C" int dmx_noise_add(const float* y, const float* z, float* out, long long n, float scale, void* stream) {
+  if (!y || !z || !out || n < 1) return DMX_ERR_SHAPE;
+  const int vec = ((((uintptr_t)y) | ((uintptr_t)z) | ((uintptr_t)out)) & 15) == 0 ? 1 : 0;
+  const long long threads = vec ? (n >> 2 > 4 ? n >> 2 : 4) : n;
+  hipLaunchKernelGGL(noise_add_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, z, out, n, scale, vec);
+  return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
+}
 
 extern "C" int dmx_randn_philox(float* out, int batch, long long n, const unsigned long long* seeds_host, unsigned long long offset,
                                 void* stream) {

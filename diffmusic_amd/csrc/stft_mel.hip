@@ -5,7 +5,8 @@
 // torch.linalg.norm(transform(y) - transform(A(x))) and torch.autograd.grad through all of it in
 // diffmusic/schedulers/scheduling_dps.py:202-212.
 //
-// One wave owns one frame at a time: 1024 windowed samples (reflect padding and the optional measurement mask applied on load,
+// One wave owns one frame at a time: 1024 windowed samples (reflect padding, the optional measurement mask and the optional
+// measurement noise -- sigma * z[b][s], z drawn once per step by rng.hip -- applied on load,
 // 256-byte coalesced reads, the next frame's samples fetched under this frame's arithmetic; neighbouring frames overlap by 86 % and
 // are served by L2) go through an in-place radix-4 Stockham FFT in LDS (five passes), |X|^2 stays in LDS, the mel filterbank is applied from a compacted table
 // (the <= 2 % non-zero weights of the triangular bank, one mel column per lane, 256-byte reads) and the dB / clamp tail runs in
@@ -33,6 +34,11 @@ constexpr int PADH = NF / 2;        // reflect padding on each side (center=True
 struct SmParams {
   const float* wav; long long wav_stride;
   const float* mask;                 // optional (L): y = wav * mask (the inpainting operator, operator.py:126-128)
+  // measurement noise inside the step (the `self.noiser(...)` that ends every operator's forward, operator.py:132-133 ... :270-271):
+  // standard-normal draws made once per step (rng.hip), scaled by nscale = sigma on load.  Additive and independent of wav: no backward term.
+  const float* add; long long add_stride;      // optional (B, >= L), sample domain: y = wav * mask + nscale * add
+  const float* addmag;               // optional (B, 513, T), magnitude domain (!power2 only): |X| + nscale * addmag (phase retrieval, operator.py:170-171)
+  float nscale;
   const float* ref; long long ref_stride;      // reference mel (B or 1, T, 64); stride 0 = one reference for every clip
   const float* dmel;                 // backward: explicit d(loss)/d(mel) (B, T, 64) instead of the L2 gradient against ref
   float* mel_out;                    // forward: (B, T, 64) or null
@@ -114,16 +120,19 @@ __device__ __forceinline__ void fft1024(float2* buf, const float2* s_tw, int lan
   fft_pass<256, INV>(buf, s_tw, lane);
 }
 
-// masked, reflect-padded samples n = lane + 64 j of frame f of clip b -> registers (frames past the end: zeros, nothing is read)
+// masked (+ noisy), reflect-padded samples n = lane + 64 j of frame f of clip b -> registers (frames past the end: zeros, nothing is
+// read).  Forward and backward both load through here, so they see the same y; the noise belongs to sample s, so a padded position
+// carries the noise of the sample it mirrors (the reference pads the already noisy signal inside torch.stft).
 __device__ __forceinline__ void fetch_frame(const SmParams& P, int b, int f, float (&x)[16], int lane) {
   const float* w = P.wav + (long long)b * P.wav_stride;
+  const float* z = P.add ? P.add + (long long)b * P.add_stride : nullptr;
   const int p0 = f * P.hop - PADH;
   const bool live = f < P.T;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const int s = fold_reflect(p0 + lane + 64 * j, P.L);
     float v = 0.f;
-    if (live) { v = w[s]; if (P.mask) v *= P.mask[s]; }
+    if (live) { v = w[s]; if (P.mask) v *= P.mask[s]; if (z) v = __fmaf_rn(P.nscale, z[s], v); }
     x[j] = v;
   }
 }
@@ -134,8 +143,10 @@ __device__ __forceinline__ void put_frame(const float (&x)[16], const float (&wi
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 }
 
-// |X|^2 (or |X|) of the 513 one-sided bins -> pw[k]; then mel column `lane`: v = sum_k fb[k][lane] * pw[k]
-__device__ __forceinline__ float power_and_mel(const SmParams& P, const float2* buf, float* pw, int lane) {
+// |X|^2 (or |X|, plus the magnitude-domain noise of frame f of clip b) of the 513 one-sided bins -> pw[k]; then mel column `lane`:
+// v = sum_k fb[k][lane] * pw[k]
+__device__ __forceinline__ float power_and_mel(const SmParams& P, const float2* buf, float* pw, int lane, int b, int f) {
+  const float* zm = (P.addmag && !P.power2) ? P.addmag + (long long)b * NB * P.T + f : nullptr;
 #pragma unroll
   for (int j = 0; j < 9; ++j) {
     const int k = lane + 64 * j;
@@ -143,6 +154,7 @@ __device__ __forceinline__ float power_and_mel(const SmParams& P, const float2* 
       const float2 x = buf[k];
       float p = x.x * x.x + x.y * x.y;
       if (!P.power2) p = sqrtf(p);
+      if (zm) p = __fmaf_rn(P.nscale, zm[(long long)k * P.T], p);
       pw[k] = p;
     }
   }
@@ -186,7 +198,7 @@ __global__ __launch_bounds__(256) void stft_mel_fwd_kernel(const SmParams P) {
     put_frame(xs, win, buf, lane);
     if (i + 1 < FWD_FPW) fetch_frame(P, b, f + 4, xs, lane);      // in flight under this frame's FFT
     fft1024<false>(buf, s_tw, lane);
-    const float v = power_and_mel(P, buf, pw, lane);
+    const float v = power_and_mel(P, buf, pw, lane, b, f);
     const float o = mel_tail(P, v);
     const long long idx = ((long long)b * P.T + f) * NM + lane;
     if (P.mel_out) P.mel_out[idx] = o;
@@ -261,7 +273,7 @@ __global__ __launch_bounds__(256) void stft_mel_bwd_kernel(const SmParams P) {
     put_frame(xs, win, buf, lane);
     if (f + 4 <= fhi) fetch_frame(P, b, f + 4, xs, lane);         // in flight under this frame's two FFTs
     fft1024<false>(buf, s_tw, lane);
-    const float v = power_and_mel(P, buf, pw, lane);
+    const float v = power_and_mel(P, buf, pw, lane, b, f);
     // d(loss)/d(mel_out) -> d/d(mel_lin): clamp passes the gradient inside (lo, hi) only, dB is 10 / ln 10 / v above the 1e-10 floor
     const long long idx = ((long long)b * P.T + f) * NM + lane;
     const float o_raw = P.to_db ? 10.f * log10f(fmaxf(v, 1e-10f)) : v;
@@ -285,7 +297,8 @@ __global__ __launch_bounds__(256) void stft_mel_bwd_kernel(const SmParams P) {
         if (P.power2) {
           g = make_float2(2.f * dp * x.x, 2.f * dp * x.y);
         } else {
-          const float mag = pw[k];
+          // the divisor is the clean |X| (d|X|/dX = X / |X|); pw[k] carries the noisy magnitude that the mel sum and the loss saw
+          const float mag = P.addmag ? sqrtf(x.x * x.x + x.y * x.y) : pw[k];
           const float c = mag > 0.f ? dp / mag : 0.f;
           g = make_float2(c * x.x, c * x.y);
         }
@@ -337,27 +350,31 @@ static void fill_common(SmParams& P, const DmxStftMelTables& t, int B, int L, in
 int dmx_stft_mel_parts(int L, int hop) { return cdiv(1 + L / hop, 4 * FWD_FPW); }
 
 int dmx_stft_mel_fwd(const DmxStftMelTables& t, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
-                     float* mel_out, float* partial, int B, int L, int hop, int power2, int to_db, float lo, float hi, hipStream_t st) {
-  if (L < NF / 2 + 1) return DMX_ERR_SHAPE;
+                     float* mel_out, float* partial, int B, int L, int hop, int power2, int to_db, float lo, float hi, hipStream_t st,
+                     const float* add, long long add_stride, const float* addmag, float nscale) {
+  if (L < NF / 2 + 1 || (addmag && power2) || (add && add_stride < L)) return DMX_ERR_SHAPE;
   SmParams P;
   memset(&P, 0, sizeof(P));
   fill_common(P, t, B, L, hop, power2, to_db, lo, hi);
   P.wav = wav; P.wav_stride = wav_stride; P.mask = mask; P.ref = ref; P.ref_stride = ref_stride; P.mel_out = mel_out;
   P.partial = ref ? partial : nullptr;
+  P.add = add; P.add_stride = add_stride; P.addmag = addmag; P.nscale = nscale;
   hipLaunchKernelGGL(stft_mel_fwd_kernel, dim3(dmx_stft_mel_parts(L, hop), B), dim3(256), 0, st, P);
   return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
 }
 
 int dmx_stft_mel_bwd(const DmxStftMelTables& t, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
                      const float* dmel, const float* partial, float gscale, float* loss, float* dwav, long long dwav_stride, int Lfull,
-                     int accumulate, int B, int L, int hop, int power2, int to_db, float lo, float hi, hipStream_t st) {
-  if (L < 2 * NF || (!dmel && (!ref || !partial)) || Lfull < L) return DMX_ERR_SHAPE;   // (left and right reflection zones must not meet)
+                     int accumulate, int B, int L, int hop, int power2, int to_db, float lo, float hi, hipStream_t st,
+                     const float* add, long long add_stride, const float* addmag, float nscale) {
+  if (L < 2 * NF || (!dmel && (!ref || !partial)) || Lfull < L || (addmag && power2) || (add && add_stride < L)) return DMX_ERR_SHAPE;   // (left and right reflection zones must not meet)
   SmParams P;
   memset(&P, 0, sizeof(P));
   fill_common(P, t, B, L, hop, power2, to_db, lo, hi);
   P.wav = wav; P.wav_stride = wav_stride; P.mask = mask; P.ref = ref; P.ref_stride = ref_stride; P.dmel = dmel;
   P.partial = const_cast<float*>(partial); P.nparts = dmx_stft_mel_parts(L, hop); P.gscale = gscale; P.loss = loss;
   P.dwav = dwav; P.dwav_stride = dwav_stride; P.Lfull = Lfull; P.accumulate = accumulate;
+  P.add = add; P.add_stride = add_stride; P.addmag = addmag; P.nscale = nscale;
   int chunk = (BWD_MAX_CHUNK / hop) * hop;                 // whole hops per workgroup
   if (chunk < hop) chunk = BWD_MAX_CHUNK;                  // (hop > 2560: any chunking is correct, frames are found from sample ranges)
   P.chunk = chunk;

@@ -169,6 +169,45 @@ std::tuple<at::Tensor, at::Tensor> mel_guidance(int64_t audio, const at::Tensor&
      "mel_guidance (backward)");
   return {loss, dwav};
 }
+// the same pair with the step's measurement noise (dmx_audio_guidance_{fwd,bwd}_ex): standard-normal `noise` (B, >= L) in the sample domain
+// and / or `noise_mag` (B, bins, frames) on the magnitudes, used as sigma * noise
+std::tuple<at::Tensor, at::Tensor> mel_guidance_noisy(int64_t audio, const at::Tensor& wav, const std::optional<at::Tensor>& mask, const at::Tensor& ref,
+                                                      at::Tensor state, int64_t L, int64_t Lfull, bool power2, bool to_db, double lo, double hi, double gscale,
+                                                      const std::optional<at::Tensor>& noise, const std::optional<at::Tensor>& noise_mag, double sigma) {
+  dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
+  TORCH_CHECK(wav.is_cuda() && wav.scalar_type() == at::kFloat && wav.dim() == 2 && wav.stride(1) == 1 && wav.size(1) >= L, "wav must be (B, >= L) fp32 on the GPU");
+  DMX_DEVICE_OF(wav);
+  f32_cuda(ref, "ref");
+  if (mask) { f32_cuda(*mask, "mask"); TORCH_CHECK(mask->numel() >= L && mask->device() == wav.device(), "mask must hold L samples"); }
+  const int B = (int)wav.size(0), T = dmx_audio_num_frames(a, (int)L);
+  if (noise) TORCH_CHECK(noise->is_cuda() && noise->device() == wav.device() && noise->scalar_type() == at::kFloat && noise->dim() == 2 && noise->stride(1) == 1 &&
+                         noise->size(0) == B && noise->size(1) >= L, "noise must be (B, >= L) fp32 on wav's device");
+  if (noise_mag) {
+    f32_cuda(*noise_mag, "noise_mag");
+    TORCH_CHECK(!power2 && noise_mag->device() == wav.device() && noise_mag->numel() == (int64_t)B * dmx_audio_num_bins(a) * T,
+                "noise_mag must be (B, bins, frames) and goes with power2 = False");
+  }
+  TORCH_CHECK(ref.device() == wav.device() && (ref.numel() == (int64_t)T * 64 || ref.numel() == (int64_t)B * T * 64), "ref must be (B or 1, frames, 64)");
+  TORCH_CHECK(state.is_cuda() && (size_t)state.nbytes() >= dmx_audio_state_bytes(a, B, (int)L), "state buffer too small");
+  TORCH_CHECK(Lfull >= L, "Lfull < L");
+  const long long rs = ref.numel() == (int64_t)T * 64 && B > 1 ? 0 : (long long)T * 64;
+  const long long ns = noise ? noise->stride(0) : 0;
+  at::Tensor loss = at::empty({B}, wav.options()), dwav = at::empty({B, Lfull}, wav.options());
+  ok(dmx_audio_guidance_fwd_ex(a, wav.data_ptr<float>(), wav.stride(0), fp(mask), ref.data_ptr<float>(), rs, nullptr, state.data_ptr(), B, (int)L,
+                               power2, to_db, (float)lo, (float)hi, fp(noise), ns, fp(noise_mag), (float)sigma, cur_stream()), "mel_guidance_noisy (forward)");
+  ok(dmx_audio_guidance_bwd_ex(a, wav.data_ptr<float>(), wav.stride(0), fp(mask), ref.data_ptr<float>(), rs, (float)gscale, loss.data_ptr<float>(),
+                               dwav.data_ptr<float>(), Lfull, (int)Lfull, state.data_ptr(), B, (int)L, power2, to_db, (float)lo, (float)hi, fp(noise), ns,
+                               fp(noise_mag), (float)sigma, cur_stream()), "mel_guidance_noisy (backward)");
+  return {loss, dwav};
+}
+at::Tensor noise_add(const at::Tensor& y, const at::Tensor& noise, double sigma) {
+  f32_cuda(y, "y"); f32_cuda(noise, "noise");
+  same_numel(y, noise, "noise_add(y, noise)");
+  DMX_DEVICE_OF(y);
+  at::Tensor out = at::empty_like(y);
+  ok(dmx_noise_add(y.data_ptr<float>(), noise.data_ptr<float>(), out.data_ptr<float>(), y.numel(), (float)sigma, cur_stream()), "noise_add");
+  return out;
+}
 at::Tensor stft_mag_fwd(int64_t audio, const at::Tensor& wav, const at::Tensor& state, int64_t L) {
   dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
   TORCH_CHECK(wav.is_cuda() && wav.scalar_type() == at::kFloat && wav.dim() == 2 && wav.stride(1) == 1, "wav must be (B, >= L) fp32 on the GPU");
@@ -334,6 +373,9 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("logmel_bwd(int audio, Tensor dmel, Tensor state, int L, bool power2, bool to_db, float lo, float hi) -> Tensor", &logmel_bwd);
   m.def("mel_guidance(int audio, Tensor wav, Tensor? mask, Tensor ref, Tensor(a!) state, int L, int Lfull, bool power2, bool to_db, float lo, float hi, "
         "float gscale) -> (Tensor, Tensor)", &mel_guidance);
+  m.def("mel_guidance_noisy(int audio, Tensor wav, Tensor? mask, Tensor ref, Tensor(a!) state, int L, int Lfull, bool power2, bool to_db, float lo, "
+        "float hi, float gscale, Tensor? noise, Tensor? noise_mag, float sigma) -> (Tensor, Tensor)", &mel_guidance_noisy);
+  m.def("noise_add(Tensor y, Tensor noise, float sigma) -> Tensor", &noise_add);
   m.def("stft_mag_fwd(int audio, Tensor wav, Tensor(a!) state, int L) -> Tensor", &stft_mag_fwd);
   m.def("stft_mag_bwd(int audio, Tensor dmag, Tensor state, int L, int Lfull) -> Tensor", &stft_mag_bwd);
   m.def("melscale_fwd(int audio, Tensor mag, float lo, float hi) -> Tensor", &melscale_fwd);

@@ -3,9 +3,9 @@ from .operator import (BaseOperator, IdentityOperator, MusicInpaintingOperator, 
                        SuperResolutionOperator, MusicDereverberationOperator, StyleGuidanceOperator)
 
 
-def get_noiser(name, sigma):                  # reference: inverse_problem/__init__.py:4-11
+def get_noiser(name, sigma, stream="global"):  # reference: inverse_problem/__init__.py:4-11; `stream`: GaussianNoise's per-step stream
     if name == "gaussian":
-        return GaussianNoise(sigma)
+        return GaussianNoise(sigma, stream=stream)
     if name == "poisson":
         return PoissonNoise(sigma)
     raise ValueError(f"Unknown noise: {name}")

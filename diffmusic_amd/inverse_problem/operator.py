@@ -8,7 +8,14 @@ Extension used by the guided schedulers (no torch.autograd on the hot path):
 `guidance(wav, L, measurement, supervised_space)` returns the per-clip loss ||y - A(wav)|| (in the
 chosen space) and its gradient with respect to the vocoder output, computed by hand-written
 backward kernels (the reference gets the same quantity from torch.autograd.grad,
-scheduling_dps.py:202-212)."""
+scheduling_dps.py:202-212).
+
+Measurement noise inside the step: the reference's `forward` ends in `self.noiser(...)` and its schedulers call it on the
+predicted audio in every step, so with sigma > 0 the loss is taken on A(wav) + sigma * z.  `guidance(..., noise=None, step=None,
+generator=None)` does the same when the operator's noiser has `additive_sigma > 0`: z is `noise` when given (a standard-normal
+tensor shaped like A(wav), for teacher forcing) and otherwise a device-side draw of the noiser (`GaussianNoise.draw`, keyed by
+`step` / `generator` on the clip stream).  The noise is additive and independent of wav: the gradient has no extra term.  With
+sigma == 0, no noiser, or a noiser without an additive part (Poisson) nothing is drawn or launched."""
 import ctypes as C
 import math
 import numpy as np
@@ -17,6 +24,7 @@ import torch
 from .. import _lib as L
 from .. import ops
 from . import dsp
+from .noise import step_sigma
 
 _NEG, _POS = -3.0e38, 3.0e38
 
@@ -77,14 +85,19 @@ class SpectralFrontend:
         """True when the fused STFT -> mel kernels (csrc/stft_mel.hip: n_fft = 1024) cover this handle and clip length."""
         return bool(L.lib().dmx_audio_is_fused(self._h, int(length)))
 
-    def guidance(self, wav, length, ref, mask=None, power2=True, to_db=True, lo=_NEG, hi=_POS, gscale=1.0):
+    def guidance(self, wav, length, ref, mask=None, power2=True, to_db=True, lo=_NEG, hi=_POS, gscale=1.0, noise=None, noise_mag=None,
+                 sigma=0.0):
         """Fused guidance pair: loss[b] = ||ref[b] - transform(wav[b, :length] * mask)||_2 and dwav = gscale * dloss/dwav, (B, wav.shape[1])
-        with zeros past `length` -- one forward and one backward launch, no spectrum in HBM (dmx_audio_guidance_{fwd,bwd})."""
+        with zeros past `length` -- one forward and one backward launch, no spectrum in HBM (dmx_audio_guidance_{fwd,bwd}).
+        noise (B, >= length) / noise_mag (B, bins, frames; power2 False): standard-normal draws entering as wav * mask + sigma * noise,
+        resp. |STFT| + sigma * noise_mag, inside both kernels (dmx_audio_guidance_{fwd,bwd}_ex)."""
         assert wav.dtype == torch.float32 and wav.is_cuda and wav.stride(1) == 1 and ref.dtype == torch.float32 and ref.is_contiguous()
         B, full = wav.shape
         st = self._get_state(B, length, wav.device)
-        return ops.hip.mel_guidance(self._h.value, wav, mask, ref, st, int(length), int(full), bool(power2), bool(to_db), float(lo),
-                                    float(hi), float(gscale))
+        args = (self._h.value, wav, mask, ref, st, int(length), int(full), bool(power2), bool(to_db), float(lo), float(hi), float(gscale))
+        if noise is None and noise_mag is None:
+            return ops.hip.mel_guidance(*args)
+        return ops.hip.mel_guidance_noisy(*args, noise, noise_mag, float(sigma))
 
     def stft_mag(self, wav, length):
         B = wav.shape[0]
@@ -136,8 +149,12 @@ class BaseOperator:
     cache_reference = True     # False: recompute transform(measurement) every step, as the reference does (operator.py:205-206 call site)
 
     def reset_cache(self):
-        """Forget the cached `transform(measurement)`; called at the start of every trajectory (set_timesteps / __call__)."""
+        """Forget the cached `transform(measurement)` and restart the noiser's step stream; called at the start of every trajectory
+        (set_timesteps / __call__)."""
         self._ref_cache = None
+        reset = getattr(getattr(self, "noiser", None), "reset", None)
+        if reset is not None:
+            reset()
 
     def _ref(self, measurement, space, fn):
         """`transform(y)` is constant over a trajectory: computed once per measurement TENSOR and supervised space.  A cache
@@ -156,8 +173,21 @@ class BaseOperator:
         del cache[4:]
         return cache[0][3]
 
-    def guidance(self, wav, length, measurement, supervised_space):
+    def guidance(self, wav, length, measurement, supervised_space, noise=None, step=None, generator=None):
         raise NotImplementedError
+
+    def _step_noise(self, shape, device, noise, step, generator):
+        """-> (z, sigma): the standard-normal tensor of shape `shape` = A(wav).shape that this step adds as sigma * z, or (None, 0.0).
+        Decided by the noiser's explicit `additive_sigma` (noise.py); `noise` given = teacher forcing, else the noiser draws."""
+        noiser = getattr(self, "noiser", None)
+        sigma = step_sigma(noiser)
+        if sigma <= 0.0:
+            return None, 0.0
+        if noise is None:
+            return noiser.draw(tuple(shape), device, step=step, generator=generator), sigma
+        if tuple(noise.shape) != tuple(shape):
+            raise ValueError(f"noise must be shaped like A(x) = {tuple(shape)}, got {tuple(noise.shape)}")
+        return _as_f32_cuda(noise).contiguous(), sigma
 
 
 class _MelOperator(BaseOperator):
@@ -187,13 +217,18 @@ class _MelOperator(BaseOperator):
 
     fused_mask = False        # True: A(.) is a per-sample mask (or the identity) that the fused mel kernels apply on load / on store
 
-    def guidance(self, wav, length, measurement, supervised_space):
+    def guidance(self, wav, length, measurement, supervised_space, noise=None, step=None, generator=None):
         if supervised_space == "mel_spectrogram" and self.fused_mask and self.frontend.fused(length):
-            # mask, STFT, mel, dB, L2 and the whole backward in two launches; y = A(wav) is never materialised
+            # mask, noise, STFT, mel, dB, L2 and the whole backward in two launches; y = A(wav) is never materialised
             lo, hi = self.clamp if self.clamp else (_NEG, _POS)
             ref = self._ref(measurement, "mel_spectrogram", lambda m: self._mel(m.reshape(m.shape[0], -1)).clone())
-            return self.frontend.guidance(wav, length, ref, self._fused_mask_tensor(wav.device, length), True, True, lo, hi)
+            z, sigma = self._step_noise((wav.shape[0], length), wav.device, noise, step, generator)
+            return self.frontend.guidance(wav, length, ref, self._fused_mask_tensor(wav.device, length), True, True, lo, hi, noise=z,
+                                          sigma=sigma)
         y = self._a_fwd(wav, length)                                         # (B, L') contiguous fp32
+        z, sigma = self._step_noise(y.shape, y.device, noise, step, generator)
+        if z is not None:
+            y = ops.hip.noise_add(y, z, sigma)                               # the noiser on the materialised A(wav); A^T is unchanged
         if supervised_space == "mel_spectrogram" and self.frontend.fused(y.shape[1]):
             lo, hi = self.clamp if self.clamp else (_NEG, _POS)
             ref = self._ref(measurement, "mel_spectrogram", lambda m: self._mel(m.reshape(m.shape[0], -1)).clone())
@@ -301,10 +336,14 @@ class PhaseRetrievalOperator(BaseOperator):               # operator.py:136-171
         mag = self.frontend.stft_mag(data, data.shape[-1])
         return self.noiser(mag) if self.noiser is not None else mag
 
-    def guidance(self, wav, length, measurement, supervised_space):
+    def guidance(self, wav, length, measurement, supervised_space, noise=None, step=None, generator=None):
+        bins_frames = (wav.shape[0], self.frontend.bins, self.frontend.frames(length))
         if supervised_space == "wav_form":          # scheduling_dps.py:199-201: || y - |STFT(wav)| ||_2 on the raw magnitudes
             mag = self.frontend.stft_mag(wav, length)
             B = mag.shape[0]
+            z, sigma = self._step_noise(bins_frames, wav.device, noise, step, generator)
+            if z is not None:                       # the backward divides by the clean |X| kept in the front end's state
+                mag = ops.hip.noise_add(mag, z, sigma)
             m32 = self._ref(measurement, "wav_form", lambda m: m.reshape(m.shape[0], -1).contiguous())
             loss, dmag = l2_loss(m32, mag.reshape(B, -1))
             dwav = torch.zeros(wav.shape[0], wav.shape[1], dtype=torch.float32, device=wav.device)
@@ -313,8 +352,12 @@ class PhaseRetrievalOperator(BaseOperator):               # operator.py:136-171
         if supervised_space != "mel_spectrogram":
             raise ValueError("supervised_space should be either 'wav_form' or 'mel_spectrogram")
         ref = self._ref(measurement, "mel_spectrogram", lambda m: self.frontend.melscale(m, -80.0, 80.0))
+        z, sigma = self._step_noise(bins_frames, wav.device, noise, step, generator)
         if self.frontend.fused(length):
-            return self.frontend.guidance(wav, length, ref, None, False, False, -80.0, 80.0)
+            return self.frontend.guidance(wav, length, ref, None, False, False, -80.0, 80.0, noise_mag=z, sigma=sigma)
+        if z is not None:
+            raise NotImplementedError("phase retrieval with measurement noise in mel space needs the fused kernels (n_fft = 1024, clips of "
+                                      ">= 2048 samples): the dense-DFT path has no entry for the magnitude-domain noise")
         pred = self.frontend.transform_fwd(wav, length, False, False, -80.0, 80.0)   # |STFT| -> MelScale -> clamp
         loss, dmel = l2_loss(ref, pred)
         dwav = torch.zeros(wav.shape[0], wav.shape[1], dtype=torch.float32, device=wav.device)
@@ -399,9 +442,9 @@ class MusicDereverberationOperator(_MelOperator):         # operator.py:208-250
         y = _fir_fwd(data, data.shape[1], h, data.shape[1] + 2 * (n // 2) - n + 1, 1, 1, n // 2)
         return self.noiser(y) if self.noiser is not None else y
 
-    def guidance(self, wav, length, measurement, supervised_space, ir=None):
+    def guidance(self, wav, length, measurement, supervised_space, ir=None, noise=None, step=None, generator=None):
         self._h, self._hrev = self._get_ir(wav.device, ir)
-        return super().guidance(wav, length, measurement, supervised_space)
+        return super().guidance(wav, length, measurement, supervised_space, noise=noise, step=step, generator=generator)
 
     def _a_fwd(self, wav, length):
         n = self._h.shape[1]
@@ -492,11 +535,14 @@ class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 
         feats, _ = self._features(audio.contiguous(), audio.shape[-1])
         return self._gram(feats)
 
-    def guidance(self, wav, length, measurement, supervised_space):
-        y = wav                                                                    # forward = identity on the vocoder output
+    def guidance(self, wav, length, measurement, supervised_space, noise=None, step=None, generator=None):
+        y = wav                                                                    # forward = noiser(identity) on the vocoder output
+        z, sigma = self._step_noise((wav.shape[0], length), wav.device, noise, step, generator)
+        if z is not None:
+            y = ops.hip.noise_add(ops.ctypes_hip.mask_mul(wav, None, length, length), z, sigma)
         if supervised_space == "wav_form":
             m32 = self._ref(measurement, "wav_form", lambda m: m.reshape(m.shape[0], -1).contiguous())
-            loss, dy = l2_loss(m32, ops.ctypes_hip.mask_mul(wav, None, length, length))
+            loss, dy = l2_loss(m32, y if z is not None else ops.ctypes_hip.mask_mul(wav, None, length, length))
             d = torch.zeros(wav.shape[0], wav.shape[1], dtype=torch.float32, device=wav.device)
             d[:, :length] = dy
             return loss, d

@@ -19,6 +19,7 @@ from .. import ops
 from ..engine import HifiGanEngine, UNetEngine, VaeDecoderEngine
 from ..torch_utils import randn_tensor
 from ..profiling import stage
+from ..inverse_problem.noise import step_sigma
 from .. import parallel
 
 
@@ -197,7 +198,14 @@ class MusicLDMPipeline:
             measurement = measurement.to(device=device, dtype=torch.float32)      # once per call (transform(y) is cached per tensor)
         # ---- clip sharding (no per-step collective; clips are independent because norms and RNG are per clip)
         sel = None
+        noiser = getattr(self.scheduler.operator, "noiser", None)
+        # measurement noise inside the step (inverse_problem/noise.py) on the process-wide stream: drawn per call, in call order
+        global_step_noise = step_sigma(noiser) > 0 and getattr(noiser, "stream", "global") == "global"
         if shard or group is not None:
+            if global_step_noise:
+                raise ValueError("clip sharding with measurement noise (sigma > 0) needs the per-clip noise stream "
+                                 "(GaussianNoise(sigma, stream='clip') / `noise.stream: clip`): draws from the global stream would depend "
+                                 "on the number of ranks")
             import torch.distributed as dist
             if not (dist.is_available() and dist.is_initialized()):
                 raise RuntimeError("shard=True needs an initialised torch.distributed process group")
@@ -224,6 +232,13 @@ class MusicLDMPipeline:
         if B > 0 and n_lanes > 1 and B > 1:
             if callback is not None:
                 raise ValueError("lanes > 1 cannot serve `callback(i, t, latents)`: the clip groups are at different steps at any one time")
+            if global_step_noise:
+                raise ValueError("lanes > 1 with measurement noise (sigma > 0) needs the per-clip noise stream "
+                                 "(GaussianNoise(sigma, stream='clip') / `noise.stream: clip`): draws from the global stream would depend "
+                                 "on the number of lanes")
+            if step_sigma(noiser) > 0 and isinstance(generator, torch.Generator):
+                raise ValueError("lanes > 1 with per-clip measurement noise needs one generator per clip (a list of length B): one shared "
+                                 "generator keys clip k by its position in the lane, not in the batch")
             if isinstance(generator, torch.Generator) and eta > 0 or (isinstance(generator, torch.Generator) and
                                                                       self.scheduler.mode in ("dsg", "diffmusic")):
                 raise ValueError("lanes > 1 with per-step noise needs one generator per clip (a list of length B): one shared "

@@ -14,6 +14,7 @@ import torch
 from .. import ops
 from ..torch_utils import randn_tensor, randn_philox
 from ..profiling import stage
+from ..inverse_problem.noise import step_sigma
 from .utils import InverseProblemSchedulerOutput
 
 _MODE = dict(ddim=0, dps=1, mpgd=2, dsg=3, diffmusic=4)
@@ -130,6 +131,15 @@ class GuidedDDIMScheduler:
         return t, a_t, a_p, sigma
 
     # ---- HIP guidance sweep: x0 -> vae -> vocoder -> A -> loss ; and back
+    def _op_kwargs(self, op_kwargs, timestep, generator):
+        """Keywords of `operator.guidance` for this step.  An operator whose noiser adds Gaussian noise inside the step (noise.py
+        `additive_sigma > 0`) also gets the step index -- the position of `timestep` in this trajectory's list, never a call counter -- and
+        the generator(s), which key the per-clip measurement-noise stream; `noise=` in op_kwargs (teacher forcing) replaces the draw."""
+        if step_sigma(getattr(self.operator, "noiser", None)) <= 0 or "noise" in (op_kwargs or {}):
+            return op_kwargs
+        ts = getattr(self, "_timesteps_host", None) or []
+        return dict(op_kwargs or {}, step=ts.index(timestep) if timestep in ts else None, generator=generator)
+
     def _guidance(self, x0, measurement, vae, vocoder, length, supervised_space, op_kwargs=None):
         zs = 1.0 / vae.config.scaling_factor
         with stage("vae_fwd"):
@@ -190,7 +200,7 @@ class GuidedDDIMScheduler:
             loss = torch.tensor([t])
         else:
             loss, g0, inv_scale = self._guidance(x0, measurement, vae, vocoder, original_waveform_length, supervised_space,
-                                                 kwargs.get("op_kwargs"))
+                                                 self._op_kwargs(kwargs.get("op_kwargs"), t, generator))
             if self.mode in ("dsg", "diffmusic"):
                 sn = kwargs.get("sample_noise")
                 if sn is None and self.device_noise:

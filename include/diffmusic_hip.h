@@ -27,6 +27,8 @@
 extern "C" {
 #endif
 
+/* Additive changes do not bump the version: dmx_audio_guidance_{fwd,bwd}_ex and dmx_noise_add (measurement noise inside the guided
+ * step) are new symbols, and every earlier entry point keeps its signature. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
 
@@ -187,6 +189,21 @@ int dmx_audio_guidance_fwd(dmx_audio* a, const float* wav, long long wav_stride,
 int dmx_audio_guidance_bwd(dmx_audio* a, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
                            float gscale, float* loss, float* dwav, long long dwav_stride, int Lfull, void* state, int batch, int L,
                            int power2, int to_db, float lo, float hi, void* stream);
+/* The same pair with the measurement noise of the step (the `self.noiser(...)` that ends every operator's forward, operator.py:132-133,
+ * :170-171 ...; noise.py:13-18), as standard-normal draws z scaled by noise_scale = sigma inside the kernels:
+ *   add    (batch, >= L) fp32, row stride add_stride, sample domain:     y = wav * mask + noise_scale * add
+ *   addmag (batch, n_fft/2+1, frames) fp32, power2 = 0 only:             |STFT(y)| + noise_scale * addmag
+ * Either may be NULL (both NULL = dmx_audio_guidance_{fwd,bwd}, which are these calls with NULLs).  The noise does not depend on wav, so
+ * it has no backward term; _bwd_ex must be given the pointers _fwd_ex saw, because it recomputes the forward. */
+int dmx_audio_guidance_fwd_ex(dmx_audio* a, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
+                              float* mel_out, void* state, int batch, int L, int power2, int to_db, float lo, float hi, const float* add,
+                              long long add_stride, const float* addmag, float noise_scale, void* stream);
+int dmx_audio_guidance_bwd_ex(dmx_audio* a, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
+                              float gscale, float* loss, float* dwav, long long dwav_stride, int Lfull, void* state, int batch, int L,
+                              int power2, int to_db, float lo, float hi, const float* add, long long add_stride, const float* addmag,
+                              float noise_scale, void* stream);
+/* out[i] = y[i] + scale * z[i], i < n (the noiser on a materialised measurement A(x): super-resolution, dereverberation, wav_form) */
+int dmx_noise_add(const float* y, const float* z, float* out, long long n, float scale, void* stream);
 /* PhaseRetrievalOperator.forward: |torch.stft(wav)| as (B, n_fft/2+1, frames) fp32 */
 int dmx_audio_stft_mag(dmx_audio* a, const float* wav, long long wav_stride, float* mag, void* state, int batch, int L, void* stream);
 /* gradient of a loss on that magnitude (PhaseRetrievalOperator.forward, operator.py:156-163, differentiated by
