@@ -230,6 +230,29 @@ def vae_dec_bwd(model, dmel, z_scale, latent_channels, scale_factor):
     return dz
 
 
+def vae_enc_fwd(model, mel, log_floor, latent_channels, scale_factor, ws):
+    """mel (B, frames, bins) fp32 -> moments (B, (frames / s) * (bins / s), 2 * latent_channels) fp32, [mean | logvar] per position."""
+    B, T, F = mel.shape
+    s = scale_factor
+    mom = torch.empty(B, (T // s) * (F // s), 2 * latent_channels, dtype=torch.float32, device=mel.device)
+    _lib.check(_lib.lib().dmx_vae_encode_fwd(model, _p(mel), log_floor, _p(mom), B, T, F, _p(ws), ws.numel(), _stream()), "vae_encode_fwd")
+    return mom
+
+
+def latent_init(moments, h, w, eps, noise, sqrt_abar, scaling_factor, sqrt_1m_abar, want_x):
+    """-> (mean, logvar clamped to [-30, 20], x or None), each (B, L, h, w) fp32; x = sqrt_abar * scaling_factor * (mean + std * eps) +
+    sqrt_1m_abar * noise (eps None: the mode, noise None: no noise term) when want_x."""
+    B, P, L2 = moments.shape
+    assert P == h * w and L2 % 2 == 0, (moments.shape, h, w)
+    L = L2 // 2
+    mean = torch.empty(B, L, h, w, dtype=torch.float32, device=moments.device)
+    logvar = torch.empty_like(mean)
+    x = torch.empty_like(mean) if want_x else None
+    _lib.check(_lib.lib().dmx_latent_init(_p(moments), _p(mean), _p(logvar), _p(x), _p(eps), _p(noise), B, L, P, sqrt_abar,
+                                          scaling_factor, sqrt_1m_abar, _stream()), "latent_init")
+    return mean, logvar, x
+
+
 def grad_normalize_(dwav, target):
     """In place on dwav (B, samples): max |g| -> target per clip; returns the factors that undo it."""
     inv_scale = torch.empty(dwav.shape[0], dtype=torch.float32, device=dwav.device)

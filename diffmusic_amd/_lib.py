@@ -87,6 +87,12 @@ _SIGS = {
     "dmx_vae_decode_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dmx_vae_decode_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "dmx_vae_encoder_create": (C.c_void_p, [C.POINTER(VaeConfig)]),
+    "dmx_vae_encoder_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "dmx_vae_encode_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
+    "dmx_latent_init": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_float] * 3 + [C.c_void_p]),
+    "dmx_conv2d_raw": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_void_p]),
     "dmx_unet_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "dmx_unet_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -153,7 +159,19 @@ _SIGS = {
     "dmx_sched_step": (C.c_int, [C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_int] + [C.c_float] * 5 + [C.c_int, C.c_void_p]),
 }
 
+# entry points added to ABI version 4 without a version bump (include/diffmusic_hip.h): a library of that version built before them
+# loads, so their presence is checked by name
+ADDED_IN_V4 = ("dmx_vae_encoder_create", "dmx_vae_encoder_workspace_bytes", "dmx_vae_encode_fwd", "dmx_latent_init")
+
 _lib = None
+
+
+def check_symbols(h, path=LIB_PATH):
+    """Raises when the loaded library `h` lacks an entry point this package binds by name."""
+    for name in ADDED_IN_V4:
+        if not hasattr(h, name):
+            raise RuntimeError(f"{path} reports ABI version {ABI_VERSION} but does not export `{name}` (a build from before the VAE "
+                               "encoder entry points): rebuild it (python -m diffmusic_amd.build --force)")
 
 
 def lib():
@@ -172,6 +190,7 @@ def lib():
         if h.dmx_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libdiffmusic_hip.so ABI version {h.dmx_abi_version()} != {ABI_VERSION} expected by this package: rebuild it "
                                "(python -m diffmusic_amd.build --force)")
+        check_symbols(h)
         _lib = h
     return _lib
 

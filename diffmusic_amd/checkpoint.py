@@ -179,7 +179,7 @@ def unet_config(cfg, what="unet/config.json"):
 
 
 def vae_config(cfg, what="vae/config.json"):
-    """diffusers AutoencoderKL config dict -> VaeDecoderEngine config (decoder side; the hot path never encodes)."""
+    """diffusers AutoencoderKL config dict -> the config of VaeDecoderEngine and VaeEncoderEngine (one dict serves both halves)."""
     ck = _Checker(cfg, what)
     cls = cfg.get("_class_name", "AutoencoderKL")
     if cls != "AutoencoderKL":
@@ -195,9 +195,14 @@ def vae_config(cfg, what="vae/config.json"):
     up = ck.get("up_block_types", ["UpDecoderBlock2D"] * n)
     if not isinstance(up, (list, tuple)) or len(up) != n or any(t != "UpDecoderBlock2D" for t in up):
         ck.fail(f"`up_block_types` = {up!r}: {n} x UpDecoderBlock2D")
-    ck.get("down_block_types", None)                  # encoder side: not built (allow_unexpected tensors of the checkpoint)
-    ck.get("in_channels", None)
-    out = dict(latent_channels=ck.get("latent_channels", 4), out_channels=ck.get("out_channels", 3), block_out_channels=list(boc),
+    down = ck.get("down_block_types", ["DownEncoderBlock2D"] * n)      # encoder side (VaeEncoderEngine: warm-started sampling)
+    if not isinstance(down, (list, tuple)) or len(down) != n or any(t != "DownEncoderBlock2D" for t in down):
+        ck.fail(f"`down_block_types` = {down!r}: {n} x DownEncoderBlock2D")
+    cin, cout = ck.get("in_channels", 3), ck.get("out_channels", 3)
+    if cin != cout:
+        # one config struct serves both halves (dmx_vae_config has no in_channels): the encoder takes what the decoder produces
+        ck.fail(f"`in_channels` = {cin!r} differs from `out_channels` = {cout!r}: an autoencoder whose input and output channels are equal")
+    out = dict(latent_channels=ck.get("latent_channels", 4), out_channels=cout, block_out_channels=list(boc),
                layers_per_block=ck.get("layers_per_block", 1), norm_num_groups=g, scaling_factor=float(ck.get("scaling_factor", 0.18215)),
                eps=1e-6)
     ck.require("act_fn", ("silu",), "silu")

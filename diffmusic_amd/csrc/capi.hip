@@ -83,6 +83,31 @@ int dmx_vae_decode_bwd(dmx_model* m, const uint16_t* dmel, float z_scale, float*
   return dmx_vae_bwd_impl(m->impl, dmel, z_scale, dz, ST(stream));
 }
 
+dmx_model* dmx_vae_encoder_create(const dmx_vae_config* cfg) {
+  if (!cfg || cfg->num_blocks > DMX_MAX_STAGES) { dmx_set_error("bad vae config"); return nullptr; }
+  Model* m = dmx_make_vae_encoder(cfg);
+  return m ? new dmx_model{m} : nullptr;
+}
+size_t dmx_vae_encoder_workspace_bytes(dmx_model* m, int batch, int frames, int bins) {
+  if (!m || !m->impl || m->impl->kind != DMX_MODEL_VAE_ENC) return 0;
+  return dmx_vae_enc_ws_impl(m->impl, batch, frames, bins);
+}
+int dmx_vae_encode_fwd(dmx_model* m, const float* mel, float log_floor, float* moments, int batch, int frames, int bins, void* ws,
+                       size_t ws_bytes, void* stream) {
+  int rc = check(m, DMX_MODEL_VAE_ENC);
+  if (rc) return rc;
+  if (!ws) { dmx_set_error("null workspace"); return DMX_ERR_WORKSPACE; }
+  return dmx_vae_enc_fwd_impl(m->impl, mel, log_floor, moments, batch, frames, bins, ws, ws_bytes, ST(stream));
+}
+int dmx_latent_init(const float* moments, float* mean, float* logvar, float* x, const float* eps, const float* noise, int batch,
+                    int latent_channels, int hw, float sqrt_abar, float scaling_factor, float sqrt_1m_abar, void* stream) {
+  return dmx_latent_init_impl(moments, mean, logvar, x, eps, noise, batch, latent_channels, hw, sqrt_abar, scaling_factor, sqrt_1m_abar, ST(stream));
+}
+int dmx_conv2d_raw(const float* w_host, const float* b_host, const void* x, void* y, int B, int Hi, int Wi, int Ci, int Co, int k, int stride,
+                   int pad_lo, int pad_hi, void* stream) {
+  return dmx_conv2d_raw_impl(w_host, b_host, (const act_t*)x, (act_t*)y, B, Hi, Wi, Ci, Co, k, stride, pad_lo, pad_hi, ST(stream));
+}
+
 dmx_model* dmx_htsat_create(const dmx_htsat_config* cfg) {
   Model* impl = dmx_make_htsat(cfg);
   if (!impl) return nullptr;

@@ -1221,7 +1221,10 @@ int dmx_groupnorm_fwd(const act_t* x, act_t* y, const float* gamma, const float*
   static const bool small_ok = getenv("DMX_NO_GN_SMALL") == nullptr, fused_ok = getenv("DMX_NO_GN_FUSED") == nullptr;
   // one workgroup per (group, image) holds its slice in registers: one launch, but its 8-byte pieces of 2C-byte rows are the
   // worst case for the memory pipeline -- it wins only where the tensor is tiny (<= 512 pixels: launch latency rules)
-  const bool small_fits = (cpg & 3) == 0 && cpg <= 256 && (long long)P * (cpg >> 2) <= 256ll * GN_SMALL_MAXU && (long long)B * G >= 128;
+  // The plan is chosen by the image's shape alone, not by the batch: the plans round differently, and a `B * G >= 128` term here made a
+  // 1-clip lane (CFG batch 2) differ from the same clip in a 3-clip batch.  (GroupNorm no longer depends on the batch; the GEMM tile /
+  // split-K choice of the U-Net still does at other sizes)
+  const bool small_fits = (cpg & 3) == 0 && cpg <= 256 && (long long)P * (cpg >> 2) <= 256ll * GN_SMALL_MAXU;
   const bool mid = y && fused_ok && P >= 512 && P <= 8192 && (C >> 3) <= 256;
   if (small_ok && small_fits && !mid) {
     hipLaunchKernelGGL(gn_small_kernel, dim3(G, B), dim3(256), 0, st, x, y, gamma, beta, stats, scale, shift, P, C, G, eps, silu);

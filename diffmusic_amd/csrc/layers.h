@@ -56,6 +56,7 @@ struct ParamStore {
 struct ConvLayer {
   int Ci = 0, Co = 0, Cip = 0, Cop = 0;
   int kh = 1, kw = 1, stride = 1, dil = 1, pad_h = 0, pad_w = 0;
+  int pad_h_hi = 0, pad_w_hi = 0;     // 2-D: zero rows / columns AFTER the image (pad_h / pad_w: before it); equal to them unless make_conv2d_asym
   bool transposed = false;  // ConvTranspose1d (weight layout Cin,Cout,k)
   bool has_bias = true, need_bwd = false;
   bool geglu = false;       // linear layer whose output is [values | gates]: rows packed in blocks of 32 = [16 values | their 16 gates]
@@ -104,6 +105,8 @@ struct Epi {
 ConvLayer make_conv1d(ParamStore& ps, const std::string& prefix, int Ci, int Co, int k, int dil, int pad, bool need_bwd);
 ConvLayer make_convT1d(ParamStore& ps, const std::string& prefix, int Ci, int Co, int k, int stride, int pad, bool need_bwd);
 ConvLayer make_conv2d(ParamStore& ps, const std::string& prefix, int Ci, int Co, int k, int stride, int pad, bool need_bwd);
+// pad_lo zero rows / columns before the image, pad_hi after it (diffusers Downsample2D with padding = 0: F.pad(x, (0, 1, 0, 1)), stride 2); forward only
+ConvLayer make_conv2d_asym(ParamStore& ps, const std::string& prefix, int Ci, int Co, int k, int stride, int pad_lo, int pad_hi);
 ConvLayer make_linear(ParamStore& ps, const std::string& prefix, int Ci, int Co, bool bias, bool need_bwd);
 int pack_layer(ParamStore& ps, ConvLayer& L, hipStream_t st);
 // n linear layers of equal input width (registered, loaded) packed as ONE layer whose output is their outputs side by side

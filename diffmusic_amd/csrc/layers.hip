@@ -142,7 +142,7 @@ static void up2x_rows(int p, int t, int (&k)[2]) {
 static int up2x_delta(int p, int t) { return p == 0 ? t - 1 : t; }      // low-resolution offset of tap t at parity p
 
 int pack_layer_up2x(ParamStore& ps, ConvLayer& L, hipStream_t st) {
-  if (L.transposed || L.kh != 3 || L.kw != 3 || L.stride != 1 || L.pad_h != 1 || L.pad_w != 1) return DMX_ERR_SHAPE;
+  if (L.transposed || L.kh != 3 || L.kw != 3 || L.stride != 1 || L.pad_h != 1 || L.pad_w != 1 || L.pad_h_hi != 1 || L.pad_w_hi != 1) return DMX_ERR_SHAPE;
   const float* w = ps.dev(L.w_id);               // W[Co][Ci][3][3]
   const int T9 = 9;
   L.wup.clear();
@@ -206,7 +206,12 @@ ConvLayer make_convT1d(ParamStore& ps, const std::string& prefix, int Ci, int Co
 ConvLayer make_conv2d(ParamStore& ps, const std::string& prefix, int Ci, int Co, int k, int stride, int pad, bool need_bwd) {
   ConvLayer L = base_layer(ps, prefix, {Co, Ci, k, k}, Co, true);
   L.Ci = Ci; L.Co = Co; L.Cip = pad8(Ci); L.Cop = pad8(Co);
-  L.kh = k; L.kw = k; L.stride = stride; L.pad_h = pad; L.pad_w = pad; L.need_bwd = need_bwd;
+  L.kh = k; L.kw = k; L.stride = stride; L.pad_h = pad; L.pad_w = pad; L.pad_h_hi = pad; L.pad_w_hi = pad; L.need_bwd = need_bwd;
+  return L;
+}
+ConvLayer make_conv2d_asym(ParamStore& ps, const std::string& prefix, int Ci, int Co, int k, int stride, int pad_lo, int pad_hi) {
+  ConvLayer L = make_conv2d(ps, prefix, Ci, Co, k, stride, pad_lo, false);
+  L.pad_h_hi = pad_hi; L.pad_w_hi = pad_hi;
   return L;
 }
 ConvLayer make_linear(ParamStore& ps, const std::string& prefix, int Ci, int Co, bool bias, bool need_bwd) {
@@ -412,7 +417,9 @@ int conv_pair_run(const GemmDesc& a, const GemmDesc& b, hipStream_t st) {
 }
 
 int conv_fwd_2d(const ConvLayer& L, const act_t* in, void* out, int B, int Hi, int Wi, const Epi& e, hipStream_t st) {
-  const int Ho = (Hi + 2 * L.pad_h - L.kh) / L.stride + 1, Wo = (Wi + 2 * L.pad_w - L.kw) / L.stride + 1;
+  // the taps start pad_h / pad_w before the output's origin; the pads after the image only decide how many outputs there are (the gather
+  // zero-fills whatever falls outside [0, Hi) x [0, Wi) on either side)
+  const int Ho = (Hi + L.pad_h + L.pad_h_hi - L.kh) / L.stride + 1, Wo = (Wi + L.pad_w + L.pad_w_hi - L.kw) / L.stride + 1;
   GemmDesc d;
   init_desc(d, e);
   if (L.has_bias) { d.bias = L.bias; d.flags |= EPI_BIAS; }
@@ -475,6 +482,7 @@ int conv_up2x_bwd(const ConvLayer& L, const act_t* dout, void* din, int B, int H
 int conv_bwd_2d(const ConvLayer& L, const act_t* dout, void* din, int B, int Hi, int Wi, const Epi& e, hipStream_t st) {
   if (!L.wb) { dmx_set_error("layer has no dgrad weights"); return DMX_ERR_STATE; }
   if (L.stride != 1) return DMX_ERR_SHAPE;
+  if (L.pad_h_hi != L.pad_h || L.pad_w_hi != L.pad_w) { dmx_set_error("conv dgrad of an asymmetrically padded layer is not built"); return DMX_ERR_SHAPE; }
   const int Ho = Hi + 2 * L.pad_h - L.kh + 1, Wo = Wi + 2 * L.pad_w - L.kw + 1;
   GemmDesc d;
   init_desc(d, e);

@@ -3,7 +3,7 @@
 #include "layers.h"
 #include "../../include/diffmusic_hip.h"
 
-enum { DMX_MODEL_HIFIGAN = 1, DMX_MODEL_VAE = 2, DMX_MODEL_UNET = 3, DMX_MODEL_HTSAT = 4 };
+enum { DMX_MODEL_HIFIGAN = 1, DMX_MODEL_VAE = 2, DMX_MODEL_UNET = 3, DMX_MODEL_HTSAT = 4, DMX_MODEL_VAE_ENC = 5 };
 
 struct Model {
   int kind = 0;
@@ -31,6 +31,14 @@ size_t dmx_vae_ws_impl(Model* m, int B, int h, int w);
 int dmx_vae_fwd_impl(Model* m, const float* z, float zs, act_t* mel, float* mel32, int B, int h, int w, int keep, void* ws, size_t wsb,
                      hipStream_t st);
 int dmx_vae_bwd_impl(Model* m, const act_t* dmel, float zs, float* dz, hipStream_t st);
+// AutoencoderKL encoder (vae_enc.hip): forward only; and the output stage moments -> mean / logvar / noised start latent
+Model* dmx_make_vae_encoder(const dmx_vae_config* c);
+size_t dmx_vae_enc_ws_impl(Model* m, int B, int T, int F);
+int dmx_vae_enc_fwd_impl(Model* m, const float* mel, float log_floor, float* moments, int B, int T, int F, void* ws, size_t wsb, hipStream_t st);
+int dmx_latent_init_impl(const float* moments, float* mean, float* logvar, float* x, const float* eps, const float* noise, int B, int L, int P,
+                         float sqrt_abar, float scaling_factor, float sqrt_1m_abar, hipStream_t st);
+int dmx_conv2d_raw_impl(const float* w_host, const float* b_host, const act_t* x, act_t* y, int B, int Hi, int Wi, int Ci, int Co, int k,
+                        int stride, int pad_lo, int pad_hi, hipStream_t st);
 Model* dmx_make_unet(const dmx_unet_config* c);
 size_t dmx_unet_ws_impl(Model* m, int B, int h, int w, int n0, int n1);
 int dmx_unet_fwd_impl(Model* m, const float* x, const float* t, const float* cls, float* eps, int B, int h, int w, void* ws, size_t wsb,

@@ -15,6 +15,13 @@
 
 #include "../../include/diffmusic_hip.h"
 
+// entry points added to C-ABI version 4 without a version bump: weak, so that a libdiffmusic_hip.so of that version built before them
+// still lets this library load far enough to say what is missing (TORCH_LIBRARY init below)
+#pragma weak dmx_vae_encoder_create
+#pragma weak dmx_vae_encoder_workspace_bytes
+#pragma weak dmx_vae_encode_fwd
+#pragma weak dmx_latent_init
+
 namespace {
 
 // every op makes its first tensor's device current for its own duration, so the outputs are allocated there and the launch goes to
@@ -272,6 +279,34 @@ std::tuple<at::Tensor, std::optional<at::Tensor>> vae_dec_fwd(int64_t model, con
                         mel32 ? mel32->data_ptr<float>() : nullptr, B, h, w, keep_state, ws.data_ptr(), ws.nbytes(), cur_stream()), "vae_dec_fwd");
   return {mel, mel32};
 }
+// `vae.encode(mel).latent_dist` moments (include/diffmusic_hip.h dmx_vae_encode_fwd): (B, h * w, 2 * latent) fp32
+at::Tensor vae_enc_fwd(int64_t model, const at::Tensor& mel, double log_floor, int64_t latent_channels, int64_t scale_factor, at::Tensor ws) {
+  f32_cuda(mel, "mel");
+  TORCH_CHECK(mel.dim() == 3 && scale_factor >= 1, "mel must be (B, frames, bins)");
+  DMX_DEVICE_OF(mel);
+  const int B = (int)mel.size(0), T = (int)mel.size(1), F = (int)mel.size(2);
+  at::Tensor mom = at::empty({B, (T / scale_factor) * (F / scale_factor), 2 * latent_channels}, mel.options());
+  ok(dmx_vae_encode_fwd(reinterpret_cast<dmx_model*>(model), mel.data_ptr<float>(), (float)log_floor, mom.data_ptr<float>(), B, T, F,
+                        ws.data_ptr(), ws.nbytes(), cur_stream()), "vae_enc_fwd");
+  return mom;
+}
+// (mean, clamped logvar, noised start latent or None) from the moments (dmx_latent_init)
+std::tuple<at::Tensor, at::Tensor, std::optional<at::Tensor>> latent_init(const at::Tensor& moments, int64_t h, int64_t w, const std::optional<at::Tensor>& eps,
+                                                                          const std::optional<at::Tensor>& noise, double sqrt_abar, double scaling_factor,
+                                                                          double sqrt_1m_abar, bool want_x) {
+  f32_cuda(moments, "moments");
+  TORCH_CHECK(moments.dim() == 3 && moments.size(1) == h * w && moments.size(2) % 2 == 0, "moments must be (B, h * w, 2 * latent_channels)");
+  DMX_DEVICE_OF(moments);
+  const int64_t B = moments.size(0), L = moments.size(2) / 2;
+  at::Tensor mean = at::empty({B, L, h, w}, moments.options()), logvar = at::empty({B, L, h, w}, moments.options());
+  if (eps) { f32_cuda(*eps, "eps"); same_numel(mean, *eps, "latent_init(eps)"); }
+  if (noise) { f32_cuda(*noise, "noise"); same_numel(mean, *noise, "latent_init(noise)"); }
+  std::optional<at::Tensor> x;
+  if (want_x) x = at::empty({B, L, h, w}, moments.options());
+  ok(dmx_latent_init(moments.data_ptr<float>(), mean.data_ptr<float>(), logvar.data_ptr<float>(), x ? x->data_ptr<float>() : nullptr, fp(eps), fp(noise),
+                     (int)B, (int)L, (int)(h * w), (float)sqrt_abar, (float)scaling_factor, (float)sqrt_1m_abar, cur_stream()), "latent_init");
+  return {mean, logvar, x};
+}
 // per-clip rescale of the waveform gradient before the 16-bit backward sweep (max |g| -> target), IN PLACE; returns the factors that undo it
 at::Tensor grad_normalize_(at::Tensor dwav, double target) {
   f32_cuda(dwav, "dwav");
@@ -355,6 +390,15 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   // diffmusic_amd.ops.enabled() falls back to the ctypes binding (which checks the same number) with one warning.
   TORCH_CHECK(dmx_abi_version() == DMX_ABI_VERSION, "libdiffmusic_torch_ops.so was built against C-ABI version ", DMX_ABI_VERSION,
               " but the loaded libdiffmusic_hip.so reports ", dmx_abi_version(), ": rebuild with `python -m diffmusic_amd.build`");
+  {
+    const std::pair<const char*, const void*> added[] = {{"dmx_vae_encoder_create", (const void*)&dmx_vae_encoder_create},
+                                                         {"dmx_vae_encoder_workspace_bytes", (const void*)&dmx_vae_encoder_workspace_bytes},
+                                                         {"dmx_vae_encode_fwd", (const void*)&dmx_vae_encode_fwd},
+                                                         {"dmx_latent_init", (const void*)&dmx_latent_init}};
+    for (const auto& s : added)
+      TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
+                  "` (a build from before the VAE encoder entry points): rebuild with `python -m diffmusic_amd.build --force`");
+  }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
   // (written by *_fwd / mel_guidance, read by the matching *_bwd) and the network workspaces `ws` (written by *_fwd; the model handle's
@@ -383,6 +427,9 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("unet_fwd_ctx(int model, Tensor x, Tensor t, Tensor? class_labels, Tensor c0, Tensor c1, Tensor bias1, Tensor(a!) ws) -> Tensor", &unet_fwd_ctx);
   m.def("vae_dec_fwd(int model, Tensor z, float z_scale, bool keep_state, bool want_f32, int scale_factor, Tensor(a!) ws) -> (Tensor, Tensor?)", &vae_dec_fwd);
   m.def("vae_dec_bwd(int model, Tensor dmel, float z_scale, int latent_channels, int scale_factor) -> Tensor", &vae_dec_bwd);
+  m.def("vae_enc_fwd(int model, Tensor mel, float log_floor, int latent_channels, int scale_factor, Tensor(a!) ws) -> Tensor", &vae_enc_fwd);
+  m.def("latent_init(Tensor moments, int h, int w, Tensor? eps, Tensor? noise, float sqrt_abar, float scaling_factor, float sqrt_1m_abar, "
+        "bool want_x) -> (Tensor, Tensor, Tensor?)", &latent_init);
   m.def("grad_normalize_(Tensor(a!) dwav, float target) -> Tensor", &grad_normalize_);
   m.def("hifigan_fwd(int model, Tensor mel, Tensor(a!) ws) -> Tensor", &hifigan_fwd);
   m.def("hifigan_bwd(int model, Tensor dwav, int frames, int model_in_dim) -> Tensor", &hifigan_bwd);

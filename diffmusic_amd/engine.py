@@ -186,6 +186,70 @@ class VaeDecoderEngine(_Engine):
         return ops.hip.vae_dec_bwd(self._h.value, dmel, float(z_scale), self.cfg["latent_channels"], self.scale_factor)
 
 
+class LatentDistribution:
+    """`DiagonalGaussianDistribution` of diffusers over the encoder's moments: `mean`, `logvar` (clamped to [-30, 20]), `mode()`, `sample()`."""
+
+    def __init__(self, moments, h, w):
+        self.moments, self._hw = moments, (int(h), int(w))
+        self.mean, self.logvar, _ = ops.hip.latent_init(moments, h, w, None, None, 1.0, 1.0, 0.0, False)
+
+    def mode(self, scale=1.0):
+        """The mean (times `scale`, e.g. the VAE's scaling_factor, inside the kernel)."""
+        if scale == 1.0:
+            return self.mean
+        return ops.hip.latent_init(self.moments, *self._hw, None, None, 1.0, float(scale), 0.0, True)[2]
+
+    def sample(self, generator=None, scale=1.0):
+        """scale * (mean + std * eps); eps is drawn through `randn_tensor`, so a list of generators seeds every clip on its own."""
+        from .torch_utils import randn_tensor
+        eps = randn_tensor(self.mean.shape, generator=generator, device=self.mean.device, dtype=torch.float32).contiguous()
+        return ops.hip.latent_init(self.moments, *self._hw, eps, None, 1.0, float(scale), 0.0, True)[2]
+
+
+class VaeEncoderEngine(_Engine):
+    """`vae.encode(x).latent_dist` of diffusers AutoencoderKL (the vendored pipeline_stable_audio.py:477), forward only: the warm start
+    of a trajectory from an initial mel.  A model handle of its own over the checkpoint's `encoder.` / `quant_conv.` tensors."""
+    kind = "vae_enc"
+    allow_unexpected = ("decoder.", "post_quant_conv.")      # the decoder half of the same AutoencoderKL checkpoint (VaeDecoderEngine)
+
+    def __init__(self, config=None, device="cuda"):
+        cfg = dict(VAE_DEFAULT)
+        cfg.update(config or {})
+        c = L.VaeConfig()
+        c.latent_channels, c.out_channels = cfg["latent_channels"], cfg["out_channels"]
+        c.num_blocks = len(cfg["block_out_channels"])
+        _fill(c.block_out_channels, cfg["block_out_channels"])
+        c.layers_per_block, c.norm_num_groups, c.eps = cfg["layers_per_block"], cfg["norm_num_groups"], cfg["eps"]
+        super().__init__(L.lib().dmx_vae_encoder_create(C.byref(c)), cfg, device)
+        self.scale_factor = 2 ** (c.num_blocks - 1)
+        self.scaling_factor = cfg["scaling_factor"]
+
+    @property
+    def config(self):
+        from types import SimpleNamespace
+        return SimpleNamespace(**self.cfg)
+
+    def encode_hip(self, mel, log_floor=0.0):
+        """mel (B, frames, bins) fp32 cuda -> moments (B, h * w, 2 * latent) fp32 = [mean | logvar] per latent position, before the clamp.
+        log_floor > 0: the input stage takes ln(max(mel, log_floor)) on load (a linear-magnitude mel, ModelMelFrontend)."""
+        assert mel.dtype == torch.float32 and mel.is_cuda and mel.is_contiguous() and mel.dim() == 3
+        B, T, F = mel.shape
+        nbytes = L.lib().dmx_vae_encoder_workspace_bytes(self._h, B, T, F)
+        if nbytes == 0:
+            L.check(-1, "vae encoder workspace")
+        ws = self._workspace(("e", B, T, F), nbytes)
+        return ops.hip.vae_enc_fwd(self._h.value, mel, float(log_floor), self.cfg["latent_channels"], self.scale_factor, ws)
+
+    def encode(self, mel, log_floor=0.0):
+        """diffusers-shaped `vae.encode(x)`: mel (B, frames, bins) or (B, 1, frames, bins) -> namespace with `latent_dist`."""
+        from types import SimpleNamespace
+        if mel.dim() == 4:
+            mel = mel.squeeze(1)
+        mel = mel.to(device=self.device, dtype=torch.float32).contiguous()
+        s = self.scale_factor
+        return SimpleNamespace(latent_dist=LatentDistribution(self.encode_hip(mel, log_floor), mel.shape[1] // s, mel.shape[2] // s))
+
+
 class UNetEngine(_Engine):
     """`self.unet(latent_model_input, t, encoder_hidden_states=None, class_labels=prompt_embeds)[0]`
     of the reference (pipeline_musicldm.py:696-703), forward only."""

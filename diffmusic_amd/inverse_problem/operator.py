@@ -114,6 +114,30 @@ class SpectralFrontend:
         return ops.ctypes_hip.melscale_fwd(self._h.value, mag.contiguous(), float(lo), float(hi), n_mels=self.n_mels)
 
 
+class ModelMelFrontend:
+    """Waveform -> mel in the domain the VAE / vocoder work in, for warm-started sampling (`init_audio`): STFT magnitudes (hann, centred,
+    reflect-padded) through a slaney-normalised mel bank, then the natural log with a floor.  The log is NOT taken here: `__call__`
+    returns the linear magnitudes and the encoder's input stage applies ln(max(x, log_floor)) on load (VaeEncoderEngine.encode,
+    `log_floor=`).  The defaults (n_fft 1024, hop 160, 64 bins, 0-8000 Hz, floor 1e-5) are the AudioLDM / MusicLDM training front end
+    as recalled -- that code is third-party and was not available to check against, so every one of them is a constructor argument."""
+
+    def __init__(self, sample_rate=16000, n_fft=1024, hop_length=160, n_mels=64, f_min=0.0, f_max=8000.0, log_floor=1e-5):
+        from transformers.audio_utils import mel_filter_bank
+        self.fb = mel_filter_bank(num_frequency_bins=n_fft // 2 + 1, num_mel_filters=n_mels, min_frequency=float(f_min),
+                                  max_frequency=float(f_max), sampling_rate=sample_rate, norm="slaney", mel_scale="slaney")
+        self.frontend = SpectralFrontend(sample_rate, n_fft, hop_length, n_mels, "hann", fb=self.fb)
+        self.log_floor = float(log_floor)
+
+    def __call__(self, wav, length, frames):
+        """wav (B, >= length) fp32 cuda -> (B, frames, n_mels) fp32 linear mel magnitudes: the clip's 1 + length // hop frames cropped, or
+        padded with the floor value (ln gives the floor's log there), to `frames`."""
+        mel = self.frontend.transform_fwd(wav, int(length), power2=False, to_db=False)
+        have = mel.shape[1]
+        if have >= frames:
+            return mel[:, :frames].contiguous()
+        return torch.nn.functional.pad(mel, (0, 0, 0, frames - have), value=self.log_floor).contiguous()
+
+
 def l2_loss(ref, pred, want_grad=True, gscale=1.0):
     """per-clip ||ref - pred||_2 over all trailing dims; ref may have batch 1 (broadcast)."""
     ref = ref.contiguous()

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..engine import HifiGanEngine, UNetEngine, VaeDecoderEngine
+from ..engine import HifiGanEngine, UNetEngine, VaeDecoderEngine, VaeEncoderEngine
 from ..torch_utils import randn_tensor
 from ..profiling import stage
 from ..inverse_problem.noise import step_sigma
@@ -28,8 +28,11 @@ class AudioPipelineOutput(SimpleNamespace):
 
 
 class MusicLDMPipeline:
-    def __init__(self, vae, unet, vocoder, scheduler=None):
+    def __init__(self, vae, unet, vocoder, scheduler=None, vae_encoder=None):
         self.vae, self.unet, self.vocoder, self.scheduler = vae, unet, vocoder, scheduler
+        self._vae_encoder = vae_encoder   # VaeEncoderEngine or None: the warm start (`init_audio` / `init_mel` + `strength`) needs it
+        self._synthetic_encoder = None    # (config, seed) of from_pretrained("synthetic"): the encoder is built on first use
+        self.mel_frontend = None          # ModelMelFrontend for `init_audio`, built on first use (or set one with other parameters)
         self.vae_scale_factor = 2 ** (len(self.vae.config.block_out_channels) - 1)
         self.device = torch.device("cuda")
         self.nan_check_every = 1          # host check of the loss every k steps (reference: every step, :742)
@@ -54,6 +57,7 @@ class MusicLDMPipeline:
             if n_ctx != want:
                 raise ConfigError(f"{repo_id}/unet: a U-Net with {n_ctx} cross-attention context(s), but {cls.__name__} conditions on {want}")
             unet, vae, voc = UNetEngine(cfgs["unet"]), VaeDecoderEngine(cfgs["vae"]), HifiGanEngine(cfgs["vocoder"])
+            enc = None
             from safetensors.torch import load_file
             for eng, sub in ((unet, "unet"), (vae, "vae"), (voc, "vocoder")):
                 files = [f for f in os.listdir(os.path.join(repo_id, sub)) if f.endswith(".safetensors")]
@@ -61,12 +65,32 @@ class MusicLDMPipeline:
                 for f in files:
                     sd.update(load_file(os.path.join(repo_id, sub, f)))
                 eng.load_state_dict(sd, strict=True)          # fails with the full list of missing / mis-shaped / unknown tensors
+                if sub == "vae" and any(k.startswith("encoder.") for k in sd):
+                    # the checkpoint carries the encoder half of the AutoencoderKL: warm-started sampling is available
+                    enc = VaeEncoderEngine(cfgs["vae"]).load_state_dict(sd, strict=True)
+            return cls(vae, unet, voc, vae_encoder=enc)
         else:
             unet = UNetEngine(unet_config if unet_config is not None else cls.unet_default_config)
             vae, voc = VaeDecoderEngine(vae_config), HifiGanEngine(vocoder_config)
             for i, eng in enumerate((unet, vae, voc)):
                 eng.load_state_dict(eng.synth_state_dict(seed=seed + i))
-        return cls(vae, unet, voc)
+        pipe = cls(vae, unet, voc)
+        pipe._synthetic_encoder = (vae_config, seed + 3)      # seeds 0..2 stay those of the three networks above
+        return pipe
+
+    @property
+    def vae_encoder(self):
+        """The encoder half of the VAE.  A synthetic pipeline builds it when it is first asked for, so that a pipeline that never
+        warm-starts allocates and launches exactly what it did without one."""
+        if self._vae_encoder is None and self._synthetic_encoder is not None:
+            cfg, seed = self._synthetic_encoder
+            enc = VaeEncoderEngine(cfg)
+            self._vae_encoder = enc.load_state_dict(enc.synth_state_dict(seed=seed))
+        return self._vae_encoder
+
+    @vae_encoder.setter
+    def vae_encoder(self, enc):
+        self._vae_encoder, self._synthetic_encoder = enc, None
 
     def to(self, device):
         self.device = torch.device(device)
@@ -156,12 +180,17 @@ class MusicLDMPipeline:
                  negative_prompt_embeds=None, return_dict=True, callback=None, callback_steps=1, cross_attention_kwargs=None,
                  output_type="np", measurement=None, optim_prompt=False, ip_guidance_rate=0.0005,
                  optim_prompt_learning_rate=0.0001, optim_outer_loop=1, show_progress=True, prompt_type=None,
-                 supervised_space="mel_spectrogram", shard=False, group=None, lanes=None):
+                 supervised_space="mel_spectrogram", shard=False, group=None, lanes=None, init_audio=None, init_mel=None, strength=1.0,
+                 init_posterior="sample"):
         """Reference signature (pipeline_musicldm.py:493-519) plus `shard` / `group` (extension): with
         torch.distributed initialised, `shard=True` (or a process `group`) makes every rank run clips k = rank, rank + G, ... of
         the batch and all-gathers the finished waveforms once at the end (RCCL over xGMI); every rank returns all B clips.
         `lanes` (default `self.lanes`): > 1 runs this rank's clips as that many clip lanes whose U-Net forwards are hidden under
-        each other's guidance sweeps (pipelines/lanes.py); a lane's clips see exactly a call on those clips alone."""
+        each other's guidance sweeps (pipelines/lanes.py); a lane's clips see exactly a call on those clips alone.
+        Warm start (extension; diffusers' img2img `strength`): `init_audio` (B, >= L) waveform at the vocoder's rate, or `init_mel`
+        (B, height, model_in_dim) in the vocoder's input domain, is encoded once by `pipe.vae_encoder`, noised to the timestep
+        `scheduler.timesteps_for_strength(strength)` starts at, and only those steps run.  Per clip the posterior draw
+        (`init_posterior="sample"`; `"mode"`: none) comes first, then the latent noise, both from that clip's generator."""
         front = getattr(self, "text_frontend", None)
         do_cfg = guidance_scale > 1.0
         if prompt_embeds is None:
@@ -194,6 +223,9 @@ class MusicLDMPipeline:
         timesteps = list(self.scheduler._timesteps_host)
         nlat = self.unet.cfg["in_channels"]
         B_all = B = batch_size * num_waveforms_per_prompt
+        init = self._check_init(init_audio, init_mel, strength, init_posterior, latents, B_all, height, original_waveform_length)
+        if init is not None:
+            timesteps = self.scheduler.timesteps_for_strength(strength)      # the tail of the full list; num_inference_steps stays N
         if measurement is not None:
             measurement = measurement.to(device=device, dtype=torch.float32)      # once per call (transform(y) is cached per tensor)
         # ---- clip sharding (no per-step collective; clips are independent because norms and RNG are per clip)
@@ -222,6 +254,8 @@ class MusicLDMPipeline:
                 generator = [generator[k] for k in sel]
             if latents is not None:
                 latents = latents[sel]
+            if init is not None:
+                init = init[sel]                                     # the clip's rows first, then encode
             if measurement is not None and measurement.shape[0] == B_all and B_all > 1:
                 measurement = measurement[sel].contiguous()
             B = len(sel)
@@ -229,6 +263,17 @@ class MusicLDMPipeline:
         self.last_losses = []
         self.nan_restarts = 0
         n_lanes = int(self.lanes if lanes is None else lanes)
+        if init is not None and B > 0:
+            # encode once per call: outer iterations and NaN-retries reuse z0 and redraw only the latent noise
+            z0 = self._encode_init(init, init_audio is not None, init_posterior, generator, original_waveform_length, height, device)
+
+            def fresh_latents(given=None):
+                shape = (B, nlat, int(height) // self.vae_scale_factor, int(vcfg.model_in_dim) // self.vae_scale_factor)
+                noise = randn_tensor(shape, generator=generator, device=device, dtype=torch.float32)
+                return self.scheduler.add_noise(z0, noise, timesteps[0])
+        else:
+            def fresh_latents(given=None):
+                return self.prepare_latents(B, nlat, height, torch.float32, device, generator, given)
         if B > 0 and n_lanes > 1 and B > 1:
             if callback is not None:
                 raise ValueError("lanes > 1 cannot serve `callback(i, t, latents)`: the clip groups are at different steps at any one time")
@@ -243,13 +288,13 @@ class MusicLDMPipeline:
                                                                       self.scheduler.mode in ("dsg", "diffmusic")):
                 raise ValueError("lanes > 1 with per-step noise needs one generator per clip (a list of length B): one shared "
                                  "generator would be drawn from in another order than by the whole batch")
-            latents = self.prepare_latents(B, nlat, height, torch.float32, device, generator, latents)
+            latents = fresh_latents(latents)
             for _ in range(optim_outer_loop):
                 latents = self._denoise_lanes(n_lanes, latents, pe, do_cfg, guidance_scale, measurement, timesteps, generator, eta,
                                               original_waveform_length, ip_guidance_rate, supervised_space, optim_prompt,
-                                              optim_prompt_learning_rate, nlat, height, show_progress)
+                                              optim_prompt_learning_rate, nlat, height, show_progress, fresh_latents)
         elif B > 0:
-            latents = self.prepare_latents(B, nlat, height, torch.float32, device, generator, latents)
+            latents = fresh_latents(latents)
             init_latents = latents
             init_pe = pe
             for _ in range(optim_outer_loop):
@@ -261,7 +306,7 @@ class MusicLDMPipeline:
                     bar = None
                     if show_progress:
                         from tqdm import tqdm
-                        bar = tqdm(total=num_inference_steps)
+                        bar = tqdm(total=len(timesteps))
                     with bar if bar is not None else contextlib.nullcontext():
                         for i, t in enumerate(timesteps):
                             noise_pred = self._unet_eps(self.scheduler.scale_model_input(latents, t), t, pe, guidance_scale, do_cfg)
@@ -282,7 +327,7 @@ class MusicLDMPipeline:
                                 if bad:                                                             # NaN-retry (:741-756)
                                     retry -= 1
                                     self.nan_restarts += 1
-                                    latents = self.prepare_latents(B, nlat, height, torch.float32, device, generator, None)
+                                    latents = fresh_latents()
                                     is_done = False
                                     pe = init_pe
                                     break
@@ -318,7 +363,7 @@ class MusicLDMPipeline:
         return AudioPipelineOutput(audios=audio)
 
     def _denoise_lanes(self, n_lanes, latents, pe, do_cfg, guidance_scale, measurement, timesteps, generator, eta, length, rate,
-                       supervised_space, optim_prompt, optim_lr, nlat, height, show_progress):
+                       supervised_space, optim_prompt, optim_lr, nlat, height, show_progress, fresh_latents):
         """The loop of `__call__` (NaN-retry included) over clip lanes.  Lane k holds a contiguous group of this call's clips with
         their conditioning rows (both halves of the CFG batch), measurement rows and generators; every lane-step is the same
         `_unet_eps` + `scheduler.step` the plain loop makes, on the lane's stream (pipeline_musicldm.py:690-758)."""
@@ -375,7 +420,48 @@ class MusicLDMPipeline:
                 return torch.cat([ln.latents for ln in lanes], dim=0)
             retry -= 1                                                                  # NaN-retry (:741-756): all clips restart
             self.nan_restarts += 1
-            latents = self.prepare_latents(B, nlat, height, torch.float32, device, generator, None)
+            latents = fresh_latents()
+
+    # ---- warm start -------------------------------------------------------------------------
+    def _check_init(self, init_audio, init_mel, strength, init_posterior, latents, B_all, height, length):
+        """Argument rules of the warm start; returns the init tensor (None: the cold path, untouched)."""
+        if init_audio is None and init_mel is None:
+            if float(strength) != 1.0:
+                raise ValueError(f"strength = {strength!r} without init_audio / init_mel: a cold start runs every step (strength = 1.0)")
+            return None
+        if init_audio is not None and init_mel is not None:
+            raise ValueError("init_audio and init_mel are two spellings of one start: pass one of them")
+        if latents is not None:
+            raise ValueError("latents= together with init_audio / init_mel: the start latent comes from one or the other")
+        if init_posterior not in ("sample", "mode"):
+            raise ValueError(f"init_posterior = {init_posterior!r}: 'sample' or 'mode'")
+        if self.vae_encoder is None:
+            raise ValueError("init_audio / init_mel need pipe.vae_encoder (a VaeEncoderEngine): the checkpoint this pipeline was loaded "
+                             "from holds no encoder.* tensors")
+        if init_mel is not None:
+            want = (B_all, int(height), int(self.vocoder.config.model_in_dim))
+            if tuple(init_mel.shape) != want:
+                raise ValueError(f"init_mel has shape {tuple(init_mel.shape)}, expected {want} (clips, mel frames of this call, mel bins)")
+            return init_mel
+        if init_audio.dim() != 2 or init_audio.shape[0] != B_all or init_audio.shape[1] < length:
+            raise ValueError(f"init_audio has shape {tuple(init_audio.shape)}, expected ({B_all}, >= {length}) samples at the vocoder's rate")
+        return init_audio
+
+    def _encode_init(self, init, is_audio, init_posterior, generator, length, height, device):
+        """-> z0 * scaling_factor (B, latent, h, w): the clean start latent in the U-Net's scale.  Posterior draw first (per clip)."""
+        init = init.to(device=device, dtype=torch.float32).contiguous()
+        with stage("vae_encode"):
+            if is_audio:
+                if self.mel_frontend is None:
+                    from ..inverse_problem.operator import ModelMelFrontend
+                    self.mel_frontend = ModelMelFrontend(sample_rate=int(self.vocoder.config.sampling_rate),
+                                                         n_mels=int(self.vocoder.config.model_in_dim))
+                mel = self.mel_frontend(init, length, int(height))                      # linear magnitudes; ln(max(., floor)) on load
+                dist = self.vae_encoder.encode(mel, log_floor=self.mel_frontend.log_floor).latent_dist
+            else:
+                dist = self.vae_encoder.encode(init).latent_dist
+            sf = float(self.vae.config.scaling_factor)           # applied by the `latent_init` kernel
+            return dist.sample(generator, scale=sf) if init_posterior == "sample" else dist.mode(scale=sf)
 
     assume_uncond_equals_cond = False      # True: prompt_embeds without negative_prompt_embeds means prompt == "" (no warning)
 

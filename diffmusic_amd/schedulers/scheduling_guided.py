@@ -117,6 +117,35 @@ class GuidedDDIMScheduler:
             self.operator.reset_cache()           # a new trajectory: forget the cached transform(measurement)
         self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
 
+    # ---- warm start (init audio + strength): the trajectory begins at an intermediate timestep of the list set_timesteps(N) made
+    def timesteps_for_strength(self, strength):
+        """diffusers' img2img rule: the last `min(int(N * strength), N)` timesteps of the current list.  `num_inference_steps` stays N, so
+        the step width of `_scalars` and the position of a timestep in the full list (measurement-noise key) are those of a cold run."""
+        n = self.num_inference_steps
+        if n is None:
+            raise ValueError("call set_timesteps(num_inference_steps) before timesteps_for_strength")
+        if not 0.0 <= float(strength) <= 1.0:
+            raise ValueError(f"strength = {strength!r}: a number in [0, 1]")
+        n_run = min(int(n * float(strength)), n)
+        if n_run == 0:
+            raise ValueError(f"strength = {strength!r} leaves no step of num_inference_steps = {n} to run (int(N * strength) == 0)")
+        return list(self._timesteps_host[n - n_run:])
+
+    def add_noise_scalars(self, timestep):
+        """(sqrt(abar_t), sqrt(1 - abar_t)) as host floats from the fp32 table."""
+        a = float(self._ac[int(timestep)])
+        return a ** 0.5, (1.0 - a) ** 0.5
+
+    def add_noise(self, original_samples, noise, timestep):
+        """x_t = sqrt(abar_t) x0 + sqrt(1 - abar_t) noise (diffusers `add_noise`, one host timestep for the batch); the sum is the HIP
+        `noise_add` launch."""
+        if not original_samples.is_cuda:
+            raise RuntimeError("diffmusic_amd schedulers run on the GPU only (no CPU fallback)")
+        sa, s1 = self.add_noise_scalars(timestep)
+        x0 = (original_samples.detach().to(torch.float32) * sa).contiguous()
+        z = noise.detach().to(device=x0.device, dtype=torch.float32).contiguous()
+        return ops.hip.noise_add(x0, z, float(s1)).to(original_samples.dtype)
+
     def _get_variance(self, timestep, prev_timestep):
         a_t = float(self._ac[timestep])
         a_p = float(self._ac[prev_timestep]) if prev_timestep >= 0 else float(self.final_alpha_cumprod)

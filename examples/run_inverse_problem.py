@@ -50,6 +50,19 @@ def build_operator(task, cfg, mask_type):
     return op, scale
 
 
+# why the measurement of a task cannot seed a warm start (the encoder takes a full-rate waveform of the clip's length)
+NO_WARM_START = dict(super_resolution="its measurement is sampled at 1 / scale of the model's rate",
+                     phase_retrieval="its measurement is an STFT magnitude, not a waveform")
+
+
+def init_from_measurement(task, measurement, length):
+    if task in NO_WARM_START:
+        raise SystemExit(f"--init measurement is not available for {task}: {NO_WARM_START[task]}")
+    if measurement.dim() != 2 or measurement.shape[1] < length:
+        raise SystemExit(f"--init measurement needs a (B, >= {length}) waveform, the measurement is {tuple(measurement.shape)}")
+    return measurement
+
+
 def load_clips(paths, n, sr, length, seed, start_s=0.0):
     """(B, length) fp32 in [-1, 1]: wav files decoded, mixed down to mono and resampled to `sr` by the dataset loader
     (diffmusic_amd/data/dataloader.py; reference dataloader.py:47-89), cropped from `start_s` / zero-padded to `length`;
@@ -88,6 +101,9 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--output_dir", default="outputs")
     ap.add_argument("--show_progress", action="store_true")
+    ap.add_argument("--init", default="none", choices=["none", "measurement"],
+                    help="warm start: encode the measurement, noise it to an intermediate timestep and run only the last steps (--strength)")
+    ap.add_argument("--strength", type=float, default=1.0, help="share of num_inference_steps a warm start runs (diffusers' img2img rule)")
     return ap.parse_args(argv)
 
 
@@ -112,6 +128,10 @@ def main(argv=None):
     else:
         pe = torch.nn.functional.normalize(torch.randn(B, 512, generator=torch.Generator().manual_seed(args.seed)), dim=-1)
     gens = [torch.Generator().manual_seed(args.seed + i) for i in range(B)]
+    if args.init == "measurement":
+        pipe_kw.update(init_audio=init_from_measurement(args.task, measurement, length), strength=args.strength)
+    elif args.strength != 1.0:
+        raise SystemExit("--strength needs --init measurement (a cold start runs every step)")
     audio = pipe(prompt_embeds=pe[:B], measurement=measurement, eta=cfg.scheduler.eta, ip_guidance_rate=cfg.scheduler.ip_guidance_rate,
                  generator=gens, show_progress=args.show_progress, supervised_space=args.supervised_space, **pipe_kw).audios
     out = Path(args.output_dir, cfg.model.name, cfg.data.name, args.config_name, args.task)

@@ -28,7 +28,9 @@ extern "C" {
 #endif
 
 /* Additive changes do not bump the version: dmx_audio_guidance_{fwd,bwd}_ex and dmx_noise_add (measurement noise inside the guided
- * step) are new symbols, and every earlier entry point keeps its signature. */
+ * step), and dmx_vae_encoder_* / dmx_vae_encode_fwd / dmx_latent_init / dmx_conv2d_raw (VAE encoder, warm-started sampling) are new
+ * symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
 
@@ -111,6 +113,22 @@ int dmx_vae_decode_fwd(dmx_model* m, const float* z, float z_scale, uint16_t* me
                        int keep_state, void* ws, size_t ws_bytes, void* stream);
 /* dmel (B, 4h, 4w) f16 -> dz (B, latent_channels, h, w) fp32 NCHW, multiplied by z_scale */
 int dmx_vae_decode_bwd(dmx_model* m, const uint16_t* dmel, float z_scale, float* dz, void* stream);
+
+/* ---- VAE encoder: `vae.encode(x).latent_dist` of diffusers AutoencoderKL (the vendored pipeline_stable_audio.py:477 call site), forward
+ * only.  Same config struct as the decoder (the input has `out_channels` channels, 1 for both models); parameter names are the
+ * checkpoint's "encoder. ..." and "quant_conv. ..." tensors.  batch <= 64; frames and bins positive multiples of 2^(num_blocks-1);
+ * latent_channels a multiple of 4. ------------------------------------------------------------------------------------------------- */
+dmx_model* dmx_vae_encoder_create(const dmx_vae_config* cfg);
+size_t dmx_vae_encoder_workspace_bytes(dmx_model* m, int batch, int frames, int bins);   /* 0: unsupported shape (dmx_last_error()) */
+/* mel (B, frames, bins) fp32, one channel (the vocoder's input layout); log_floor > 0: ln(max(mel, log_floor)) is taken on load ->
+ * moments (B, h * w, 2 * latent_channels) fp32 channels-last = [mean | logvar] before the clamp, h = frames / s, w = bins / s */
+int dmx_vae_encode_fwd(dmx_model* m, const float* mel, float log_floor, float* moments, int batch, int frames, int bins, void* ws,
+                       size_t ws_bytes, void* stream);
+/* moments (B, hw, 2L) -> mean, logvar (B, L, hw) fp32 NCHW, logvar clamped to [-30, 20] (DiagonalGaussianDistribution) and, when x != NULL,
+ * x = sqrt_abar * scaling_factor * (mean + exp(0.5 logvar) * eps) + sqrt_1m_abar * noise  (B, L, hw): the start latent of a warm-started
+ * trajectory.  eps, noise (B, L, hw) fp32; eps NULL = posterior mode, noise NULL = no noise term. */
+int dmx_latent_init(const float* moments, float* mean, float* logvar, float* x, const float* eps, const float* noise, int batch,
+                    int latent_channels, int hw, float sqrt_abar, float scaling_factor, float sqrt_1m_abar, void* stream);
 
 /* ---- U-Net forward: replaces `self.unet(latent_model_input, t, ..., class_labels=...)` -------- */
 size_t dmx_unet_workspace_bytes(dmx_model* m, int batch, int h, int w);
@@ -298,6 +316,11 @@ size_t dmx_groupnorm_part_floats(int B, int P, int N);
 int dmx_groupnorm_parts_raw(const void* x, void* y, const float* gamma, const float* beta, float* stats, float* scale, float* shift,
                             int B, int P, int C, int G, float eps, int silu, int nreg, float* const* part, const int* geom, void* stream);
 int dmx_gemm_last_tile_rows_raw(void);
+/* test hook: one 2-D convolution as the executors build it (weights w_host (Co, Ci, k, k) and bias b_host (Co) fp32 in HOST memory):
+ * x (B, Hi, Wi, pad8(Ci)) -> y (B, Ho, Wo, pad8(Co)) 16-bit channels-last, pad_lo zero rows / columns before the image and pad_hi after
+ * it (Ho = (Hi + pad_lo + pad_hi - k) / stride + 1).  Allocates and synchronises. */
+int dmx_conv2d_raw(const float* w_host, const float* b_host, const void* x, void* y, int B, int Hi, int Wi, int Ci, int Co, int k, int stride,
+                   int pad_lo, int pad_hi, void* stream);
 /* GroupNorm(+SiLU) backward (input gradient): the two per-group sums from EPI_GNBWD partial sums of the dgrad launch that produced dy
  * (nreg regions, as above) or, with nreg == 0, from the classic pass over x and dy.  stats / scale / shift: the forward's outputs;
  * k0, k1: (B, C) fp32 scratch; partial: dmx_groupnorm_scratch_floats(B, C, G) floats (used when nreg == 0); add: optional tensor added to dx. */
