@@ -171,6 +171,32 @@ def noise_add(y, noise, sigma):
     return out
 
 
+def track_stitch_fwd(wav, starts, L, R, T):
+    """wav (W, >= L) with any row stride -> the (1, T) track: the windows at `starts`, cross-faded with the overlap taper R."""
+    W = wav.shape[0]
+    if not wav.is_cuda:
+        raise RuntimeError("track_stitch_fwd: wav must be (W, >= L) fp32 on the GPU (no CPU fallback)")
+    assert wav.dtype == torch.float32 and wav.dim() == 2 and wav.stride(1) == 1 and len(starts) == W and wav.shape[1] >= L, \
+        (wav.shape, len(starts), L)
+    track = torch.empty(1, T, dtype=torch.float32, device=wav.device)
+    arr = (C.c_int * W)(*[int(s) for s in starts])
+    _lib.check(_lib.lib().dmx_track_stitch_fwd(_p(wav), wav.stride(0), _p(track), arr, W, L, R, T, _stream()), "track_stitch_fwd")
+    return track
+
+
+def track_stitch_bwd(dtrack, starts, L, R, Lfull):
+    """The transpose: dtrack (1, T) contiguous -> (W, Lfull), zeros past L."""
+    W = len(starts)
+    if not dtrack.is_cuda:
+        raise RuntimeError("track_stitch_bwd: dtrack must be a GPU tensor (no CPU fallback)")
+    assert dtrack.dtype == torch.float32 and dtrack.is_contiguous() and W >= 1, dtrack.shape
+    dwav = torch.empty(W, Lfull, dtype=torch.float32, device=dtrack.device)
+    arr = (C.c_int * W)(*[int(s) for s in starts])
+    _lib.check(_lib.lib().dmx_track_stitch_bwd(_p(dtrack), _p(dwav), Lfull, arr, W, L, R, dtrack.numel(), Lfull, _stream()),
+               "track_stitch_bwd")
+    return dwav
+
+
 def stft_mag_fwd(audio, wav, state, L):
     lib = _lib.lib()
     B = wav.shape[0]

@@ -148,6 +148,8 @@ _SIGS = {
     "dmx_audio_melscale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
     "dmx_mask_apply": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dmx_l2_loss": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_void_p]),
+    "dmx_track_stitch_fwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.POINTER(C.c_int)] + [C.c_int] * 4 + [C.c_void_p]),
+    "dmx_track_stitch_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_int)] + [C.c_int] * 5 + [C.c_void_p]),
     "dmx_grad_normalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_void_p]),
     "dmx_fir_fwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 7 + [C.c_void_p]),
     "dmx_fir_bwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 7 + [C.c_void_p]),
@@ -161,7 +163,8 @@ _SIGS = {
 
 # entry points added to ABI version 4 without a version bump (include/diffmusic_hip.h): a library of that version built before them
 # loads, so their presence is checked by name
-ADDED_IN_V4 = ("dmx_vae_encoder_create", "dmx_vae_encoder_workspace_bytes", "dmx_vae_encode_fwd", "dmx_latent_init")
+ADDED_IN_V4 = ("dmx_vae_encoder_create", "dmx_vae_encoder_workspace_bytes", "dmx_vae_encode_fwd", "dmx_latent_init",
+               "dmx_track_stitch_fwd", "dmx_track_stitch_bwd")
 
 _lib = None
 
@@ -171,7 +174,7 @@ def check_symbols(h, path=LIB_PATH):
     for name in ADDED_IN_V4:
         if not hasattr(h, name):
             raise RuntimeError(f"{path} reports ABI version {ABI_VERSION} but does not export `{name}` (a build from before the VAE "
-                               "encoder entry points): rebuild it (python -m diffmusic_amd.build --force)")
+                               "encoder / track-mode entry points): rebuild it (python -m diffmusic_amd.build --force)")
 
 
 def lib():

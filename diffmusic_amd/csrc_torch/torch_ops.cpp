@@ -21,6 +21,8 @@
 #pragma weak dmx_vae_encoder_workspace_bytes
 #pragma weak dmx_vae_encode_fwd
 #pragma weak dmx_latent_init
+#pragma weak dmx_track_stitch_fwd
+#pragma weak dmx_track_stitch_bwd
 
 namespace {
 
@@ -215,6 +217,27 @@ at::Tensor noise_add(const at::Tensor& y, const at::Tensor& noise, double sigma)
   ok(dmx_noise_add(y.data_ptr<float>(), noise.data_ptr<float>(), out.data_ptr<float>(), y.numel(), (float)sigma, cur_stream()), "noise_add");
   return out;
 }
+// track mode (include/diffmusic_hip.h dmx_track_stitch_{fwd,bwd}): the windows wav (W, >= L) at `starts` -> the (1, T) track, and the transpose
+at::Tensor track_stitch_fwd(const at::Tensor& wav, at::IntArrayRef starts, int64_t L, int64_t R, int64_t T) {
+  TORCH_CHECK(wav.is_cuda() && wav.scalar_type() == at::kFloat && wav.dim() == 2 && wav.stride(1) == 1, "wav must be (W, >= L) fp32 on the GPU");
+  TORCH_CHECK((int64_t)starts.size() == wav.size(0) && wav.size(1) >= L, "one start per window, windows of at least L samples");
+  DMX_DEVICE_OF(wav);
+  at::Tensor track = at::empty({1, T}, wav.options());
+  std::vector<int> s(starts.begin(), starts.end());
+  ok(dmx_track_stitch_fwd(wav.data_ptr<float>(), wav.stride(0), track.data_ptr<float>(), s.data(), (int)s.size(), (int)L, (int)R, (int)T, cur_stream()),
+     "track_stitch_fwd");
+  return track;
+}
+at::Tensor track_stitch_bwd(const at::Tensor& dtrack, at::IntArrayRef starts, int64_t L, int64_t R, int64_t Lfull) {
+  f32_cuda(dtrack, "dtrack");
+  TORCH_CHECK(!starts.empty(), "one start per window");
+  DMX_DEVICE_OF(dtrack);
+  at::Tensor dwav = at::empty({(int64_t)starts.size(), Lfull}, dtrack.options());
+  std::vector<int> s(starts.begin(), starts.end());
+  ok(dmx_track_stitch_bwd(dtrack.data_ptr<float>(), dwav.data_ptr<float>(), Lfull, s.data(), (int)s.size(), (int)L, (int)R, (int)dtrack.numel(), (int)Lfull,
+                          cur_stream()), "track_stitch_bwd");
+  return dwav;
+}
 at::Tensor stft_mag_fwd(int64_t audio, const at::Tensor& wav, const at::Tensor& state, int64_t L) {
   dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
   TORCH_CHECK(wav.is_cuda() && wav.scalar_type() == at::kFloat && wav.dim() == 2 && wav.stride(1) == 1, "wav must be (B, >= L) fp32 on the GPU");
@@ -394,10 +417,12 @@ TORCH_LIBRARY(diffmusic_hip, m) {
     const std::pair<const char*, const void*> added[] = {{"dmx_vae_encoder_create", (const void*)&dmx_vae_encoder_create},
                                                          {"dmx_vae_encoder_workspace_bytes", (const void*)&dmx_vae_encoder_workspace_bytes},
                                                          {"dmx_vae_encode_fwd", (const void*)&dmx_vae_encode_fwd},
-                                                         {"dmx_latent_init", (const void*)&dmx_latent_init}};
+                                                         {"dmx_latent_init", (const void*)&dmx_latent_init},
+                                                         {"dmx_track_stitch_fwd", (const void*)&dmx_track_stitch_fwd},
+                                                         {"dmx_track_stitch_bwd", (const void*)&dmx_track_stitch_bwd}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
-                  "` (a build from before the VAE encoder entry points): rebuild with `python -m diffmusic_amd.build --force`");
+                  "` (a build from before the VAE encoder / track-mode entry points): rebuild with `python -m diffmusic_amd.build --force`");
   }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
@@ -420,6 +445,8 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("mel_guidance_noisy(int audio, Tensor wav, Tensor? mask, Tensor ref, Tensor(a!) state, int L, int Lfull, bool power2, bool to_db, float lo, "
         "float hi, float gscale, Tensor? noise, Tensor? noise_mag, float sigma) -> (Tensor, Tensor)", &mel_guidance_noisy);
   m.def("noise_add(Tensor y, Tensor noise, float sigma) -> Tensor", &noise_add);
+  m.def("track_stitch_fwd(Tensor wav, int[] starts, int L, int R, int T) -> Tensor", &track_stitch_fwd);
+  m.def("track_stitch_bwd(Tensor dtrack, int[] starts, int L, int R, int Lfull) -> Tensor", &track_stitch_bwd);
   m.def("stft_mag_fwd(int audio, Tensor wav, Tensor(a!) state, int L) -> Tensor", &stft_mag_fwd);
   m.def("stft_mag_bwd(int audio, Tensor dmag, Tensor state, int L, int Lfull) -> Tensor", &stft_mag_bwd);
   m.def("melscale_fwd(int audio, Tensor mag, float lo, float hi) -> Tensor", &melscale_fwd);

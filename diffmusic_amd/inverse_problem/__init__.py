@@ -1,6 +1,7 @@
 from .noise import GaussianNoise, PoissonNoise
 from .operator import (BaseOperator, IdentityOperator, MusicInpaintingOperator, PhaseRetrievalOperator,
                        SuperResolutionOperator, MusicDereverberationOperator, StyleGuidanceOperator)
+from .track import TrackLayout, TrackOperator, seconds_for_samples
 
 
 def get_noiser(name, sigma, stream="global"):  # reference: inverse_problem/__init__.py:4-11; `stream`: GaussianNoise's per-step stream

@@ -20,6 +20,7 @@ from ..engine import HifiGanEngine, UNetEngine, VaeDecoderEngine, VaeEncoderEngi
 from ..torch_utils import randn_tensor
 from ..profiling import stage
 from ..inverse_problem.noise import step_sigma
+from ..inverse_problem.track import TrackOperator
 from .. import parallel
 
 
@@ -223,6 +224,9 @@ class MusicLDMPipeline:
         timesteps = list(self.scheduler._timesteps_host)
         nlat = self.unet.cfg["in_channels"]
         B_all = B = batch_size * num_waveforms_per_prompt
+        track = self.scheduler.operator if isinstance(self.scheduler.operator, TrackOperator) else None
+        if track is not None:
+            self._check_track(track, B_all, original_waveform_length, shard, group, lanes)
         init = self._check_init(init_audio, init_mel, strength, init_posterior, latents, B_all, height, original_waveform_length)
         if init is not None:
             timesteps = self.scheduler.timesteps_for_strength(strength)      # the tail of the full list; num_inference_steps stays N
@@ -349,7 +353,10 @@ class MusicLDMPipeline:
         if B > 0:
             with stage("final_decode"):
                 mel = self.vae.decode(latents / self.vae.config.scaling_factor).sample                 # (B,1,H,W) fp32
-                audio = self.vocoder(mel.squeeze(1))[:, :original_waveform_length].float()         # :428-435, on the device
+                if track is None:
+                    audio = self.vocoder(mel.squeeze(1))[:, :original_waveform_length].float()     # :428-435, on the device
+                else:
+                    audio = track.stitch(self.vocoder(mel.squeeze(1)).float())                     # the W windows -> the (1, T) track
         else:
             audio = torch.zeros(0, original_waveform_length, dtype=torch.float32, device=device)
         if sel is not None:
@@ -421,6 +428,25 @@ class MusicLDMPipeline:
             retry -= 1                                                                  # NaN-retry (:741-756): all clips restart
             self.nan_restarts += 1
             latents = fresh_latents()
+
+    # ---- track mode -------------------------------------------------------------------------
+    def _check_track(self, track, B_all, length, shard, group, lanes):
+        """Argument rules of a call whose operator is a TrackOperator (inverse_problem/track.py): the batch is the track's windows, one
+        sample under one loss, so nothing may split it and the scheduler's norms go over all of it."""
+        lay = track.layout
+        if B_all != lay.num_windows:
+            raise ValueError(f"track mode: the call holds {B_all} clips, but the track has {lay.num_windows} windows ({lay!r}): pass one "
+                             "prompt embedding per window")
+        if length != lay.window_len:
+            raise ValueError(f"track mode: audio_length_in_s gives windows of {length} samples, but the layout's window_len is "
+                             f"{lay.window_len}")
+        if shard or group is not None:
+            raise ValueError("track mode cannot be sharded over ranks (shard / group): the windows are coupled in every step")
+        if int(self.lanes if lanes is None else lanes) > 1:
+            raise ValueError("track mode cannot run as clip lanes (lanes > 1): the windows are coupled in every step")
+        if getattr(self.scheduler, "per_clip_norm", False):
+            raise ValueError("track mode needs whole-batch norms: construct the scheduler with per_clip_norm=False")
+        track.check_noise_stream()
 
     # ---- warm start -------------------------------------------------------------------------
     def _check_init(self, init_audio, init_mel, strength, init_posterior, latents, B_all, height, length):

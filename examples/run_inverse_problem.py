@@ -7,6 +7,11 @@ embedding file (`--prompt_embeds x.npy`, (B, 512) CLAP text embeddings for Music
 
     python examples/run_inverse_problem.py -c dps -t music_inpainting --wav a.wav b.wav --weights /ckpt/musicldm
     python examples/run_inverse_problem.py -c mpgd -t super_resolution --num_inference_steps 20      # synthetic clips + weights
+    python examples/run_inverse_problem.py -c dps -t music_dereverberation --wav take.wav --track_overlap_s 1.28   # a long take, whole
+
+`--track_overlap_s S` restores a recording longer than the model window whole (track mode, inverse_problem/track.py): the first `--wav`
+(or a synthetic 2.5-window signal) becomes overlapping windows under one loss and one stitched file is written.  Without the flag a
+long `--wav` is cropped to the window as before.
 """
 import argparse
 import math
@@ -28,14 +33,16 @@ from diffmusic_amd.schedulers import get_scheduler                              
 TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation")
 
 
-def build_operator(task, cfg, mask_type):
-    """run.py:157-212: one operator per task, constructor arguments from the data / model config."""
+def build_operator(task, cfg, mask_type, audio_length_in_s=None):
+    """run.py:157-212: one operator per task, constructor arguments from the data / model config.  `audio_length_in_s`: the length the
+    operator acts on when it is not the model window (a track)."""
     noiser = P.get_noiser(**cfg.inverse_problem.noise)
     d, scale = cfg.data, 1
+    seconds = cfg.model.pipe.audio_length_in_s if audio_length_in_s is None else audio_length_in_s
     if task == "music_generation":
         op = P.IdentityOperator(sample_rate=d.sample_rate)
     elif task == "music_inpainting":
-        op = P.MusicInpaintingOperator(audio_length_in_s=cfg.model.pipe.audio_length_in_s, sample_rate=d.sample_rate, mask_type=mask_type,
+        op = P.MusicInpaintingOperator(audio_length_in_s=seconds, sample_rate=d.sample_rate, mask_type=mask_type,
                                        start_inpainting_s=d.start_inpainting_s - d.start_s, end_inpainting_s=d.end_inpainting_s - d.start_s,
                                        mask_percentage=0.3, interval_s=1, mask_duration_s=0.1, noiser=noiser)
     elif task == "super_resolution":
@@ -63,10 +70,12 @@ def init_from_measurement(task, measurement, length):
     return measurement
 
 
-def load_clips(paths, n, sr, length, seed, start_s=0.0):
+def load_clips(paths, n, sr, length, seed, start_s=0.0, whole=False):
     """(B, length) fp32 in [-1, 1]: wav files decoded, mixed down to mono and resampled to `sr` by the dataset loader
     (diffmusic_amd/data/dataloader.py; reference dataloader.py:47-89), cropped from `start_s` / zero-padded to `length`;
-    seeded synthetic chords fill up to `n`."""
+    seeded synthetic chords fill up to `n`.  whole=True (track mode): the first file uncropped, or 2.5 windows of chords, as (1, T)."""
+    if whole:
+        paths, n = paths[:1], 1
     from diffmusic_amd.data.dataloader import load_wav
     from diffmusic_amd.pipelines.prompt_audioldm2 import resample_to
     clips = []
@@ -75,9 +84,12 @@ def load_clips(paths, n, sr, length, seed, start_s=0.0):
         x = x.mean(dim=0, keepdim=True)
         if rate != sr:
             x = resample_to(x, rate, sr)
-        x = x[0, int(start_s * sr):][:length]
+        x = x[0, int(start_s * sr):]
+        x = x if whole else x[:length]
         clips.append(torch.nn.functional.pad(x, (0, max(0, length - x.numel()))))
     g = torch.Generator().manual_seed(seed)
+    if whole and not clips:
+        length = 5 * length // 2
     while len(clips) < n:
         f = 110.0 * 2 ** (torch.randint(0, 36, (4,), generator=g).float() / 12)
         t = torch.arange(length, dtype=torch.float32) / sr
@@ -103,6 +115,8 @@ def parse_args(argv=None):
     ap.add_argument("--show_progress", action="store_true")
     ap.add_argument("--init", default="none", choices=["none", "measurement"],
                     help="warm start: encode the measurement, noise it to an intermediate timestep and run only the last steps (--strength)")
+    ap.add_argument("--track_overlap_s", type=float, default=None,
+                    help="track mode: restore the first --wav whole as overlapping model windows under one loss, with this overlap in seconds")
     ap.add_argument("--strength", type=float, default=1.0, help="share of num_inference_steps a warm start runs (diffusers' img2img rule)")
     return ap.parse_args(argv)
 
@@ -113,27 +127,45 @@ def main(argv=None):
     if args.model != "musicldm":
         raise SystemExit("this driver feeds MusicLDM's class-embedding conditioning; AudioLDM2 needs its T5 / GPT-2 states (see bench.py --workload)")
     device = torch.device("cuda")
-    op, scale = build_operator(args.task, cfg, args.mask_type)
-    pipe = get_pipeline(cfg.model.name).from_pretrained(args.weights, seed=args.seed).to(device)
-    pipe.scheduler = get_scheduler(cfg.name)(operator=op, **cfg.model.scheduler)
     pipe_kw = dict(cfg.model.pipe)
     if args.num_inference_steps:
         pipe_kw["num_inference_steps"] = args.num_inference_steps
     sr, length = cfg.data.sample_rate, int(pipe_kw["audio_length_in_s"] * cfg.data.sample_rate)
-    gt = load_clips(args.wav, args.batch, sr, length, args.seed).to(device)
-    B = gt.shape[0]
+    sched_kw = dict(cfg.model.scheduler)
+    layout = None
+    if args.track_overlap_s is None:
+        gt = load_clips(args.wav, args.batch, sr, length, args.seed).to(device)
+        op, scale = build_operator(args.task, cfg, args.mask_type)
+        B = gt.shape[0]
+    else:
+        if args.task == "music_generation":
+            raise SystemExit("--track_overlap_s restores a recording: pick an inverse problem with -t")
+        gt = load_clips(args.wav, 1, sr, length, args.seed, whole=True).to(device)                 # (1, T), T >= one window
+        T = gt.shape[1]
+        layout = P.TrackLayout(T, length, int(round(args.track_overlap_s * sr)))
+        inner, scale = build_operator(args.task, cfg, args.mask_type, audio_length_in_s=P.seconds_for_samples(T, sr))
+        op = P.TrackOperator(inner, layout)
+        B = layout.num_windows
+        sched_kw["per_clip_norm"] = False                                          # one loss, norms over all windows
+        print(f"track mode: {T / sr:.2f} s as {B} windows of {length / sr:.2f} s, starts (s) {[round(s / sr, 2) for s in layout.starts]}")
+    pipe = get_pipeline(cfg.model.name).from_pretrained(args.weights, seed=args.seed).to(device)
+    pipe.scheduler = get_scheduler(cfg.name)(operator=op, **sched_kw)
     measurement = op.forward(gt)                                                   # run.py:290-300: degrade the ground truth once
     if args.prompt_embeds:
         pe = torch.from_numpy(np.load(args.prompt_embeds)).float()
     else:
-        pe = torch.nn.functional.normalize(torch.randn(B, 512, generator=torch.Generator().manual_seed(args.seed)), dim=-1)
+        pe = torch.nn.functional.normalize(torch.randn(1 if layout else B, 512, generator=torch.Generator().manual_seed(args.seed)), dim=-1)
+    if layout is not None and pe.shape[0] == 1:
+        pe = pe.repeat(B, 1)                                                       # one prompt for every window of the track
     gens = [torch.Generator().manual_seed(args.seed + i) for i in range(B)]
     if args.init == "measurement":
-        pipe_kw.update(init_audio=init_from_measurement(args.task, measurement, length), strength=args.strength)
+        init = init_from_measurement(args.task, measurement, gt.shape[1])
+        pipe_kw.update(init_audio=init if layout is None else layout.cut(init[:, :gt.shape[1]]), strength=args.strength)
     elif args.strength != 1.0:
         raise SystemExit("--strength needs --init measurement (a cold start runs every step)")
     audio = pipe(prompt_embeds=pe[:B], measurement=measurement, eta=cfg.scheduler.eta, ip_guidance_rate=cfg.scheduler.ip_guidance_rate,
                  generator=gens, show_progress=args.show_progress, supervised_space=args.supervised_space, **pipe_kw).audios
+    B, length = gt.shape                                                           # what is written: the clips, or the one track
     out = Path(args.output_dir, cfg.model.name, cfg.data.name, args.config_name, args.task)
     for d in ("wav_input", "wav_recon", "wav_label", "mel_recon"):
         os.makedirs(out / d, exist_ok=True)
@@ -145,7 +177,7 @@ def main(argv=None):
             scipy.io.wavfile.write(out / "wav_input" / f"{name}.wav", sr // scale, measurement[i].float().cpu().numpy())
         scipy.io.wavfile.write(out / "wav_recon" / f"{name}.wav", sr, audio[i])
         mel = to_mel.transform(torch.from_numpy(audio[i:i + 1]).to(device))[0].T      # (frames, 64)
-        pipe.save_mel_spectrogram(mel[: int(pipe_kw["audio_length_in_s"] * 100)], out / "mel_recon" / f"{name}.png")
+        pipe.save_mel_spectrogram(mel[: length * 100 // sr], out / "mel_recon" / f"{name}.png")
     ref = gt.cpu().numpy()
     print(f"wrote {B} clip(s) to {out}; LSD {LogSpectralDistance().score(ref, audio[:, :length]):.4f}  MSE {MeanSquaredError().score(ref, audio[:, :length]):.6f}")
 

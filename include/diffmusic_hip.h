@@ -28,8 +28,9 @@ extern "C" {
 #endif
 
 /* Additive changes do not bump the version: dmx_audio_guidance_{fwd,bwd}_ex and dmx_noise_add (measurement noise inside the guided
- * step), and dmx_vae_encoder_* / dmx_vae_encode_fwd / dmx_latent_init / dmx_conv2d_raw (VAE encoder, warm-started sampling) are new
- * symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * step), dmx_vae_encoder_* / dmx_vae_encode_fwd / dmx_latent_init / dmx_conv2d_raw (VAE encoder, warm-started sampling) and
+ * dmx_track_stitch_fwd / dmx_track_stitch_bwd (track mode: overlapping windows as one sample) are new symbols, and every earlier entry
+ * point keeps its signature.  A binding that meets a version-4 library without them names the missing
  * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
@@ -237,6 +238,16 @@ int dmx_mask_apply(const float* x, long long x_stride, const float* mask, float*
 /* per-clip loss[b] = ||ref_b - pred_b||_2 (torch.linalg.norm, scheduling_dps.py:211) and dpred = gscale * dloss/dpred */
 int dmx_l2_loss(const float* ref, long long ref_stride, const float* pred, float* loss, float* dpred, int batch, long long n,
                 float gscale, void* stream);
+/* Track mode (diffmusic_amd/inverse_problem/track.py; no counterpart in the reference, which restores one window): `windows` <= 64
+ * windows of L samples, window w at track sample starts_host[w] (HOST array, increasing by less than L, first 0, last T - L), taper
+ * u(i) = min(i + 0.5, L - 0.5 - i, R) / R with 0 < R <= L / 2, L <= 2^22, den[n] = sum of u over the windows that cover track sample n.
+ *   fwd  S:   track[n]   = sum_w (u(n - start[w]) / den[n]) * wav[w, n - start[w]]          wav (windows, >= L), row stride wav_stride
+ *   bwd  S^T: dwav[w, i] = (u(i) / den[start[w] + i]) * dtrack[start[w] + i] for i < L, 0 for L <= i < full; row stride dwav_stride
+ * A sample that one window covers has weight exactly 1 (copied bit for bit).  One launch each, no workspace. */
+int dmx_track_stitch_fwd(const float* wav, long long wav_stride, float* track, const int* starts_host, int windows, int L, int R, int T,
+                         void* stream);
+int dmx_track_stitch_bwd(const float* dtrack, float* dwav, long long dwav_stride, const int* starts_host, int windows, int L, int R, int T,
+                         int full, void* stream);
 /* per-clip x *= target/max|x| ; inv_scale[b] = max|x|/target  (keeps the fp16 backward sweep in range) */
 int dmx_grad_normalize(float* x, float* inv_scale, int batch, long long n, float target, void* stream);
 
