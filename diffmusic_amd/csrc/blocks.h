@@ -1,6 +1,7 @@
-// 2-D building blocks shared by the VAE decoder and the U-Net executors: GroupNorm, ResnetBlock2D,
-// attention through batched GEMMs.  Semantics follow diffusers 0.31.0 (SURVEY.md section 8c Appendix
-// B2/B3/B6); tensors are channels-last (B, P, C) fp16.
+// 2-D building blocks shared by the VAE decoder, the VAE encoder and the U-Net executors: GroupNorm, the
+// convolutions that feed one (statistics from their epilogues), ResnetBlock2D, attention through batched
+// GEMMs, the VAE's single-head mid attention.  Semantics follow diffusers 0.31.0 (SURVEY.md section 8c
+// Appendix B2/B3/B6); tensors are channels-last (B, P, C) fp16.
 //
 // Arena discipline: a block first takes its persistent (tape) buffers, then marks the arena, takes
 // temporaries and releases back to the mark.  Launches are stream-ordered, so a released temporary
@@ -29,7 +30,8 @@ inline bool gn_parts_wanted(const Ctx& cx, size_t P) {
   return on && P > 512;                   // (<= 512 pixels: the single-launch gn_small plan, which needs no partial sums)
 }
 inline float* gn_part_alloc(Ctx& cx, int B, size_t P, int Np) { return cx.arena->f32(dmx_gn_part_floats(B, (int)P, Np)); }
-// after the launch that carried EPI_GNSTATS into `buf` (`tm` = dmx_gemm_last_tile_rows() of it; dry runs record a placeholder)
+// records the launch that carried EPI_GNSTATS / EPI_GNBWD into `buf`: `tm` = the slot rows that launch reported (0 = it carried no
+// statistics: the tensor's parts become invalid); dry runs launch nothing and record a placeholder
 inline void gn_parts_push(Ctx& cx, GnParts* gp, float* buf, int tm, int P, int Np, int Creal, int qoff = 0) {
   if (!gp || gp->n < 0) return;
   if (cx.dry) tm = 32;
@@ -53,6 +55,48 @@ inline GnParts gn_parts_new(Ctx& cx, int B, size_t P, int Np) {
 }
 inline float* gn_parts_buf(const GnParts& g) { return g.n == 0 ? g.r[0].part : nullptr; }
 
+// conv_fwd_2d whose output feeds a GroupNorm: the launch also writes that GroupNorm's partial sums into out_parts (a gn_parts_new of
+// the output tensor, Np = L.Cop; Creal = its un-padded channels) and the region is recorded (n = 1), or the parts are marked invalid
+// (n = -1) when the launch could not carry them.  out_parts == nullptr or without a fresh buffer: a plain conv_fwd_2d.
+inline int conv_fwd_2d_gn(Ctx& cx, const ConvLayer& L, const act_t* in, void* out, int B, int H, int W, Epi e, GnParts* out_parts, int Creal) {
+  float* buf = out_parts ? gn_parts_buf(*out_parts) : nullptr;
+  e.gn_part = buf;
+  int rows = 0;
+  CRUN(conv_fwd_2d(L, in, out, B, H, W, e, cx.st, &rows));
+  const int Ho = (H + L.pad_h + L.pad_h_hi - L.kh) / L.stride + 1, Wo = (W + L.pad_w + L.pad_w_hi - L.kw) / L.stride + 1;
+  if (buf) gn_parts_push(cx, out_parts, buf, rows, Ho * Wo, L.Cop, Creal);
+  return DMX_OK;
+}
+
+// nearest upsampling of x (B, H, W, C) to (H2, W2) + the 3x3 convolution L -> y, with the partial sums of y in *out_parts.
+// fold (needs H2 = 2H, W2 = 2W and pack_layer_up2x): four 2x2-tap convolutions of the low-resolution tensor, one per output parity --
+// 4/9 of the multiply-adds and no upsampled tensor (Upsample2D, diffusers 0.31.0 semantics); one region per
+// parity launch, each covering H * W low-resolution positions per image.
+inline int upsample_conv_fwd_gn(Ctx& cx, const ConvLayer& L, const act_t* x, act_t* y, int B, int H, int W, int H2, int W2, int C, bool fold,
+                                GnParts* out_parts) {
+  Arena& A = *cx.arena;
+  const size_t P = (size_t)H * W, P2 = (size_t)H2 * W2;
+  GnParts up;
+  float* ubuf[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (gn_parts_wanted(cx, P2)) for (int q = 0; q < (fold ? 4 : 1); ++q) ubuf[q] = gn_part_alloc(cx, B, fold ? P : P2, L.Cop);
+  else up.n = -1;
+  const size_t mk = A.mark();
+  Epi e;
+  if (fold) {
+    int rows[4] = {0, 0, 0, 0};
+    CRUN(conv_up2x_fwd(L, x, y, B, H, W, e, cx.st, ubuf[0] ? ubuf : nullptr, rows));
+    if (ubuf[0]) for (int q = 0; q < 4; ++q) gn_parts_push(cx, &up, ubuf[q], rows[q], (int)P, L.Cop, C);
+  } else {
+    act_t* u = A.bf(B * P2 * C);
+    CRUN(dmx_upsample_nearest(x, u, B, H, W, H2, W2, C, cx.st));
+    up.r[0].part = ubuf[0];
+    CTRY(conv_fwd_2d_gn(cx, L, u, y, B, H2, W2, e, &up, C));
+  }
+  A.release(mk);
+  *out_parts = up;
+  return DMX_OK;
+}
+
 struct GnLayer {
   GroupNormLayer g;
   const float* gamma = nullptr;
@@ -71,22 +115,26 @@ struct GnLayer {
                            gn_parts_valid(parts)));
     return DMX_OK;
   }
-  // bparts: backward partial sums written by the dgrad launch that produced dy (bwd_epi below)
-  // arm the Epi of the dgrad launch that produces dy of THIS GroupNorm (input x, tape t): the launch writes the backward partial sums into
-  // a fresh buffer (EPI_GNBWD); call bwd_parts() after the launch.  Returns the buffer (nullptr: the classic statistics pass will run).
-  float* bwd_epi(Ctx& cx, Epi& e, const act_t* x, int B, size_t P, int silu, const GnTape& t) const {
-    if (!gn_parts_wanted(cx, P) || ((g.C / g.G) & 3) || (g.C & 7) || getenv("DMX_NO_GN_BWD_PARTS")) return nullptr;
-    float* buf = gn_part_alloc(cx, B, P, g.C);
-    e.gn_part = buf; e.gnb_x = x; e.gnb_scale = t.scale; e.gnb_shift = t.shift; e.gnb_silu = silu;
-    e.gnb_stats = t.stats; e.gnb_cpg = g.C / g.G;
-    return buf;
-  }
-  GnParts bwd_parts(Ctx& cx, float* buf, size_t P) const {
+  // the dgrad launch of L that produces dy (B, H, W, C) of THIS GroupNorm (input x, tape t) from dout: it also writes the backward partial
+  // sums into a fresh buffer (EPI_GNBWD).  *bparts: what bwd() below takes (n = -1: its classic statistics pass will run).
+  int conv_bwd_2d_gn(Ctx& cx, const ConvLayer& L, const act_t* dout, act_t* dy, int B, int H, int W, const act_t* x, int silu, const GnTape& t,
+                     GnParts* bparts) const {
+    const size_t P = (size_t)H * W;
     GnParts gp;
-    if (buf) gn_parts_push(cx, &gp, buf, cx.dry ? 0 : dmx_gemm_last_tile_rows(), (int)P, g.C, g.C);
-    else gp.n = -1;
-    return gp;
+    Epi e;
+    int rows = 0;
+    if (!gn_parts_wanted(cx, P) || ((g.C / g.G) & 3) || (g.C & 7) || getenv("DMX_NO_GN_BWD_PARTS")) {
+      gp.n = -1;
+    } else {
+      e.gn_part = gn_part_alloc(cx, B, P, g.C);
+      e.gnb_x = x; e.gnb_scale = t.scale; e.gnb_shift = t.shift; e.gnb_silu = silu; e.gnb_stats = t.stats; e.gnb_cpg = g.C / g.G;
+    }
+    CRUN(conv_bwd_2d(L, dout, dy, B, H, W, e, cx.st, &rows));
+    if (e.gn_part) gn_parts_push(cx, &gp, e.gn_part, rows, (int)P, g.C, g.C);
+    *bparts = gp;
+    return DMX_OK;
   }
+  // bparts: backward partial sums written by the dgrad launch that produced dy (conv_bwd_2d_gn above)
   int bwd(Ctx& cx, const act_t* x, const act_t* dy, const act_t* add, act_t* dx, int B, int P, int silu, const GnTape& t,
           const GnParts* bparts = nullptr) const {
     const size_t mk = cx.arena->mark();
@@ -127,8 +175,8 @@ struct Resnet2D {
   // x (B,H,W,Cin) -> out (B,H,W,Cout) (caller-allocated).  silu_emb (B, temb_ch) fp16, already SiLU'd.
   // tape != nullptr keeps what backward() needs (persistent arena allocations).
   // rb_pre / ldrb: this block's slice of a time-embedding projection computed for all blocks in one GEMM (U-Net)
-  // x_parts: partial sums of x from its producers (norm1 then skips its statistics pass); out_parts: the caller's GnParts for `out` with
-  // r[0].part pointing at a buffer of dmx_gn_part_floats(B, P, pad8(Cout)) floats -- conv2 fills it (n = 1) or marks it invalid (n = -1)
+  // x_parts: partial sums of x from its producers (norm1 then skips its statistics pass); out_parts: the caller's gn_parts_new(cx, B, P,
+  // pad8(Cout)) for `out` -- conv2 fills it (n = 1) or marks it invalid (n = -1)
   int fwd(Ctx& cx, const act_t* x, act_t* out, int B, int H, int W, const act_t* silu_emb, ResnetTape* tape,
           const float* rb_pre = nullptr, int ldrb = 0, const GnParts* x_parts = nullptr, GnParts* out_parts = nullptr) const {
     Arena& A = *cx.arena;
@@ -141,8 +189,7 @@ struct Resnet2D {
     act_t* n = A.bf(B * P * (Cin > Cout ? Cin : Cout));
     CTRY(norm1.fwd(cx, x, n, B, (int)P, 1, t.g1, x_parts));
     Epi e1;
-    GnParts h1p;
-    float* h1buf = gn_parts_wanted(cx, P) ? gn_part_alloc(cx, B, P, conv1.Cop) : nullptr;      // conv1 -> norm2
+    GnParts h1p = gn_parts_new(cx, B, P, conv1.Cop);      // conv1 -> norm2
     if (has_temb && rb_pre) {
       e1.flags = EPI_ROWBIAS; e1.rowbias = rb_pre; e1.ldrb = ldrb;
     } else if (has_temb) {
@@ -151,9 +198,7 @@ struct Resnet2D {
       CRUN(linear_fwd(temb, silu_emb, temb.Cip, rb, Cout, B, et, cx.st));
       e1.flags = EPI_ROWBIAS; e1.rowbias = rb;
     }
-    e1.gn_part = h1buf;
-    CRUN(conv_fwd_2d(conv1, n, t.h1, B, H, W, e1, cx.st));
-    if (h1buf) gn_parts_push(cx, &h1p, h1buf, cx.dry ? 0 : dmx_gemm_last_tile_rows(), (int)P, conv1.Cop, Cout);
+    CTRY(conv_fwd_2d_gn(cx, conv1, n, t.h1, B, H, W, e1, &h1p, Cout));
     CTRY(norm2.fwd(cx, t.h1, n, B, (int)P, 1, t.g2, &h1p));
     Epi e2; e2.flags = EPI_RESID; e2.R = x;
     if (has_shortcut) {
@@ -162,10 +207,7 @@ struct Resnet2D {
       CRUN(conv_fwd_2d(shortcut, x, sc, B, H, W, es, cx.st));
       e2.R = sc;
     }
-    float* obuf = out_parts ? gn_parts_buf(*out_parts) : nullptr;
-    e2.gn_part = obuf;
-    CRUN(conv_fwd_2d(conv2, n, out, B, H, W, e2, cx.st));
-    if (obuf) gn_parts_push(cx, out_parts, obuf, cx.dry ? 0 : dmx_gemm_last_tile_rows(), (int)P, conv2.Cop, Cout);
+    CTRY(conv_fwd_2d_gn(cx, conv2, n, out, B, H, W, e2, out_parts, Cout));
     A.release(mk);
     if (tape) *tape = t;
     return DMX_OK;
@@ -179,16 +221,11 @@ struct Resnet2D {
     act_t* b = A.bf(B * P * (Cin > Cout ? Cin : Cout));
     Epi e;
     // the dgrad launches also write the backward sums of the GroupNorm they feed (EPI_GNBWD): norm2.bwd / norm1.bwd skip their pass over x, dy
-    Epi e2;
-    float* pb2 = norm2.bwd_epi(cx, e2, t.h1, B, P, 1, t.g2);
-    CRUN(conv_bwd_2d(conv2, dout, a, B, H, W, e2, cx.st));                // d n2
-    const GnParts bp2 = norm2.bwd_parts(cx, pb2, P);
+    GnParts bp2, bp1;
+    CTRY(norm2.conv_bwd_2d_gn(cx, conv2, dout, a, B, H, W, t.h1, 1, t.g2, &bp2));   // d n2
     CTRY(norm2.bwd(cx, t.h1, a, nullptr, b, B, (int)P, 1, t.g2, &bp2));   // d h1 (in b, Cout channels)
     act_t* c = A.bf(B * P * Cin);
-    Epi e1;
-    float* pb1 = norm1.bwd_epi(cx, e1, t.x, B, P, 1, t.g1);
-    CRUN(conv_bwd_2d(conv1, b, c, B, H, W, e1, cx.st));                   // d n1
-    const GnParts bp1 = norm1.bwd_parts(cx, pb1, P);
+    CTRY(norm1.conv_bwd_2d_gn(cx, conv1, b, c, B, H, W, t.x, 1, t.g1, &bp1));       // d n1
     const act_t* add = dout;
     if (has_shortcut) {
       CRUN(conv_bwd_2d(shortcut, dout, b, B, H, W, e, cx.st));            // reuse b (Cin channels)
@@ -251,3 +288,117 @@ inline int attention_core(Ctx& cx, const act_t* q, const act_t* k, const act_t* 
   A.release(mk);
   return DMX_OK;
 }
+
+// Single-head self-attention of the AutoencoderKL mid block (diffusers Attention with a GroupNorm in front and a residual behind), forward
+// for both halves of the autoencoder and the input-gradient backward for the decoder.  The block owns its tape: the GroupNorm's, x, q, k, v
+// and -- when the forward is told to keep them -- the probabilities P and O = P V.
+struct VaeMidAttention {
+  int C = 0;
+  bool need_bwd = false;
+  GnLayer norm;
+  ConvLayer to_q, to_k, to_v, to_out;
+  GnTape t_norm;
+  const act_t* x_in = nullptr;
+  act_t *q = nullptr, *k = nullptr, *v = nullptr, *Pm = nullptr, *O = nullptr;
+
+  void build(ParamStore& ps, const std::string& pre, int C_, int G, float eps, bool need_bwd_) {
+    C = C_; need_bwd = need_bwd_;
+    norm.build(ps, pre + ".group_norm", C, G, eps);
+    to_q = make_linear(ps, pre + ".to_q", C, C, true, need_bwd);
+    to_k = make_linear(ps, pre + ".to_k", C, C, true, need_bwd);
+    to_v = make_linear(ps, pre + ".to_v", C, C, true, need_bwd);
+    to_out = make_linear(ps, pre + ".to_out.0", C, C, true, need_bwd);
+  }
+  int pack(ParamStore& ps, hipStream_t st) {
+    norm.bind(ps);
+    CTRY(pack_layer(ps, to_q, st));
+    CTRY(pack_layer(ps, to_k, st));
+    CTRY(pack_layer(ps, to_v, st));
+    CTRY(pack_layer(ps, to_out, st));
+    return DMX_OK;
+  }
+  // x (B,H,W,C) -> *out (B,H,W,C), allocated here together with *out_parts (its partial sums); x_parts: those of x.
+  // Arena order: tape (a block built without backward keeps q, k, v among the temporaries), out and its parts, mark, temporaries.
+  int fwd(Ctx& cx, const act_t* x, act_t** out, int B, int H, int W, bool keep, const GnParts* x_parts, GnParts* out_parts) {
+    Arena& A = *cx.arena;
+    const int N = H * W;
+    const size_t n = (size_t)B * N * C;
+    x_in = x;
+    t_norm = norm.alloc(cx, B);
+    if (need_bwd) { q = A.bf(n); k = A.bf(n); v = A.bf(n); }
+    Pm = keep ? A.bf((size_t)B * N * pad8(N)) : nullptr;
+    O = keep ? A.bf(n) : nullptr;        // O = P V stays on the tape: delta = rowsum(dO * O) in the backward pass
+    act_t* y = A.bf(n);
+    GnParts op = gn_parts_new(cx, B, (size_t)N, pad8(C));
+    const size_t mk = A.mark();
+    act_t* xn = A.bf(n);
+    if (!need_bwd) { q = A.bf(n); k = A.bf(n); v = A.bf(n); }
+    act_t* o = keep ? O : A.bf(n);
+    CTRY(norm.fwd(cx, x, xn, B, N, 0, t_norm, x_parts));
+    Epi e;
+    CRUN(linear_fwd(to_q, xn, C, q, C, (long long)B * N, e, cx.st));
+    CRUN(linear_fwd(to_k, xn, C, k, C, (long long)B * N, e, cx.st));
+    CRUN(linear_fwd(to_v, xn, C, v, C, (long long)B * N, e, cx.st));
+    CTRY(attention_core(cx, q, k, v, o, B, N, N, C, 1, Pm, nullptr));
+    Epi er; er.flags = EPI_RESID; er.R = x;
+    // with statistics: as a 1x1 convolution over the (H, W) image -- the same GEMM, with rows-per-image known to the statistics epilogue
+    if (gn_parts_buf(op)) CTRY(conv_fwd_2d_gn(cx, to_out, o, y, B, H, W, er, &op, C));
+    else CRUN(linear_fwd(to_out, o, C, y, C, (long long)B * N, er, cx.st));
+    A.release(mk);
+    *out = y; *out_parts = op;
+    return DMX_OK;
+  }
+  // g (B,H,W,C) = d out -> gx (caller-allocated), after a fwd with keep
+  int bwd(Ctx& cx, const act_t* g, act_t* gx, int B, int H, int W) const {
+    Arena& A = *cx.arena;
+    const int N = H * W;
+    hipStream_t st = cx.st;
+    if (N & 7) { dmx_set_error("vae attention backward needs h*w %% 8 == 0"); return DMX_ERR_SHAPE; }
+    // the softmax backward exists only as the fused epilogue of the dP GEMM on the LDS-DMA 256x256 tile (32-bit buffer offsets):
+    // say so here instead of failing inside the launch (B <= 64 keeps every supported shape below the limit)
+    if ((long long)B * N * C >= (1ll << 29)) { dmx_set_error("vae attention backward: B*h*w*C >= 2^29 elements unsupported"); return DMX_ERR_SHAPE; }
+    const float scale = 1.0f / sqrtf((float)C);
+    const size_t mk = A.mark();
+    act_t* go = A.bf((size_t)B * N * C);
+    act_t* goT = A.bf((size_t)B * N * C);
+    act_t* PT = A.bf((size_t)B * N * N);
+    float* delta = A.f32((size_t)B * N);
+    act_t* dS = A.bf((size_t)B * N * N);
+    act_t* T1 = A.bf((size_t)B * N * C);
+    act_t* gq = A.bf((size_t)B * N * C);
+    act_t* gk = A.bf((size_t)B * N * C);
+    act_t* gv = A.bf((size_t)B * N * C);
+    act_t* gxn = A.bf((size_t)B * N * C);
+    Epi e;
+    CRUN(linear_bwd(to_out, g, C, go, C, (long long)B * N, e, st));
+    GemmBatch gb; gb.Z = B; gb.Zi = 1;
+    // dS = P * (go . v^T - delta) * scale with delta = rowsum(go * O) (= rowsum(dP * P)): the softmax backward runs in the
+    // epilogue of the dP GEMM, so neither the fp32 dP (512 MB at B = 8) nor a separate softmax-backward pass exists
+    CRUN(dmx_rowdot(go, O, delta, (long long)B * N, C, C, C, st));
+    gb.sAo = (long long)N * C; gb.sBo = (long long)N * C; gb.sCo = (long long)N * N;
+    {
+      Epi es; es.flags = EPI_SOFTBWD; es.X = Pm; es.rowbias = delta; es.alpha = scale;
+      CRUN(gemm_nt(go, C, v, C, dS, N, N, N, C, es, gb, st));
+    }
+    // dv = P^T . go = gemm_nt(PT (Nk,Nq), goT (C,Nq))
+    CRUN(dmx_transpose(Pm, PT, N, N, N, N, B, 1, (long long)N * N, 0, (long long)N * N, 0, st));
+    CRUN(dmx_transpose(go, goT, N, C, C, N, B, 1, (long long)N * C, 0, (long long)N * C, 0, st));
+    gb.sAo = (long long)N * N; gb.sBo = (long long)N * C; gb.sCo = (long long)N * C;
+    CRUN(gemm_nt(PT, N, goT, N, gv, C, N, C, N, e, gb, st));
+    // dq = dS . k = gemm_nt(dS (Nq,Nk), kT (C,Nk))
+    CRUN(dmx_transpose(k, T1, N, C, C, N, B, 1, (long long)N * C, 0, (long long)N * C, 0, st));
+    CRUN(gemm_nt(dS, N, T1, N, gq, C, N, C, N, e, gb, st));
+    // dk = dS^T . q = gemm_nt(dST (Nk,Nq), qT (C,Nq))   (PT buffer reused for dS^T)
+    CRUN(dmx_transpose(dS, PT, N, N, N, N, B, 1, (long long)N * N, 0, (long long)N * N, 0, st));
+    CRUN(dmx_transpose(q, T1, N, C, C, N, B, 1, (long long)N * C, 0, (long long)N * C, 0, st));
+    CRUN(gemm_nt(PT, N, T1, N, gk, C, N, C, N, e, gb, st));
+    // d xn = gq Wq + gk Wk + gv Wv
+    Epi ea; ea.flags = EPI_ACCUM;
+    CRUN(linear_bwd(to_q, gq, C, gxn, C, (long long)B * N, e, st));
+    CRUN(linear_bwd(to_k, gk, C, gxn, C, (long long)B * N, ea, st));
+    CRUN(linear_bwd(to_v, gv, C, gxn, C, (long long)B * N, ea, st));
+    CTRY(norm.bwd(cx, x_in, gxn, g, gx, B, N, 0, t_norm));
+    A.release(mk);
+    return DMX_OK;
+  }
+};

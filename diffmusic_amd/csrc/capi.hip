@@ -167,10 +167,13 @@ int dmx_unet_fwd_ctx(dmx_model* m, const float* x, const float* t, const float* 
   return dmx_unet_fwd_impl(m->impl, x, t, class_labels, eps, batch, h, w, ws, ws_bytes, ST(stream), ctx0, n0, ctx1, n1, bias1);
 }
 
+// test hook pair: dmx_gemm_last_tile_rows_raw() returns the slot rows that this thread's most recent dmx_gemm_raw launch reported
+static thread_local int g_raw_gn_rows = 0;
 int dmx_gemm_raw(const void* desc, size_t desc_bytes, void* stream) {
   if (desc_bytes != sizeof(GemmDesc)) { dmx_set_error("GemmDesc size mismatch: %zu vs %zu", desc_bytes, sizeof(GemmDesc)); return DMX_ERR_SHAPE; }
-  return dmx_gemm_launch(*reinterpret_cast<const GemmDesc*>(desc), ST(stream));
+  return dmx_gemm_launch(*reinterpret_cast<const GemmDesc*>(desc), ST(stream), &g_raw_gn_rows);
 }
+int dmx_gemm_last_tile_rows_raw(void) { return g_raw_gn_rows; }
 
 int dmx_conv_pair_raw(const void* desc_a, const void* desc_b, size_t desc_bytes, void* stream) {
   if (desc_bytes != sizeof(GemmDesc)) { dmx_set_error("GemmDesc size mismatch: %zu vs %zu", desc_bytes, sizeof(GemmDesc)); return DMX_ERR_SHAPE; }
@@ -235,7 +238,6 @@ int dmx_groupnorm_parts_raw(const void* x, void* y, const float* gamma, const fl
   if (rc == DMX_ERR_SHAPE) dmx_set_error("groupnorm: unsupported channel / group counts");
   return rc;
 }
-int dmx_gemm_last_tile_rows_raw(void) { return dmx_gemm_last_tile_rows(); }
 // GroupNorm(+SiLU) backward: dx = d/dx of <dy, act(GN(x))> (+ add), with the two per-group sums taken from partial sums the dgrad launch
 // that produced dy wrote (EPI_GNBWD; regions as in dmx_groupnorm_parts_raw) or, with nreg == 0, by the classic pass over x and dy.
 // stats / scale / shift: the forward's tape; k0 / k1: (B, C) fp32 scratch; partial: scratch of dmx_groupnorm_scratch_floats (nreg == 0).

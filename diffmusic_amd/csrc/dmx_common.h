@@ -112,8 +112,8 @@ enum {
   EPI_ROWSTATS = 32768, // also write per-row partial sums (sum v, sum v^2 per 32-column slot, fp32) of the final values to rowstats_out
                         // [row][nslots][2]: the statistics of a LayerNorm folded into the next projection (identity row map, N % 32 == 0)
   EPI_GNSTATS = 65536,  // also write GroupNorm partial sums of the stored output to gn_part: (sum v, sum v^2) per 4-channel quad, per wave tile and
-                        // image -- [image][slot][N / 4][2] fp32 with slot = wave-tile index inside the image (rows per tile = the tile's TM,
-                        // reported by dmx_gemm_last_tile_rows()); the consumer's GroupNorm needs no statistics pass over the tensor
+                        // image -- [image][slot][N / 4][2] fp32 with slot = wave-tile index inside the image (rows per slot: what the launch
+                        // reports through dmx_gemm_launch's gn_rows); the consumer's GroupNorm needs no statistics pass over the tensor
   EPI_GNBWD = 131072,   // the output is dy of a GroupNorm(+SiLU): also write the BACKWARD partial sums (sum dxh, sum dxh x per quad, slot layout of
                         // EPI_GNSTATS) to gn_part, from gnb_x (the GroupNorm's input, row stride gnb_ldx), gnb_scale / gnb_shift ([image][N]) and gnb_stats
   EPI_BIASINIT = 262144, // internal (set by the LDS-DMA launchers in place of EPI_BIAS): the accumulators start at bias[n] instead of zero
@@ -163,15 +163,13 @@ struct GemmDesc {
   int gnb_cpg;               // EPI_GNBWD: channels per group (a multiple of 4)
 };
 
-int dmx_gemm_launch(const GemmDesc& d, hipStream_t stream);
+// gn_rows (optional): on return the rows per statistics slot of THIS launch (EPI_GNSTATS / EPI_GNBWD), 0 when it carried no statistics
+// (split-K plan, direct epilogue, a descriptor the statistics epilogue does not take, images smaller than a slot)
+int dmx_gemm_launch(const GemmDesc& d, hipStream_t stream, int* gn_rows = nullptr);
 void dmx_gemm_set_splitk_workspace(float* ws, size_t bytes);
 void dmx_gemm_release_splitk_workspace(const float* ws);
 // EPI_LNFOLD launches (gemm_ln.hip): tile configuration `cfg` as numbered in gemm_conv.hip, mapped onto the instantiated subset
 int dmx_gemm_launch_ln(int cfg, const GemmDesc& d, hipStream_t stream);
 int dmx_gemm_launch_rowstats(int cfg, const GemmDesc& d, hipStream_t stream);      // EPI_ROWSTATS producers (same file)
-int dmx_gemm_launch_gnstats(int cfg, const GemmDesc& d, hipStream_t stream);       // EPI_GNSTATS producers (gemm_gn.hip)
-// rows per wave tile (the TM of EPI_GNSTATS slots) of the most recent dmx_gemm_launch of this thread, 0 when that launch carried no
-// statistics (split-K plan, direct epilogue)
-int dmx_gemm_last_tile_rows();
-void dmx_gemm_reset_last_tile_rows();
+int dmx_gemm_launch_gnstats(int cfg, const GemmDesc& d, hipStream_t stream, int* gn_rows);       // EPI_GNSTATS producers (gemm_gn.hip)
 bool dmx_prof_is_active();

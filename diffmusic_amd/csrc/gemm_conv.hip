@@ -61,11 +61,11 @@ bool glds_ok(const GemmDesc& d) {
   return in_elems < (1ll << 29) && (long long)d.M * d.lda < (1ll << 29) && ((long long)d.N + 512) * d.ldw < (1ll << 29) &&
          (d.sy == 1 || strided_ok);
 }
-int launch_by_cfg(int cfg, const GemmDesc& d, hipStream_t stream) {
+int launch_by_cfg(int cfg, const GemmDesc& d, hipStream_t stream, int* gn_rows = nullptr) {
   g_last_cfg = cfg;
   if (d.flags & EPI_LNFOLD) return dmx_gemm_launch_ln(cfg, d, stream);       // (gemm_ln.hip: the same tiles with the LayerNorm correction ahead of the epilogue)
   if (d.flags & EPI_ROWSTATS) return dmx_gemm_launch_rowstats(cfg, d, stream);   // (... and with the row-statistics epilogue)
-  if (d.flags & (EPI_GNSTATS | EPI_GNBWD)) return dmx_gemm_launch_gnstats(cfg, d, stream);     // (gemm_gn.hip: GroupNorm partial sums of the stored tile)
+  if (d.flags & (EPI_GNSTATS | EPI_GNBWD)) return dmx_gemm_launch_gnstats(cfg, d, stream, gn_rows);     // (gemm_gn.hip: GroupNorm partial sums of the stored tile)
   switch (cfg) {
     case 1: return launch_glds<256, 256, 2, 4, 2>(d, stream);
     case 2: return launch_glds<256, 128, 4, 2, 3>(d, stream);
@@ -91,10 +91,10 @@ int launch_by_cfg(int cfg, const GemmDesc& d, hipStream_t stream) {
     default: return launch_cfg<64, 64, 2, 2>(d, stream);
   }
 }
-int launch_dispatch(const GemmDesc& d, hipStream_t stream) {
+int launch_dispatch(const GemmDesc& d, hipStream_t stream, int* gn_rows) {
   const bool gl = glds_ok(d);
-  if (d.flags & EPI_SOFTBWD) return gl ? launch_by_cfg(1, d, stream) : DMX_ERR_SHAPE;   // (its one caller checks the span up front: vae.hip)
-  if (d.tile_cfg >= 1 && d.tile_cfg <= 19 && ((d.tile_cfg > 2 && d.tile_cfg < 7) || gl)) return launch_by_cfg(d.tile_cfg, d, stream);
+  if (d.flags & EPI_SOFTBWD) return gl ? launch_by_cfg(1, d, stream, gn_rows) : DMX_ERR_SHAPE;   // (its one caller checks the span up front: vae.hip)
+  if (d.tile_cfg >= 1 && d.tile_cfg <= 19 && ((d.tile_cfg > 2 && d.tile_cfg < 7) || gl)) return launch_by_cfg(d.tile_cfg, d, stream, gn_rows);
   {  // tuning hook: DMX_CFG_OVERRIDE="N:cfg,N:cfg" forces a tile configuration for large-M launches with that N
     static int ovN[8], ovC[8], nov = -1;
     if (nov < 0) {
@@ -109,13 +109,13 @@ int launch_dispatch(const GemmDesc& d, hipStream_t stream) {
       }
     }
     if (gl && d.M >= 40000)
-      for (int i = 0; i < nov; ++i) if (ovN[i] == d.N) return launch_by_cfg(ovC[i], d, stream);
+      for (int i = 0; i < nov; ++i) if (ovN[i] == d.N) return launch_by_cfg(ovC[i], d, stream, gn_rows);
   }
   // measured best configuration for the shapes of the shipped benchmark configs (scripts/dev/tune_tiles.py)
   for (const TileEntry* e = g_tile_table; e->cfg; ++e)
     if (e->M == d.M && e->N == d.N && e->K == d.K && e->Z == d.Z) {
       const int c = e->cfg % 100;                  // (hundreds = a split-K plan, taken by splitk_plan when the launch allows it)
-      if ((c > 2 && c < 7) || gl) return launch_by_cfg(c, d, stream);
+      if ((c > 2 && c < 7) || gl) return launch_by_cfg(c, d, stream, gn_rows);
     }
   if (gl && d.M >= 2048 && d.N % 128 == 0) {
     // otherwise pick the tile that minimises (rounds over the 256 CUs) x (time per block); efficiencies measured on MI355X
@@ -140,18 +140,18 @@ int launch_dispatch(const GemmDesc& d, hipStream_t stream) {
       const double v = cost(c.bm, c.bn, c.slots, c.eff);
       if (v < bc) { bc = v; best = c.cfg; }
     }
-    if (best && best != 3) return launch_by_cfg(best, d, stream);
+    if (best && best != 3) return launch_by_cfg(best, d, stream, gn_rows);
   }
   // small problems: 64x64 tiles so that at least ~1 block per CU exists (U-Net levels with 1k-4k pixels)
   if (d.N > 32 && (long long)cdiv(d.M, 128) * cdiv(d.N, 128) * d.Z < 200) {
     // shapes the measured table does not know (other batch sizes / clip lengths): what the tuner found on ~150 of them -- the 4-stage LDS-DMA
     // 64-row tiles win from K >= 512 on (64x128 when N allows it and there are rows enough), the register-staged tile below that
-    if (gl && d.K >= 512 && d.Z == 1) return launch_by_cfg(d.N % 128 == 0 && d.M >= 4000 ? 14 : 12, d, stream);
-    return launch_by_cfg(6, d, stream);
+    if (gl && d.K >= 512 && d.Z == 1) return launch_by_cfg(d.N % 128 == 0 && d.M >= 4000 ? 14 : 12, d, stream, gn_rows);
+    return launch_by_cfg(6, d, stream, gn_rows);
   }
-  if (d.N > 64) return launch_by_cfg(3, d, stream);
-  if (d.N > 32) return launch_by_cfg(4, d, stream);
-  return launch_by_cfg(5, d, stream);
+  if (d.N > 64) return launch_by_cfg(3, d, stream, gn_rows);
+  if (d.N > 32) return launch_by_cfg(4, d, stream, gn_rows);
+  return launch_by_cfg(5, d, stream, gn_rows);
 }
 }  // namespace
 
@@ -324,7 +324,8 @@ void dmx_prof_close(int rec, hipStream_t st, double flops, double bytes, int M, 
   r.flops = flops; r.bytes = bytes; r.M = M; r.N = N; r.K = K; r.Z = 1; r.taps = taps; r.flags = flags; r.cfg = cfg;
 }
 
-int dmx_gemm_launch(const GemmDesc& d, hipStream_t stream) {
+int dmx_gemm_launch(const GemmDesc& d, hipStream_t stream, int* gn_rows) {
+  if (gn_rows) *gn_rows = 0;
   if (d.M <= 0 || d.N <= 0 || d.K <= 0) return DMX_ERR_SHAPE;
   if ((d.Ci & 7) || (d.N & 3) || (d.K & 7) || (d.lda & 7) || (d.ldw & 7) || (d.ldc & 3)) return DMX_ERR_SHAPE;
   if (d.ntaps < 1 || d.ntaps > DMX_MAX_TAPS || d.K != d.ntaps * d.Ci) return DMX_ERR_SHAPE;
@@ -352,7 +353,7 @@ int dmx_gemm_launch(const GemmDesc& d, hipStream_t stream) {
     // with a folded LayerNorm the bias (d.bias, folded: b + W beta) is added together with the LayerNorm correction ahead of the epilogue
     GemmDesc q = d;
     q.flags &= ~EPI_BIAS;
-    return dmx_gemm_launch(q, stream);
+    return dmx_gemm_launch(q, stream, gn_rows);
   }
   if (d.flags & EPI_LNFOLD) {
     // LayerNorm fold: single-tap projection over the whole normalised width, row statistics from the producer of A
@@ -367,20 +368,19 @@ int dmx_gemm_launch(const GemmDesc& d, hipStream_t stream) {
       return DMX_ERR_SHAPE;
     if (!(d.osy == 1 && d.osx == 1 && d.ooy == 0 && d.oox == 0 && d.Ho == d.Hq && d.Wo == d.Wq)) return DMX_ERR_SHAPE;
   }
-  dmx_gemm_reset_last_tile_rows();
   if (d.flags & (EPI_GNSTATS | EPI_GNBWD)) {
     // GroupNorm partial sums ride on the LDS-staged 16-bit epilogue of an unsplit launch; anything else launches WITHOUT them and reports
-    // 0 tile rows, so that the caller's GroupNorm takes its own statistics pass
+    // 0 slot rows, so that the caller's GroupNorm takes its own statistics pass
     bool can = d.gn_part && d.Z == 1 && !(d.flags & (EPI_F32OUT | EPI_NO_C | EPI_GEGLU | EPI_SOFTBWD | EPI_MASKBITS | EPI_BITS2 | EPI_LNFOLD | EPI_ROWSTATS | EPI_LRELU2)) &&
                !((d.N | d.ldc | d.ldr | d.ldx | d.ldc2) & 7) && (d.flags & (EPI_GNSTATS | EPI_GNBWD)) != (EPI_GNSTATS | EPI_GNBWD);
     if (d.flags & EPI_GNBWD) can = can && d.gnb_x && d.gnb_scale && d.gnb_shift && d.gnb_stats && !(d.gnb_ldx & 7) && d.gnb_cpg >= 4 && !(d.gnb_cpg & 3) && d.N % d.gnb_cpg == 0;
     int kt = 12;
-    if (!can || splitk_plan(d, &kt) > 1) { GemmDesc q = d; q.flags &= ~(EPI_GNSTATS | EPI_GNBWD); return dmx_gemm_launch(q, stream); }
+    if (!can || splitk_plan(d, &kt) > 1) { GemmDesc q = d; q.flags &= ~(EPI_GNSTATS | EPI_GNBWD); return dmx_gemm_launch(q, stream, gn_rows); }
   }
   int ktile = 12;
   const int ksp = splitk_plan(d, &ktile);
   if (ksp <= 1 && d.tile_cfg >= 100) return DMX_ERR_SHAPE;          // a forced split-K plan this launch cannot take (tuning hook)
-  if (!g_prof) return ksp > 1 ? launch_splitk(d, ksp, ktile, stream) : launch_dispatch(d, stream);
+  if (!g_prof) return ksp > 1 ? launch_splitk(d, ksp, ktile, stream) : launch_dispatch(d, stream, gn_rows);
   ProfRec r;
   (void)hipEventCreate(&r.a); (void)hipEventCreate(&r.b);
   r.flops = 2.0 * d.M * (double)d.N * d.K * d.Z;
@@ -398,7 +398,7 @@ int dmx_gemm_launch(const GemmDesc& d, hipStream_t stream) {
   }
   r.M = d.M; r.N = d.N; r.K = d.K; r.Z = d.Z; r.taps = d.ntaps; r.flags = d.flags;
   (void)hipEventRecord(r.a, stream);
-  const int rc = ksp > 1 ? launch_splitk(d, ksp, ktile, stream) : launch_dispatch(d, stream);
+  const int rc = ksp > 1 ? launch_splitk(d, ksp, ktile, stream) : launch_dispatch(d, stream, gn_rows);
   (void)hipEventRecord(r.b, stream);
   r.cfg = g_last_cfg;
   g_prof_recs.push_back(r);

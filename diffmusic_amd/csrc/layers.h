@@ -92,7 +92,7 @@ struct Epi {
   float* rowstats_out = nullptr;       // EPI_ROWSTATS: per-row partial sums of the output (for a LayerNorm folded into the next projection)
   const float* rowstats_in = nullptr;  // linear_fwd of a LayerNorm-folded layer: the partial sums its input's producer wrote
   int nslots = 0;                      // 32-column slots per row of either
-  float* gn_part = nullptr;            // EPI_GNSTATS: GroupNorm partial sums of the output (ask dmx_gemm_last_tile_rows() after the launch)
+  float* gn_part = nullptr;            // EPI_GNSTATS: GroupNorm partial sums of the output (the launch reports the rows per slot: gn_rows below)
   // EPI_GNBWD (with gn_part): the output is dy of a GroupNorm(+SiLU) with saved input gnb_x and tape scale / shift: backward partial sums
   const act_t* gnb_x = nullptr;
   const float* gnb_scale = nullptr;
@@ -122,16 +122,17 @@ int conv_bwd_1d(const ConvLayer& L, const act_t* dout, void* din, int B, int Ti,
 int conv_fwd_1d_desc(const ConvLayer& L, const act_t* in, void* out, int B, int Ti, const Epi& e, GemmDesc& d);
 int conv_bwd_1d_desc(const ConvLayer& L, const act_t* dout, void* din, int B, int Ti, const Epi& e, GemmDesc& d);
 int conv_pair_run(const GemmDesc& a, const GemmDesc& b, hipStream_t st);
-int conv_fwd_2d(const ConvLayer& L, const act_t* in, void* out, int B, int Hi, int Wi, const Epi& e, hipStream_t st);
+// gn_rows (optional, here and in conv_bwd_2d): rows per statistics slot of this launch, 0 = it carried none (dmx_gemm_launch)
+int conv_fwd_2d(const ConvLayer& L, const act_t* in, void* out, int B, int Hi, int Wi, const Epi& e, hipStream_t st, int* gn_rows = nullptr);
 // conv3x3(pad 1)(nearest_upsample_x2(in)) without the upsampled tensor: in (B, Hi, Wi, Cip) -> out (B, 2Hi, 2Wi, Cop), and its dgrad
 // dout (B, 2Hi, 2Wi, Cop) -> din (B, Hi, Wi, Cip) (the gradient w.r.t. the LOW-resolution input, upsample backward included)
 int pack_layer_up2x(ParamStore& ps, ConvLayer& L, hipStream_t st);
-// gn_buf / gn_tm (optional, 4 entries): GroupNorm partial-sum buffers of the four output-parity launches (EPI_GNSTATS) and, on return, the
-// slot rows each launch used (0 = that launch carried no statistics)
+// gn_buf / gn_rows (optional, 4 entries): GroupNorm partial-sum buffers of the four output-parity launches (EPI_GNSTATS) and, on return, the
+// slot rows each of them reported (0 = that launch carried no statistics)
 int conv_up2x_fwd(const ConvLayer& L, const act_t* in, void* out, int B, int Hi, int Wi, const Epi& e, hipStream_t st,
-                  float* const* gn_buf = nullptr, int* gn_tm = nullptr);
+                  float* const* gn_buf = nullptr, int* gn_rows = nullptr);
 int conv_up2x_bwd(const ConvLayer& L, const act_t* dout, void* din, int B, int Hi, int Wi, const Epi& e, hipStream_t st);
-int conv_bwd_2d(const ConvLayer& L, const act_t* dout, void* din, int B, int Hi, int Wi, const Epi& e, hipStream_t st);
+int conv_bwd_2d(const ConvLayer& L, const act_t* dout, void* din, int B, int Hi, int Wi, const Epi& e, hipStream_t st, int* gn_rows = nullptr);
 // plain (batched) NT GEMM: C[z] = alpha * A[z] (M,K; lda) * Bm[z]^T (N,K; ldb)  (+ epilogue)
 struct GemmBatch { int Z = 1, Zi = 1; long long sAo = 0, sAi = 0, sBo = 0, sBi = 0, sCo = 0, sCi = 0; };
 int gemm_nt(const act_t* A, int lda, const act_t* Bm, int ldb, void* C, int ldc, int M, int N, int K, const Epi& e,

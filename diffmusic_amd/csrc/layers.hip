@@ -416,7 +416,7 @@ int conv_pair_run(const GemmDesc& a, const GemmDesc& b, hipStream_t st) {
   return rc != DMX_OK ? rc : dmx_gemm_launch(b, st);
 }
 
-int conv_fwd_2d(const ConvLayer& L, const act_t* in, void* out, int B, int Hi, int Wi, const Epi& e, hipStream_t st) {
+int conv_fwd_2d(const ConvLayer& L, const act_t* in, void* out, int B, int Hi, int Wi, const Epi& e, hipStream_t st, int* gn_rows) {
   // the taps start pad_h / pad_w before the output's origin; the pads after the image only decide how many outputs there are (the gather
   // zero-fills whatever falls outside [0, Hi) x [0, Wi) on either side)
   const int Ho = (Hi + L.pad_h + L.pad_h_hi - L.kh) / L.stride + 1, Wo = (Wi + L.pad_w + L.pad_w_hi - L.kw) / L.stride + 1;
@@ -432,11 +432,11 @@ int conv_fwd_2d(const ConvLayer& L, const act_t* in, void* out, int B, int Hi, i
       d.tdy[ky * L.kw + kx] = (signed char)(ky - L.pad_h);
       d.tdx[ky * L.kw + kx] = (signed char)(kx - L.pad_w);
     }
-  return dmx_gemm_launch(d, st);
+  return dmx_gemm_launch(d, st, gn_rows);
 }
 
 int conv_up2x_fwd(const ConvLayer& L, const act_t* in, void* out, int B, int Hi, int Wi, const Epi& e, hipStream_t st,
-                  float* const* gn_buf, int* gn_tm) {
+                  float* const* gn_buf, int* gn_rows) {
   if (L.wup.size() != 4) { dmx_set_error("layer has no upsample-folded weights"); return DMX_ERR_STATE; }
   for (int py = 0; py < 2; ++py)
     for (int px = 0; px < 2; ++px) {
@@ -455,9 +455,8 @@ int conv_up2x_fwd(const ConvLayer& L, const act_t* in, void* out, int B, int Hi,
           d.tdy[ty * 2 + tx] = (signed char)up2x_delta(py, ty);
           d.tdx[ty * 2 + tx] = (signed char)up2x_delta(px, tx);
         }
-      const int rc = dmx_gemm_launch(d, st);
+      const int rc = dmx_gemm_launch(d, st, gn_rows ? gn_rows + py * 2 + px : nullptr);
       if (rc != DMX_OK) return rc;
-      if (gn_tm) gn_tm[py * 2 + px] = dmx_gemm_last_tile_rows();
     }
   return DMX_OK;
 }
@@ -479,7 +478,7 @@ int conv_up2x_bwd(const ConvLayer& L, const act_t* dout, void* din, int B, int H
   return dmx_gemm_launch(d, st);
 }
 
-int conv_bwd_2d(const ConvLayer& L, const act_t* dout, void* din, int B, int Hi, int Wi, const Epi& e, hipStream_t st) {
+int conv_bwd_2d(const ConvLayer& L, const act_t* dout, void* din, int B, int Hi, int Wi, const Epi& e, hipStream_t st, int* gn_rows) {
   if (!L.wb) { dmx_set_error("layer has no dgrad weights"); return DMX_ERR_STATE; }
   if (L.stride != 1) return DMX_ERR_SHAPE;
   if (L.pad_h_hi != L.pad_h || L.pad_w_hi != L.pad_w) { dmx_set_error("conv dgrad of an asymmetrically padded layer is not built"); return DMX_ERR_SHAPE; }
@@ -495,7 +494,7 @@ int conv_bwd_2d(const ConvLayer& L, const act_t* dout, void* din, int B, int Hi,
       d.tdy[ky * L.kw + kx] = (signed char)(L.pad_h - ky);
       d.tdx[ky * L.kw + kx] = (signed char)(L.pad_w - kx);
     }
-  return dmx_gemm_launch(d, st);
+  return dmx_gemm_launch(d, st, gn_rows);
 }
 
 int gemm_nt(const act_t* A, int lda, const act_t* Bm, int ldb, void* C, int ldc, int M, int N, int K, const Epi& e,

@@ -189,9 +189,7 @@ struct Transformer2D {
       A.release(mk2);
     }
     Epi eo; eo.flags = EPI_RESID; eo.R = x;
-    eo.gn_part = out_parts ? gn_parts_buf(*out_parts) : nullptr;
-    CRUN(conv_fwd_2d(proj_out, hbuf, out, B, H, W, eo, cx.st));
-    if (eo.gn_part) gn_parts_push(cx, out_parts, eo.gn_part, cx.dry ? 0 : dmx_gemm_last_tile_rows(), N, proj_out.Cop, C);
+    CTRY(conv_fwd_2d_gn(cx, proj_out, hbuf, out, B, H, W, eo, out_parts, C));
     A.release(mk);
     return DMX_OK;
   }
@@ -497,9 +495,7 @@ struct UNet : Model {
       const size_t mk = A.mark();
       act_t* x16 = A.bf((size_t)B * H * W * Cin_p);
       CRUN(dmx_nchw_f32_to_nhwc_bf16(x, x16, B, cfg.in_channels, H * W, Cin_p, 1.f, st));
-      Epi ei; ei.gn_part = gn_parts_buf(curp);
-      CRUN(conv_fwd_2d(conv_in, x16, cur, B, H, W, ei, st));
-      if (ei.gn_part) gn_parts_push(cx, &curp, ei.gn_part, dry ? 0 : dmx_gemm_last_tile_rows(), H * W, conv_in.Cop, boc[0]);
+      CTRY(conv_fwd_2d_gn(cx, conv_in, x16, cur, B, H, W, e, &curp, boc[0]));
       A.release(mk);
     }
     skips.push_back({cur, H, W, boc[0], curp});
@@ -525,9 +521,7 @@ struct UNet : Model {
         const int H2 = (H + 2 - 3) / 2 + 1, W2 = (W + 2 - 3) / 2 + 1;
         act_t* y = A.bf((size_t)B * H2 * W2 * b.ch);
         GnParts yp = gn_parts_new(cx, B, (size_t)H2 * W2, b.sampler.Cop);
-        Epi es; es.gn_part = gn_parts_buf(yp);
-        CRUN(conv_fwd_2d(b.sampler, cur, y, B, H, W, es, st));
-        if (es.gn_part) gn_parts_push(cx, &yp, es.gn_part, dry ? 0 : dmx_gemm_last_tile_rows(), H2 * W2, b.sampler.Cop, b.ch);
+        CTRY(conv_fwd_2d_gn(cx, b.sampler, cur, y, B, H, W, e, &yp, b.ch));
         cur = y; curp = yp; H = H2; W = W2;
         skips.push_back({cur, H, W, b.ch, curp});
       }
@@ -577,26 +571,9 @@ struct UNet : Model {
         const Skip nxt = skips.back();                 // upsample to the matching skip's size (forward_upsample_size)
         const int H2 = nxt.H, W2 = nxt.W;
         act_t* y = A.bf((size_t)B * H2 * W2 * b.ch);
-        const bool fold = up2x && H2 == 2 * H && W2 == 2 * W;
-        GnParts upp;
-        float* ubuf[4] = {nullptr, nullptr, nullptr, nullptr};
-        if (gn_parts_wanted(cx, (size_t)H2 * W2)) for (int q = 0; q < (fold ? 4 : 1); ++q) ubuf[q] = gn_part_alloc(cx, B, fold ? (size_t)H * W : (size_t)H2 * W2, b.sampler.Cop);
-        else upp.n = -1;
-        const size_t mk = A.mark();
-        if (fold) {
-          // exact x2 (the other levels interpolate to the skip tensor's odd size): nearest x2 + conv3x3 as four parity convolutions
-          int tms[4] = {0, 0, 0, 0};
-          CRUN(conv_up2x_fwd(b.sampler, cur, y, B, H, W, e, st, ubuf[0] ? ubuf : nullptr, tms));
-          if (ubuf[0]) for (int q = 0; q < 4; ++q) gn_parts_push(cx, &upp, ubuf[q], tms[q], H * W, b.sampler.Cop, b.ch);
-        } else {
-          act_t* u = A.bf((size_t)B * H2 * W2 * b.ch);
-          CRUN(dmx_upsample_nearest(cur, u, B, H, W, H2, W2, b.ch, st));
-          Epi eu; eu.gn_part = ubuf[0];
-          CRUN(conv_fwd_2d(b.sampler, u, y, B, H2, W2, eu, st));
-          if (ubuf[0]) gn_parts_push(cx, &upp, ubuf[0], dry ? 0 : dmx_gemm_last_tile_rows(), H2 * W2, b.sampler.Cop, b.ch);
-        }
-        A.release(mk);
-        cur = y; curp = upp; H = H2; W = W2;
+        // exact x2 folds into the convolution (the other levels interpolate to the skip tensor's odd size)
+        CTRY(upsample_conv_fwd_gn(cx, b.sampler, cur, y, B, H, W, H2, W2, b.ch, up2x && H2 == 2 * H && W2 == 2 * W, &curp));
+        cur = y; H = H2; W = W2;
       }
     }
     // ---- out

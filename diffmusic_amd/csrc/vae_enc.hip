@@ -2,8 +2,8 @@
 // other half of the autoencoder whose decoder is vae.hip.  Replaces `vae.encode(audio).latent_dist` of the vendored
 // pipeline_stable_audio.py:477 for warm-started sampling (an initial mel -> a noised start latent).  Forward only, no tape.
 //
-// Built from the decoder's blocks (blocks.h): Resnet2D, GnLayer with partial sums from the producing GEMM's epilogue, attention_core,
-// conv_fwd_2d.  New device code: the input stage (fp32 one-channel mel -> channels-last 16-bit, optional ln(max(x, floor)) on load), the
+// Built from the decoder's blocks (blocks.h): Resnet2D, GnLayer with partial sums from the producing GEMM's epilogue, VaeMidAttention,
+// conv_fwd_2d_gn.  New device code: the input stage (fp32 one-channel mel -> channels-last 16-bit, optional ln(max(x, floor)) on load), the
 // output stage (moments -> mean / clamped logvar / noised start latent) and the asymmetric padding of the downsampler's descriptor
 // (ConvLayer::pad_h_hi / pad_w_hi, layers.hip).
 #include "blocks.h"
@@ -119,8 +119,8 @@ struct VaeEncoder : Model {
   std::vector<std::vector<Resnet2D>> down_res;
   std::vector<ConvLayer> down_conv;
   Resnet2D mid0, mid1;
-  GnLayer attn_gn, norm_out;
-  ConvLayer to_q, to_k, to_v, to_out;
+  VaeMidAttention attn;
+  GnLayer norm_out;
   float* gn_partial = nullptr;
   int Cmid = 0;
 
@@ -143,12 +143,7 @@ struct VaeEncoder : Model {
       prev = ch;
     }
     mid0.build(ps, "encoder.mid_block.resnets.0", Cmid, Cmid, 0, G, eps, false);
-    const std::string ap = "encoder.mid_block.attentions.0";
-    attn_gn.build(ps, ap + ".group_norm", Cmid, G, eps);
-    to_q = make_linear(ps, ap + ".to_q", Cmid, Cmid, true, false);
-    to_k = make_linear(ps, ap + ".to_k", Cmid, Cmid, true, false);
-    to_v = make_linear(ps, ap + ".to_v", Cmid, Cmid, true, false);
-    to_out = make_linear(ps, ap + ".to_out.0", Cmid, Cmid, true, false);
+    attn.build(ps, "encoder.mid_block.attentions.0", Cmid, G, eps, false);
     mid1.build(ps, "encoder.mid_block.resnets.1", Cmid, Cmid, 0, G, eps, false);
     norm_out.build(ps, "encoder.conv_norm_out", Cmid, G, eps);
     conv_out = make_conv2d(ps, "encoder.conv_out", Cmid, 2 * c.latent_channels, 3, 1, 1, false);
@@ -164,11 +159,8 @@ struct VaeEncoder : Model {
     for (auto& l : down_conv) CTRY(pack_layer(ps, l, st));
     CTRY(mid0.pack(ps, st));
     CTRY(mid1.pack(ps, st));
-    attn_gn.bind(ps); norm_out.bind(ps);
-    CTRY(pack_layer(ps, to_q, st));
-    CTRY(pack_layer(ps, to_k, st));
-    CTRY(pack_layer(ps, to_v, st));
-    CTRY(pack_layer(ps, to_out, st));
+    norm_out.bind(ps);
+    CTRY(attn.pack(ps, st));
     return DMX_OK;
   }
 
@@ -192,11 +184,7 @@ struct VaeEncoder : Model {
     // xp: GroupNorm partial sums of x, written by the launch that produced it (as in the decoder: no statistics pass, and the canonical
     // slot order that keeps a clip's result independent of the batch around it)
     GnParts xp = gn_parts_new(cx, B, P, conv_in.Cop);
-    {
-      Epi ei; ei.gn_part = gn_parts_buf(xp);
-      CRUN(conv_fwd_2d(conv_in, in16, x, B, H, W, ei, st));
-      if (ei.gn_part) gn_parts_push(cx, &xp, ei.gn_part, dry ? 0 : dmx_gemm_last_tile_rows(), (int)P, conv_in.Cop, conv_in.Co);
-    }
+    CTRY(conv_fwd_2d_gn(cx, conv_in, in16, x, B, H, W, Epi(), &xp, conv_in.Co));
     for (int i = 0; i < nb; ++i) {
       const int ch = cfg.block_out_channels[i];
       for (int j = 0; j < cfg.layers_per_block; ++j) {
@@ -209,9 +197,7 @@ struct VaeEncoder : Model {
         const int H2 = H / 2, W2 = W / 2;
         act_t* y = A.bf((size_t)B * H2 * W2 * ch);
         GnParts yp = gn_parts_new(cx, B, (size_t)H2 * W2, down_conv[i].Cop);     // (as the U-Net's stride-2 sampler: statistics from the epilogue)
-        Epi e; e.gn_part = gn_parts_buf(yp);
-        CRUN(conv_fwd_2d(down_conv[i], x, y, B, H, W, e, st));
-        if (e.gn_part) gn_parts_push(cx, &yp, e.gn_part, dry ? 0 : dmx_gemm_last_tile_rows(), H2 * W2, down_conv[i].Cop, ch);
+        CTRY(conv_fwd_2d_gn(cx, down_conv[i], x, y, B, H, W, Epi(), &yp, ch));
         x = y; xp = yp; H = H2; W = W2; P = (size_t)H * W;
       }
     }
@@ -219,34 +205,8 @@ struct VaeEncoder : Model {
     GnParts yp = gn_parts_new(cx, B, P, pad8(Cmid));
     CTRY(mid0.fwd(cx, x, y, B, H, W, nullptr, nullptr, nullptr, 0, &xp, &yp));
     x = y; xp = yp;
-    {  // mid attention (one head of dim Cmid), as the decoder's without the tape
-      const int N = (int)P, C = Cmid;
-      const GnTape tg = attn_gn.alloc(cx, B);
-      act_t* out = A.bf((size_t)B * N * C);
-      GnParts op = gn_parts_new(cx, B, P, pad8(C));
-      const size_t mk = A.mark();
-      act_t* xn = A.bf((size_t)B * N * C);
-      act_t* q = A.bf((size_t)B * N * C);
-      act_t* k = A.bf((size_t)B * N * C);
-      act_t* v = A.bf((size_t)B * N * C);
-      act_t* o = A.bf((size_t)B * N * C);
-      CTRY(attn_gn.fwd(cx, x, xn, B, N, 0, tg, &xp));
-      Epi e;
-      CRUN(linear_fwd(to_q, xn, C, q, C, (long long)B * N, e, st));
-      CRUN(linear_fwd(to_k, xn, C, k, C, (long long)B * N, e, st));
-      CRUN(linear_fwd(to_v, xn, C, v, C, (long long)B * N, e, st));
-      CTRY(attention_core(cx, q, k, v, o, B, N, N, C, 1, nullptr, nullptr));
-      Epi er; er.flags = EPI_RESID; er.R = x;
-      er.gn_part = gn_parts_buf(op);
-      if (er.gn_part) {
-        CRUN(conv_fwd_2d(to_out, o, out, B, H, W, er, st));
-        gn_parts_push(cx, &op, er.gn_part, dry ? 0 : dmx_gemm_last_tile_rows(), (int)P, to_out.Cop, C);
-      } else {
-        CRUN(linear_fwd(to_out, o, C, out, C, (long long)B * N, er, st));
-      }
-      A.release(mk);
-      x = out; xp = op;
-    }
+    CTRY(attn.fwd(cx, x, &y, B, H, W, false, &xp, &yp));      // mid attention (one head of dim Cmid); no tape
+    x = y; xp = yp;
     y = A.bf(B * P * Cmid);
     yp = gn_parts_new(cx, B, P, pad8(Cmid));
     CTRY(mid1.fwd(cx, x, y, B, H, W, nullptr, nullptr, nullptr, 0, &xp, &yp));
