@@ -163,6 +163,68 @@ def mel_guidance_noisy(audio, wav, mask, ref, state, L, Lfull, power2, to_db, lo
     return loss, dwav
 
 
+def mel_guidance_shaped(audio, wav, mask, ref, state, L, Lfull, power2, to_db, lo, hi, gscale, noise, noise_mag, sigma, thr):
+    """mel_guidance_noisy with a hard clip between the mask and the noise: thr (B) fp32 per-clip thresholds c > 0, y = clip(wav * mask, c) +
+    sigma * noise, gradient through -c <= wav * mask <= c only.  thr None: mel_guidance_noisy, bit for bit."""
+    lib = _lib.lib()
+    B = wav.shape[0]
+    T = lib.dmx_audio_num_frames(audio, L)
+    assert ref.numel() in (T * 64, B * T * 64), (ref.shape, B, T)
+    assert noise is None or (noise.shape[0] == B and noise.shape[1] >= L and noise.stride(1) == 1), noise.shape
+    assert noise_mag is None or (noise_mag.is_contiguous() and noise_mag.numel() == B * lib.dmx_audio_num_bins(audio) * T), noise_mag.shape
+    assert thr is None or (thr.is_cuda and thr.dtype == torch.float32 and thr.is_contiguous() and thr.numel() == B), (thr.shape, B)
+    rs = 0 if (ref.numel() == T * 64 and B > 1) else T * 64
+    ns = noise.stride(0) if noise is not None else 0
+    loss = torch.empty(B, dtype=torch.float32, device=wav.device)
+    dwav = torch.empty(B, Lfull, dtype=torch.float32, device=wav.device)
+    _lib.check(lib.dmx_audio_guidance_fwd_shaped(audio, _p(wav), wav.stride(0), _p(mask), _p(ref), rs, None, _p(state), B, L, int(power2),
+                                                 int(to_db), lo, hi, _p(noise), ns, _p(noise_mag), sigma, _p(thr), _stream()),
+               "audio_guidance_fwd_shaped")
+    _lib.check(lib.dmx_audio_guidance_bwd_shaped(audio, _p(wav), wav.stride(0), _p(mask), _p(ref), rs, gscale, _p(loss), _p(dwav), Lfull, Lfull,
+                                                 _p(state), B, L, int(power2), int(to_db), lo, hi, _p(noise), ns, _p(noise_mag), sigma, _p(thr),
+                                                 _stream()), "audio_guidance_bwd_shaped")
+    return loss, dwav
+
+
+def _clip_args(name, x, thr, L):
+    if not x.is_cuda:
+        raise RuntimeError(f"{name}: tensors must be on the GPU (no CPU fallback)")
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] >= L >= 1, (name, x.shape, L)
+    assert thr.is_cuda and thr.dtype == torch.float32 and thr.is_contiguous() and thr.numel() == x.shape[0], (name, thr.shape, x.shape)
+
+
+def clip_fwd(x, thr, L):
+    """x (B, >= L) with any row stride, thr (B) -> contiguous (B, L): min(max(x, -thr[b]), thr[b]); a NaN stays NaN."""
+    _clip_args("clip_fwd", x, thr, L)
+    B = x.shape[0]
+    y = torch.empty(B, L, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_clip_fwd(_p(x), x.stride(0), _p(thr), _p(y), L, B, L, _stream()), "clip_fwd")
+    return y
+
+
+def clip_bwd(dy, wav, thr, Lfull):
+    """dy (B, L) contiguous, wav (B, >= L) with any row stride -> (B, Lfull): dy where -thr[b] <= wav <= thr[b], zero elsewhere and past L."""
+    assert dy.dtype == torch.float32 and dy.dim() == 2 and dy.is_contiguous() and Lfull >= dy.shape[1], (dy.shape, Lfull)
+    B, L = dy.shape
+    _clip_args("clip_bwd", wav, thr, L)
+    assert wav.shape[0] == B and dy.is_cuda, (wav.shape, dy.shape)
+    d = torch.empty(B, Lfull, dtype=torch.float32, device=dy.device)
+    _lib.check(_lib.lib().dmx_clip_bwd(_p(dy), L, _p(wav), wav.stride(0), _p(thr), _p(d), Lfull, B, L, Lfull, _stream()), "clip_bwd")
+    return d
+
+
+def declip_project(wav, measurement, thr, L):
+    """wav (B, >= L) restored, measurement (B, >= L) clipped at thr (B) -> contiguous (B, L): the measurement where |y| < c, else the
+    restored sample pushed to the clipped side (max(wav, c) for y >= c, min(wav, -c) for y <= -c)."""
+    _clip_args("declip_project", wav, thr, L)
+    _clip_args("declip_project", measurement, thr, L)
+    B = wav.shape[0]
+    out = torch.empty(B, L, dtype=torch.float32, device=wav.device)
+    _lib.check(_lib.lib().dmx_declip_project(_p(wav), wav.stride(0), _p(measurement), measurement.stride(0), _p(thr), _p(out), L, B, L, _stream()),
+               "declip_project")
+    return out
+
+
 def noise_add(y, noise, sigma):
     """-> y + sigma * noise (new tensor; y and noise contiguous, same number of elements)."""
     assert y.is_contiguous() and noise.is_contiguous() and y.numel() == noise.numel(), (y.shape, noise.shape)

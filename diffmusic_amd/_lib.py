@@ -142,6 +142,17 @@ _SIGS = {
     "dmx_audio_guidance_bwd_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_void_p,
                                             C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                             C.c_void_p, C.c_longlong, C.c_void_p, C.c_float, C.c_void_p]),
+    "dmx_audio_guidance_fwd_shaped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                C.c_float, C.c_void_p, C.c_void_p]),
+    "dmx_audio_guidance_bwd_shaped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_void_p,
+                                                C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                C.c_void_p, C.c_longlong, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "dmx_clip_fwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p]),
+    "dmx_clip_bwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                               C.c_void_p]),
+    "dmx_declip_project": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int,
+                                     C.c_void_p]),
     "dmx_noise_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_void_p]),
     "dmx_audio_stft_mag": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dmx_audio_stft_mag_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -164,7 +175,8 @@ _SIGS = {
 # entry points added to ABI version 4 without a version bump (include/diffmusic_hip.h): a library of that version built before them
 # loads, so their presence is checked by name
 ADDED_IN_V4 = ("dmx_vae_encoder_create", "dmx_vae_encoder_workspace_bytes", "dmx_vae_encode_fwd", "dmx_latent_init",
-               "dmx_track_stitch_fwd", "dmx_track_stitch_bwd")
+               "dmx_track_stitch_fwd", "dmx_track_stitch_bwd", "dmx_audio_guidance_fwd_shaped", "dmx_audio_guidance_bwd_shaped",
+               "dmx_clip_fwd", "dmx_clip_bwd", "dmx_declip_project")
 
 _lib = None
 
@@ -174,7 +186,7 @@ def check_symbols(h, path=LIB_PATH):
     for name in ADDED_IN_V4:
         if not hasattr(h, name):
             raise RuntimeError(f"{path} reports ABI version {ABI_VERSION} but does not export `{name}` (a build from before the VAE "
-                               "encoder / track-mode entry points): rebuild it (python -m diffmusic_amd.build --force)")
+                               "encoder / track-mode / declipping entry points): rebuild it (python -m diffmusic_amd.build --force)")
 
 
 def lib():

@@ -138,20 +138,33 @@ int dmx_audio_guidance_bwd(dmx_audio* a, const float* wav, long long wav_stride,
 int dmx_audio_guidance_fwd_ex(dmx_audio* a, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
                               float* mel_out, void* state, int batch, int L, int power2, int to_db, float lo, float hi, const float* add,
                               long long add_stride, const float* addmag, float noise_scale, void* stream) {
+  return dmx_audio_guidance_fwd_shaped(a, wav, wav_stride, mask, ref, ref_stride, mel_out, state, batch, L, power2, to_db, lo, hi, add, add_stride,
+                                       addmag, noise_scale, nullptr, stream);
+}
+int dmx_audio_guidance_fwd_shaped(dmx_audio* a, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
+                                  float* mel_out, void* state, int batch, int L, int power2, int to_db, float lo, float hi, const float* add,
+                                  long long add_stride, const float* addmag, float noise_scale, const float* thr, void* stream) {
   if (!dmx_audio_is_fused(a, L)) { dmx_set_error("fused guidance needs n_fft = 1024, 64 mel columns and a clip of >= 2048 samples"); return DMX_ERR_SHAPE; }
   if (!ref) { dmx_set_error("guidance_fwd needs the reference transform"); return DMX_ERR_SHAPE; }
   if (!noise_args_ok(add, add_stride, addmag, L, power2)) return DMX_ERR_SHAPE;
   return dmx_stft_mel_fwd(a->ft, wav, wav_stride, mask, ref, ref_stride, mel_out, fused_partials(a, state, batch, L), batch, L, a->hop,
-                          power2, to_db, lo, hi, ST(stream), add, add_stride, addmag, noise_scale);
+                          power2, to_db, lo, hi, ST(stream), add, add_stride, addmag, noise_scale, thr);
 }
 int dmx_audio_guidance_bwd_ex(dmx_audio* a, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
                               float gscale, float* loss, float* dwav, long long dwav_stride, int Lfull, void* state, int batch, int L,
                               int power2, int to_db, float lo, float hi, const float* add, long long add_stride, const float* addmag,
                               float noise_scale, void* stream) {
+  return dmx_audio_guidance_bwd_shaped(a, wav, wav_stride, mask, ref, ref_stride, gscale, loss, dwav, dwav_stride, Lfull, state, batch, L, power2,
+                                       to_db, lo, hi, add, add_stride, addmag, noise_scale, nullptr, stream);
+}
+int dmx_audio_guidance_bwd_shaped(dmx_audio* a, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
+                                  float gscale, float* loss, float* dwav, long long dwav_stride, int Lfull, void* state, int batch, int L,
+                                  int power2, int to_db, float lo, float hi, const float* add, long long add_stride, const float* addmag,
+                                  float noise_scale, const float* thr, void* stream) {
   if (!dmx_audio_is_fused(a, L)) { dmx_set_error("fused guidance needs n_fft = 1024, 64 mel columns and a clip of >= 2048 samples"); return DMX_ERR_SHAPE; }
   if (!noise_args_ok(add, add_stride, addmag, L, power2)) return DMX_ERR_SHAPE;
   return dmx_stft_mel_bwd(a->ft, wav, wav_stride, mask, ref, ref_stride, nullptr, fused_partials(a, state, batch, L), gscale, loss, dwav,
-                          dwav_stride, Lfull, 0, batch, L, a->hop, power2, to_db, lo, hi, ST(stream), add, add_stride, addmag, noise_scale);
+                          dwav_stride, Lfull, 0, batch, L, a->hop, power2, to_db, lo, hi, ST(stream), add, add_stride, addmag, noise_scale, thr);
 }
 int dmx_audio_transform_bwd(dmx_audio* a, const float* dmel, float* dwav, long long dwav_stride, void* state, int batch, int L,
                             int power2, int to_db, float lo, float hi, int accumulate, void* stream) {

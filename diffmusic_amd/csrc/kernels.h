@@ -83,13 +83,17 @@ struct DmxStftMelTables {
 int dmx_stft_mel_parts(int L, int hop);                  // workgroups per clip of the forward launch (= partial sums per clip)
 int dmx_stft_mel_fwd(const DmxStftMelTables& t, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
                      float* mel_out, float* partial, int B, int L, int hop, int power2, int to_db, float lo, float hi, hipStream_t st,
-                     const float* add = nullptr, long long add_stride = 0, const float* addmag = nullptr, float nscale = 0.f);
+                     const float* add = nullptr, long long add_stride = 0, const float* addmag = nullptr, float nscale = 0.f,
+                     const float* thr = nullptr);
 int dmx_stft_mel_bwd(const DmxStftMelTables& t, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
                      const float* dmel, const float* partial, float gscale, float* loss, float* dwav, long long dwav_stride, int Lfull,
                      int accumulate, int B, int L, int hop, int power2, int to_db, float lo, float hi, hipStream_t st,
-                     const float* add = nullptr, long long add_stride = 0, const float* addmag = nullptr, float nscale = 0.f);
+                     const float* add = nullptr, long long add_stride = 0, const float* addmag = nullptr, float nscale = 0.f,
+                     const float* thr = nullptr);
 // measurement noise: sample-domain `add` (B, >= L; row stride add_stride) enters as wav * mask + nscale * add, magnitude-domain `addmag`
-// (B, 513, frames; power2 = 0 only) as |X| + nscale * addmag, in the forward and in the backward's recomputation alike
+// (B, 513, frames; power2 = 0 only) as |X| + nscale * addmag, in the forward and in the backward's recomputation alike;
+// hard clipping: thr (B) per-clip thresholds c > 0, y = min(max(wav * mask, -c), c) + nscale * add, gradient through -c <= wav * mask <= c only
+
 
 // ---- sched.hip
 int dmx_pred_x0(const float* x, const float* eps, float* x0, long long n, float sqrt_a, float sqrt_1ma, hipStream_t st);

@@ -39,6 +39,9 @@ struct SmParams {
   const float* add; long long add_stride;      // optional (B, >= L), sample domain: y = wav * mask + nscale * add
   const float* addmag;               // optional (B, 513, T), magnitude domain (!power2 only): |X| + nscale * addmag (phase retrieval, operator.py:170-171)
   float nscale;
+  // hard clipping (the declipping operator, a nonlinear A): per-clip thresholds c[b] > 0, y = min(max(wav * mask, -c), c) before the noise;
+  // the backward passes the gradient through the samples inside [-c, c] only.  null = no clipping, the code path of every other operator
+  const float* thr;                  // optional (B)
   const float* ref; long long ref_stride;      // reference mel (B or 1, T, 64); stride 0 = one reference for every clip
   const float* dmel;                 // backward: explicit d(loss)/d(mel) (B, T, 64) instead of the L2 gradient against ref
   float* mel_out;                    // forward: (B, T, 64) or null
@@ -120,19 +123,25 @@ __device__ __forceinline__ void fft1024(float2* buf, const float2* s_tw, int lan
   fft_pass<256, INV>(buf, s_tw, lane);
 }
 
+// hard clip written with comparisons: a NaN sample fails both and stays NaN (fminf / fmaxf would return the bound)
+__device__ __forceinline__ float hard_clip(float v, float c) { return v < -c ? -c : (v > c ? c : v); }
+
 // masked (+ noisy), reflect-padded samples n = lane + 64 j of frame f of clip b -> registers (frames past the end: zeros, nothing is
 // read).  Forward and backward both load through here, so they see the same y; the noise belongs to sample s, so a padded position
-// carries the noise of the sample it mirrors (the reference pads the already noisy signal inside torch.stft).
+// carries the noise of the sample it mirrors (the reference pads the already noisy signal inside torch.stft).  The optional hard clip
+// sits between the mask and the noise (the noiser ends the operator's forward); a padded position clips its source sample.
 __device__ __forceinline__ void fetch_frame(const SmParams& P, int b, int f, float (&x)[16], int lane) {
   const float* w = P.wav + (long long)b * P.wav_stride;
   const float* z = P.add ? P.add + (long long)b * P.add_stride : nullptr;
   const int p0 = f * P.hop - PADH;
   const bool live = f < P.T;
+  const bool clip = P.thr != nullptr;                      // wave-uniform
+  const float c = clip ? P.thr[b] : 0.f;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const int s = fold_reflect(p0 + lane + 64 * j, P.L);
     float v = 0.f;
-    if (live) { v = w[s]; if (P.mask) v *= P.mask[s]; if (z) v = __fmaf_rn(P.nscale, z[s], v); }
+    if (live) { v = w[s]; if (P.mask) v *= P.mask[s]; if (clip) v = hard_clip(v, c); if (z) v = __fmaf_rn(P.nscale, z[s], v); }
     x[j] = v;
   }
 }
@@ -199,7 +208,8 @@ __global__ __launch_bounds__(256) void stft_mel_fwd_kernel(const SmParams P) {
     if (i + 1 < FWD_FPW) fetch_frame(P, b, f + 4, xs, lane);      // in flight under this frame's FFT
     fft1024<false>(buf, s_tw, lane);
     const float v = power_and_mel(P, buf, pw, lane, b, f);
-    const float o = mel_tail(P, v);
+    float o = mel_tail(P, v);
+    if (P.thr && v != v) o = v;                            // declipping: a NaN sample reaches the loss (fmaxf in the tail would drop it); wave-uniform test first
     const long long idx = ((long long)b * P.T + f) * NM + lane;
     if (P.mel_out) P.mel_out[idx] = o;
     if (P.ref) {
@@ -330,8 +340,16 @@ __global__ __launch_bounds__(256) void stft_mel_bwd_kernel(const SmParams P) {
   }
   __syncthreads();
   float* out = P.dwav + (long long)b * P.dwav_stride;
+  const float* wrow = P.wav + (long long)b * P.wav_stride;
+  const bool clip = P.thr != nullptr;                      // wave-uniform
+  const float c = clip ? P.thr[b] : 0.f;
   for (int i = tid; i < s1 - s0; i += 256) {
     float g = ((s_acc[0][i] + s_acc[1][i]) + s_acc[2][i]) + s_acc[3][i];
+    if (clip) {                                            // d clip / d y = 1 on -c <= y <= c (torch.clamp's rule), 0 outside: one coalesced re-read
+      float y = wrow[s0 + i];
+      if (P.mask) y *= P.mask[s0 + i];
+      if (!(y >= -c && y <= c)) g = 0.f;
+    }
     if (P.mask) g *= P.mask[s0 + i];
     if (P.accumulate) out[s0 + i] += g; else out[s0 + i] = g;
   }
@@ -351,14 +369,14 @@ int dmx_stft_mel_parts(int L, int hop) { return cdiv(1 + L / hop, 4 * FWD_FPW); 
 
 int dmx_stft_mel_fwd(const DmxStftMelTables& t, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
                      float* mel_out, float* partial, int B, int L, int hop, int power2, int to_db, float lo, float hi, hipStream_t st,
-                     const float* add, long long add_stride, const float* addmag, float nscale) {
+                     const float* add, long long add_stride, const float* addmag, float nscale, const float* thr) {
   if (L < NF / 2 + 1 || (addmag && power2) || (add && add_stride < L)) return DMX_ERR_SHAPE;
   SmParams P;
   memset(&P, 0, sizeof(P));
   fill_common(P, t, B, L, hop, power2, to_db, lo, hi);
   P.wav = wav; P.wav_stride = wav_stride; P.mask = mask; P.ref = ref; P.ref_stride = ref_stride; P.mel_out = mel_out;
   P.partial = ref ? partial : nullptr;
-  P.add = add; P.add_stride = add_stride; P.addmag = addmag; P.nscale = nscale;
+  P.add = add; P.add_stride = add_stride; P.addmag = addmag; P.nscale = nscale; P.thr = thr;
   hipLaunchKernelGGL(stft_mel_fwd_kernel, dim3(dmx_stft_mel_parts(L, hop), B), dim3(256), 0, st, P);
   return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
 }
@@ -366,7 +384,7 @@ int dmx_stft_mel_fwd(const DmxStftMelTables& t, const float* wav, long long wav_
 int dmx_stft_mel_bwd(const DmxStftMelTables& t, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
                      const float* dmel, const float* partial, float gscale, float* loss, float* dwav, long long dwav_stride, int Lfull,
                      int accumulate, int B, int L, int hop, int power2, int to_db, float lo, float hi, hipStream_t st,
-                     const float* add, long long add_stride, const float* addmag, float nscale) {
+                     const float* add, long long add_stride, const float* addmag, float nscale, const float* thr) {
   if (L < 2 * NF || (!dmel && (!ref || !partial)) || Lfull < L || (addmag && power2) || (add && add_stride < L)) return DMX_ERR_SHAPE;   // (left and right reflection zones must not meet)
   SmParams P;
   memset(&P, 0, sizeof(P));
@@ -374,7 +392,7 @@ int dmx_stft_mel_bwd(const DmxStftMelTables& t, const float* wav, long long wav_
   P.wav = wav; P.wav_stride = wav_stride; P.mask = mask; P.ref = ref; P.ref_stride = ref_stride; P.dmel = dmel;
   P.partial = const_cast<float*>(partial); P.nparts = dmx_stft_mel_parts(L, hop); P.gscale = gscale; P.loss = loss;
   P.dwav = dwav; P.dwav_stride = dwav_stride; P.Lfull = Lfull; P.accumulate = accumulate;
-  P.add = add; P.add_stride = add_stride; P.addmag = addmag; P.nscale = nscale;
+  P.add = add; P.add_stride = add_stride; P.addmag = addmag; P.nscale = nscale; P.thr = thr;
   int chunk = (BWD_MAX_CHUNK / hop) * hop;                 // whole hops per workgroup
   if (chunk < hop) chunk = BWD_MAX_CHUNK;                  // (hop > 2560: any chunking is correct, frames are found from sample ranges)
   P.chunk = chunk;

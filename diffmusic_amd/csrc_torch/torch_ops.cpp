@@ -23,6 +23,11 @@
 #pragma weak dmx_latent_init
 #pragma weak dmx_track_stitch_fwd
 #pragma weak dmx_track_stitch_bwd
+#pragma weak dmx_audio_guidance_fwd_shaped
+#pragma weak dmx_audio_guidance_bwd_shaped
+#pragma weak dmx_clip_fwd
+#pragma weak dmx_clip_bwd
+#pragma weak dmx_declip_project
 
 namespace {
 
@@ -208,6 +213,81 @@ std::tuple<at::Tensor, at::Tensor> mel_guidance_noisy(int64_t audio, const at::T
                                dwav.data_ptr<float>(), Lfull, (int)Lfull, state.data_ptr(), B, (int)L, power2, to_db, (float)lo, (float)hi, fp(noise), ns,
                                fp(noise_mag), (float)sigma, cur_stream()), "mel_guidance_noisy (backward)");
   return {loss, dwav};
+}
+// the same pair with a hard clip between the mask and the noise (dmx_audio_guidance_{fwd,bwd}_shaped): thr (B) per-clip thresholds; thr None
+// is mel_guidance_noisy
+inline void thr_ok(const std::optional<at::Tensor>& thr, const at::Tensor& like, int64_t B) {
+  if (!thr) return;
+  f32_cuda(*thr, "thr");
+  TORCH_CHECK(thr->numel() == B && thr->device() == like.device(), "thr must hold one threshold per clip on the waveform's device");
+}
+std::tuple<at::Tensor, at::Tensor> mel_guidance_shaped(int64_t audio, const at::Tensor& wav, const std::optional<at::Tensor>& mask, const at::Tensor& ref,
+                                                       at::Tensor state, int64_t L, int64_t Lfull, bool power2, bool to_db, double lo, double hi, double gscale,
+                                                       const std::optional<at::Tensor>& noise, const std::optional<at::Tensor>& noise_mag, double sigma,
+                                                       const std::optional<at::Tensor>& thr) {
+  dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
+  TORCH_CHECK(wav.is_cuda() && wav.scalar_type() == at::kFloat && wav.dim() == 2 && wav.stride(1) == 1 && wav.size(1) >= L, "wav must be (B, >= L) fp32 on the GPU");
+  DMX_DEVICE_OF(wav);
+  f32_cuda(ref, "ref");
+  if (mask) { f32_cuda(*mask, "mask"); TORCH_CHECK(mask->numel() >= L && mask->device() == wav.device(), "mask must hold L samples"); }
+  const int B = (int)wav.size(0), T = dmx_audio_num_frames(a, (int)L);
+  thr_ok(thr, wav, B);
+  if (noise) TORCH_CHECK(noise->is_cuda() && noise->device() == wav.device() && noise->scalar_type() == at::kFloat && noise->dim() == 2 && noise->stride(1) == 1 &&
+                         noise->size(0) == B && noise->size(1) >= L, "noise must be (B, >= L) fp32 on wav's device");
+  if (noise_mag) {
+    f32_cuda(*noise_mag, "noise_mag");
+    TORCH_CHECK(!power2 && noise_mag->device() == wav.device() && noise_mag->numel() == (int64_t)B * dmx_audio_num_bins(a) * T,
+                "noise_mag must be (B, bins, frames) and goes with power2 = False");
+  }
+  TORCH_CHECK(ref.device() == wav.device() && (ref.numel() == (int64_t)T * 64 || ref.numel() == (int64_t)B * T * 64), "ref must be (B or 1, frames, 64)");
+  TORCH_CHECK(state.is_cuda() && (size_t)state.nbytes() >= dmx_audio_state_bytes(a, B, (int)L), "state buffer too small");
+  TORCH_CHECK(Lfull >= L, "Lfull < L");
+  const long long rs = ref.numel() == (int64_t)T * 64 && B > 1 ? 0 : (long long)T * 64;
+  const long long ns = noise ? noise->stride(0) : 0;
+  at::Tensor loss = at::empty({B}, wav.options()), dwav = at::empty({B, Lfull}, wav.options());
+  ok(dmx_audio_guidance_fwd_shaped(a, wav.data_ptr<float>(), wav.stride(0), fp(mask), ref.data_ptr<float>(), rs, nullptr, state.data_ptr(), B, (int)L,
+                                   power2, to_db, (float)lo, (float)hi, fp(noise), ns, fp(noise_mag), (float)sigma, fp(thr), cur_stream()),
+     "mel_guidance_shaped (forward)");
+  ok(dmx_audio_guidance_bwd_shaped(a, wav.data_ptr<float>(), wav.stride(0), fp(mask), ref.data_ptr<float>(), rs, (float)gscale, loss.data_ptr<float>(),
+                                   dwav.data_ptr<float>(), Lfull, (int)Lfull, state.data_ptr(), B, (int)L, power2, to_db, (float)lo, (float)hi, fp(noise), ns,
+                                   fp(noise_mag), (float)sigma, fp(thr), cur_stream()), "mel_guidance_shaped (backward)");
+  return {loss, dwav};
+}
+// hard clipping on materialised waveforms (include/diffmusic_hip.h dmx_clip_fwd / dmx_clip_bwd / dmx_declip_project)
+inline void rows_ok(const at::Tensor& x, int64_t L, const char* name) {
+  TORCH_CHECK(x.is_cuda(), name, " must be a GPU tensor (the diffmusic_hip ops have no CPU fallback)");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.dim() == 2 && x.stride(1) == 1 && L >= 1 && x.size(1) >= L, name, " must be (B, >= L) fp32");
+}
+at::Tensor clip_fwd(const at::Tensor& x, const at::Tensor& thr, int64_t L) {
+  rows_ok(x, L, "x");
+  DMX_DEVICE_OF(x);
+  thr_ok(thr, x, x.size(0));
+  at::Tensor y = at::empty({x.size(0), L}, x.options());
+  ok(dmx_clip_fwd(x.data_ptr<float>(), x.stride(0), thr.data_ptr<float>(), y.data_ptr<float>(), L, (int)x.size(0), (int)L, cur_stream()), "clip_fwd");
+  return y;
+}
+at::Tensor clip_bwd(const at::Tensor& dy, const at::Tensor& wav, const at::Tensor& thr, int64_t Lfull) {
+  f32_cuda(dy, "dy");
+  TORCH_CHECK(dy.dim() == 2 && Lfull >= dy.size(1), "dy must be (B, L) with L <= Lfull");
+  const int64_t B = dy.size(0), L = dy.size(1);
+  rows_ok(wav, L, "wav");
+  TORCH_CHECK(wav.size(0) == B && wav.device() == dy.device(), "wav must hold dy's clips");
+  DMX_DEVICE_OF(dy);
+  thr_ok(thr, dy, B);
+  at::Tensor d = at::empty({B, Lfull}, dy.options());
+  ok(dmx_clip_bwd(dy.data_ptr<float>(), L, wav.data_ptr<float>(), wav.stride(0), thr.data_ptr<float>(), d.data_ptr<float>(), Lfull, (int)B, (int)L,
+                  (int)Lfull, cur_stream()), "clip_bwd");
+  return d;
+}
+at::Tensor declip_project(const at::Tensor& wav, const at::Tensor& measurement, const at::Tensor& thr, int64_t L) {
+  rows_ok(wav, L, "wav"); rows_ok(measurement, L, "measurement");
+  TORCH_CHECK(measurement.size(0) == wav.size(0) && measurement.device() == wav.device(), "measurement must hold wav's clips");
+  DMX_DEVICE_OF(wav);
+  thr_ok(thr, wav, wav.size(0));
+  at::Tensor out = at::empty({wav.size(0), L}, wav.options());
+  ok(dmx_declip_project(wav.data_ptr<float>(), wav.stride(0), measurement.data_ptr<float>(), measurement.stride(0), thr.data_ptr<float>(),
+                        out.data_ptr<float>(), L, (int)wav.size(0), (int)L, cur_stream()), "declip_project");
+  return out;
 }
 at::Tensor noise_add(const at::Tensor& y, const at::Tensor& noise, double sigma) {
   f32_cuda(y, "y"); f32_cuda(noise, "noise");
@@ -419,10 +499,15 @@ TORCH_LIBRARY(diffmusic_hip, m) {
                                                          {"dmx_vae_encode_fwd", (const void*)&dmx_vae_encode_fwd},
                                                          {"dmx_latent_init", (const void*)&dmx_latent_init},
                                                          {"dmx_track_stitch_fwd", (const void*)&dmx_track_stitch_fwd},
-                                                         {"dmx_track_stitch_bwd", (const void*)&dmx_track_stitch_bwd}};
+                                                         {"dmx_track_stitch_bwd", (const void*)&dmx_track_stitch_bwd},
+                                                         {"dmx_audio_guidance_fwd_shaped", (const void*)&dmx_audio_guidance_fwd_shaped},
+                                                         {"dmx_audio_guidance_bwd_shaped", (const void*)&dmx_audio_guidance_bwd_shaped},
+                                                         {"dmx_clip_fwd", (const void*)&dmx_clip_fwd},
+                                                         {"dmx_clip_bwd", (const void*)&dmx_clip_bwd},
+                                                         {"dmx_declip_project", (const void*)&dmx_declip_project}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
-                  "` (a build from before the VAE encoder / track-mode entry points): rebuild with `python -m diffmusic_amd.build --force`");
+                  "` (a build from before the VAE encoder / track-mode / declipping entry points): rebuild with `python -m diffmusic_amd.build --force`");
   }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
@@ -444,6 +529,11 @@ TORCH_LIBRARY(diffmusic_hip, m) {
         "float gscale) -> (Tensor, Tensor)", &mel_guidance);
   m.def("mel_guidance_noisy(int audio, Tensor wav, Tensor? mask, Tensor ref, Tensor(a!) state, int L, int Lfull, bool power2, bool to_db, float lo, "
         "float hi, float gscale, Tensor? noise, Tensor? noise_mag, float sigma) -> (Tensor, Tensor)", &mel_guidance_noisy);
+  m.def("mel_guidance_shaped(int audio, Tensor wav, Tensor? mask, Tensor ref, Tensor(a!) state, int L, int Lfull, bool power2, bool to_db, float lo, "
+        "float hi, float gscale, Tensor? noise, Tensor? noise_mag, float sigma, Tensor? thr) -> (Tensor, Tensor)", &mel_guidance_shaped);
+  m.def("clip_fwd(Tensor x, Tensor thr, int L) -> Tensor", &clip_fwd);
+  m.def("clip_bwd(Tensor dy, Tensor wav, Tensor thr, int Lfull) -> Tensor", &clip_bwd);
+  m.def("declip_project(Tensor wav, Tensor measurement, Tensor thr, int L) -> Tensor", &declip_project);
   m.def("noise_add(Tensor y, Tensor noise, float sigma) -> Tensor", &noise_add);
   m.def("track_stitch_fwd(Tensor wav, int[] starts, int L, int R, int T) -> Tensor", &track_stitch_fwd);
   m.def("track_stitch_bwd(Tensor dtrack, int[] starts, int L, int R, int Lfull) -> Tensor", &track_stitch_bwd);

@@ -86,15 +86,19 @@ class SpectralFrontend:
         return bool(L.lib().dmx_audio_is_fused(self._h, int(length)))
 
     def guidance(self, wav, length, ref, mask=None, power2=True, to_db=True, lo=_NEG, hi=_POS, gscale=1.0, noise=None, noise_mag=None,
-                 sigma=0.0):
+                 sigma=0.0, thr=None):
         """Fused guidance pair: loss[b] = ||ref[b] - transform(wav[b, :length] * mask)||_2 and dwav = gscale * dloss/dwav, (B, wav.shape[1])
         with zeros past `length` -- one forward and one backward launch, no spectrum in HBM (dmx_audio_guidance_{fwd,bwd}).
         noise (B, >= length) / noise_mag (B, bins, frames; power2 False): standard-normal draws entering as wav * mask + sigma * noise,
-        resp. |STFT| + sigma * noise_mag, inside both kernels (dmx_audio_guidance_{fwd,bwd}_ex)."""
+        resp. |STFT| + sigma * noise_mag, inside both kernels (dmx_audio_guidance_{fwd,bwd}_ex).
+        thr (B) fp32: per-clip hard-clip thresholds, y = clip(wav * mask, thr) + sigma * noise inside both kernels
+        (dmx_audio_guidance_{fwd,bwd}_shaped); None takes the calls above."""
         assert wav.dtype == torch.float32 and wav.is_cuda and wav.stride(1) == 1 and ref.dtype == torch.float32 and ref.is_contiguous()
         B, full = wav.shape
         st = self._get_state(B, length, wav.device)
         args = (self._h.value, wav, mask, ref, st, int(length), int(full), bool(power2), bool(to_db), float(lo), float(hi), float(gscale))
+        if thr is not None:
+            return ops.hip.mel_guidance_shaped(*args, noise, noise_mag, float(sigma), thr)
         if noise is None and noise_mag is None:
             return ops.hip.mel_guidance(*args)
         return ops.hip.mel_guidance_noisy(*args, noise, noise_mag, float(sigma))
@@ -343,6 +347,90 @@ class MusicInpaintingOperator(_MelOperator):              # operator.py:48-133
 
     def _a_bwd(self, dy, full):
         return ops.ctypes_hip.mask_mul(dy, self._mask_on(dy.device), dy.shape[1], full)
+
+
+class DeclippingOperator(_MelOperator):
+    """Hard clipping (extension; the reference has no nonlinear operator): A(x)[b, s] = min(max(x[b, s], -c[b]), c[b]) with one threshold
+    c[b] > 0 per clip, forward = noiser(A(x)), transform = clamp(wav2mel, -80, 80) like the IdentityOperator's.
+
+    threshold: a positive float (every clip), a sequence or a (B,) tensor (one per clip; the batch of `forward` / `guidance` must then be
+    B -- inside a TrackOperator that is the one track).  dA/dx = 1 on -c <= x <= c (torch.clamp's rule at equality), 0 outside: a restored
+    sample beyond the threshold on the right side costs nothing, and the loss pulls only through the unclipped positions.  A NaN sample
+    stays NaN.  In mel space with fused kernels the clip happens on load inside the guidance pair (csrc/stft_mel.hip); elsewhere through
+    `clip_fwd` / `clip_bwd` (csrc/waveshape.hip).  `project` is the optional output stage.
+
+    The front end and the device copy of the thresholds are made on first use, so the operator can be built without a GPU."""
+
+    def __init__(self, sample_rate, threshold, noiser=None):
+        thr = torch.as_tensor(threshold, dtype=torch.float32).detach().cpu().reshape(-1)
+        if thr.numel() < 1 or not bool(torch.isfinite(thr).all()) or not bool((thr > 0).all()):
+            raise ValueError(f"threshold = {threshold!r}: positive finite value(s), one for all clips or one per clip")
+        self.sample_rate, self.noiser = sample_rate, noiser
+        self.per_clip = torch.as_tensor(threshold).dim() > 0      # a scalar broadcasts over any batch
+        self.threshold = thr.clone()                          # host copy: (1,) broadcast over the batch, or (B,)
+        self._thr_dev = None
+        self._frontend = None
+        self._wav = None
+
+    @property
+    def frontend(self):
+        if self._frontend is None:
+            self._frontend = SpectralFrontend(self.sample_rate, 1024, 160, 64, "hann")
+        return self._frontend
+
+    def _check_batch(self, batch):
+        n = self.threshold.numel()
+        if self.per_clip and n != batch:
+            raise ValueError(f"DeclippingOperator holds {n} per-clip threshold(s), the batch has {batch} clip(s)")
+
+    def thresholds(self, batch, device):
+        """The (batch,) fp32 thresholds on `device` (one tensor, kept)."""
+        self._check_batch(batch)
+        t = self._thr_dev
+        if t is None or t.device != device or t.numel() != batch:
+            t = self._thr_dev = self.threshold.to(device).expand(batch).contiguous()
+        return t
+
+    def forward(self, data, **kwargs):
+        self._check_batch(data.shape[0])
+        data = _as_f32_cuda(data)
+        y = ops.hip.clip_fwd(data, self.thresholds(data.shape[0], data.device), data.shape[1])
+        return self.noiser(y) if self.noiser is not None else y
+
+    def _a_fwd(self, wav, length):
+        self._wav = wav                                       # the Jacobian of a nonlinear A needs the point it is taken at
+        return ops.hip.clip_fwd(wav, self.thresholds(wav.shape[0], wav.device), int(length))
+
+    def _a_bwd(self, dy, full):
+        wav, self._wav = self._wav, None
+        return ops.hip.clip_bwd(dy.contiguous(), wav, self.thresholds(wav.shape[0], wav.device), int(full))
+
+    def guidance(self, wav, length, measurement, supervised_space, noise=None, step=None, generator=None):
+        self._check_batch(wav.shape[0])
+        if supervised_space == "mel_spectrogram" and self.frontend.fused(length):
+            # clip, noise, STFT, mel, dB, L2 and the whole backward in two launches; A(wav) is never materialised
+            lo, hi = self.clamp
+            ref = self._ref(measurement, "mel_spectrogram", lambda m: self._mel(m.reshape(m.shape[0], -1)).clone())
+            z, sigma = self._step_noise((wav.shape[0], length), wav.device, noise, step, generator)
+            return self.frontend.guidance(wav, length, ref, None, True, True, lo, hi, noise=z, sigma=sigma,
+                                          thr=self.thresholds(wav.shape[0], wav.device))
+        return super().guidance(wav, length, measurement, supervised_space, noise=noise, step=step, generator=generator)
+
+    def project(self, wav, measurement):
+        """The conventional output stage of declipping -> (B, L), L the measurement's length: reliable samples (|y| < c) are the
+        measurement's, clipped ones are the restored sample pushed to the clipped side (max(x, c) for y >= c, min(x, -c) for y <= -c).
+        Opt-in; refused with measurement noise, under which no sample of y is reliable."""
+        if step_sigma(self.noiser) > 0:
+            raise ValueError("project: the measurement carries additive noise (sigma > 0), so none of its samples is reliable")
+        y = _as_f32_cuda(measurement)
+        y = y.reshape(y.shape[0], -1)
+        wav = _as_f32_cuda(torch.as_tensor(wav).to(y.device))
+        wav = wav.reshape(wav.shape[0], -1)
+        if wav.shape[0] != y.shape[0] or wav.shape[1] < y.shape[1]:
+            raise ValueError(f"project: restored audio {tuple(wav.shape)} does not cover the measurement {tuple(y.shape)}")
+        if wav.stride(1) != 1:
+            wav = wav.contiguous()
+        return ops.hip.declip_project(wav, y.contiguous(), self.thresholds(y.shape[0], y.device), y.shape[1])
 
 
 class PhaseRetrievalOperator(BaseOperator):               # operator.py:136-171

@@ -8,6 +8,7 @@ embedding file (`--prompt_embeds x.npy`, (B, 512) CLAP text embeddings for Music
     python examples/run_inverse_problem.py -c dps -t music_inpainting --wav a.wav b.wav --weights /ckpt/musicldm
     python examples/run_inverse_problem.py -c mpgd -t super_resolution --num_inference_steps 20      # synthetic clips + weights
     python examples/run_inverse_problem.py -c dps -t music_dereverberation --wav take.wav --track_overlap_s 1.28   # a long take, whole
+    python examples/run_inverse_problem.py -c dps -t music_declipping --clip_sdr_db 3 --init measurement --strength 0.5 --project
 
 `--track_overlap_s S` restores a recording longer than the model window whole (track mode, inverse_problem/track.py): the first `--wav`
 (or a synthetic 2.5-window signal) becomes overlapping windows under one loss and one stitched file is written.  Without the flag a
@@ -30,12 +31,13 @@ from diffmusic_amd.metrics import LogSpectralDistance, MeanSquaredError         
 from diffmusic_amd.pipelines import get_pipeline                                    # noqa: E402
 from diffmusic_amd.schedulers import get_scheduler                                  # noqa: E402
 
-TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation")
+TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation", "music_declipping")
 
 
-def build_operator(task, cfg, mask_type, audio_length_in_s=None):
+def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None):
     """run.py:157-212: one operator per task, constructor arguments from the data / model config.  `audio_length_in_s`: the length the
-    operator acts on when it is not the model window (a track)."""
+    operator acts on when it is not the model window (a track).  `clip_threshold`: music_declipping's threshold(s), a float or one value
+    per clip (`threshold_for_sdr` of the clean clips)."""
     noiser = P.get_noiser(**cfg.inverse_problem.noise)
     d, scale = cfg.data, 1
     seconds = cfg.model.pipe.audio_length_in_s if audio_length_in_s is None else audio_length_in_s
@@ -52,6 +54,10 @@ def build_operator(task, cfg, mask_type, audio_length_in_s=None):
         op = P.PhaseRetrievalOperator(n_fft=d.n_fft, hop_length=d.hop_length, win_length=d.win_length, noiser=noiser)
     elif task == "music_dereverberation":
         op = P.MusicDereverberationOperator(ir_length=5000, decay_factor=0.99, noiser=noiser)
+    elif task == "music_declipping":
+        if clip_threshold is None:
+            raise ValueError("music_declipping needs clip_threshold (e.g. inverse_problem.threshold_for_sdr(clean, sdr_db))")
+        op = P.DeclippingOperator(sample_rate=d.sample_rate, threshold=clip_threshold, noiser=noiser)
     else:
         raise ValueError(f"Unknown task: {task}")
     return op, scale
@@ -117,13 +123,22 @@ def parse_args(argv=None):
                     help="warm start: encode the measurement, noise it to an intermediate timestep and run only the last steps (--strength)")
     ap.add_argument("--track_overlap_s", type=float, default=None,
                     help="track mode: restore the first --wav whole as overlapping model windows under one loss, with this overlap in seconds")
+    ap.add_argument("--clip_sdr_db", type=float, default=3.0,
+                    help="music_declipping: input SDR in dB of the clipped measurement (each clip's threshold is found from it)")
+    ap.add_argument("--project", action="store_true",
+                    help="music_declipping: finish with the consistency projection (measurement kept where it is unclipped)")
     ap.add_argument("--strength", type=float, default=1.0, help="share of num_inference_steps a warm start runs (diffusers' img2img rule)")
     return ap.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_args(argv)
-    cfg = compose(args.config_name, overrides=[f"data={args.data}", f"model={args.model}"])
+    overrides = [f"data={args.data}", f"model={args.model}"]
+    if args.task == "music_declipping":
+        overrides.append("inverse_problem=music_declipping")
+    elif args.project:
+        raise SystemExit("--project is the output stage of -t music_declipping")
+    cfg = compose(args.config_name, overrides=overrides)
     if args.model != "musicldm":
         raise SystemExit("this driver feeds MusicLDM's class-embedding conditioning; AudioLDM2 needs its T5 / GPT-2 states (see bench.py --workload)")
     device = torch.device("cuda")
@@ -135,7 +150,8 @@ def main(argv=None):
     layout = None
     if args.track_overlap_s is None:
         gt = load_clips(args.wav, args.batch, sr, length, args.seed).to(device)
-        op, scale = build_operator(args.task, cfg, args.mask_type)
+        thr = P.threshold_for_sdr(gt, args.clip_sdr_db) if args.task == "music_declipping" else None
+        op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr)
         B = gt.shape[0]
     else:
         if args.task == "music_generation":
@@ -143,7 +159,8 @@ def main(argv=None):
         gt = load_clips(args.wav, 1, sr, length, args.seed, whole=True).to(device)                 # (1, T), T >= one window
         T = gt.shape[1]
         layout = P.TrackLayout(T, length, int(round(args.track_overlap_s * sr)))
-        inner, scale = build_operator(args.task, cfg, args.mask_type, audio_length_in_s=P.seconds_for_samples(T, sr))
+        thr = float(P.threshold_for_sdr(gt, args.clip_sdr_db)[0]) if args.task == "music_declipping" else None
+        inner, scale = build_operator(args.task, cfg, args.mask_type, audio_length_in_s=P.seconds_for_samples(T, sr), clip_threshold=thr)
         op = P.TrackOperator(inner, layout)
         B = layout.num_windows
         sched_kw["per_clip_norm"] = False                                          # one loss, norms over all windows
@@ -166,6 +183,8 @@ def main(argv=None):
     audio = pipe(prompt_embeds=pe[:B], measurement=measurement, eta=cfg.scheduler.eta, ip_guidance_rate=cfg.scheduler.ip_guidance_rate,
                  generator=gens, show_progress=args.show_progress, supervised_space=args.supervised_space, **pipe_kw).audios
     B, length = gt.shape                                                           # what is written: the clips, or the one track
+    if args.project:                                                               # reliable samples kept, clipped ones made consistent
+        audio = (op.inner if layout is not None else op).project(torch.from_numpy(audio[:, :length]), measurement).cpu().numpy()
     out = Path(args.output_dir, cfg.model.name, cfg.data.name, args.config_name, args.task)
     for d in ("wav_input", "wav_recon", "wav_label", "mel_recon"):
         os.makedirs(out / d, exist_ok=True)

@@ -28,9 +28,10 @@ extern "C" {
 #endif
 
 /* Additive changes do not bump the version: dmx_audio_guidance_{fwd,bwd}_ex and dmx_noise_add (measurement noise inside the guided
- * step), dmx_vae_encoder_* / dmx_vae_encode_fwd / dmx_latent_init / dmx_conv2d_raw (VAE encoder, warm-started sampling) and
- * dmx_track_stitch_fwd / dmx_track_stitch_bwd (track mode: overlapping windows as one sample) are new symbols, and every earlier entry
- * point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * step), dmx_vae_encoder_* / dmx_vae_encode_fwd / dmx_latent_init / dmx_conv2d_raw (VAE encoder, warm-started sampling),
+ * dmx_track_stitch_fwd / dmx_track_stitch_bwd (track mode: overlapping windows as one sample) and dmx_audio_guidance_{fwd,bwd}_shaped /
+ * dmx_clip_fwd / dmx_clip_bwd / dmx_declip_project (declipping: a hard clip inside and beside the guidance pair) are new symbols, and every
+ * earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
  * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
@@ -221,6 +222,29 @@ int dmx_audio_guidance_bwd_ex(dmx_audio* a, const float* wav, long long wav_stri
                               float gscale, float* loss, float* dwav, long long dwav_stride, int Lfull, void* state, int batch, int L,
                               int power2, int to_db, float lo, float hi, const float* add, long long add_stride, const float* addmag,
                               float noise_scale, void* stream);
+/* The same pair with a hard clip between the mask and the noise (the declipping operator; no counterpart in the reference):
+ *   thr (batch) fp32, per-clip thresholds c[b] > 0:   y = min(max(wav * mask, -c), c) + noise_scale * add
+ * and dwav passes the gradient through the samples with -c <= wav * mask <= c only (inclusive, torch.clamp's rule).  A NaN sample stays
+ * NaN.  thr NULL = dmx_audio_guidance_{fwd,bwd}_ex, which are these calls with NULL.  _bwd_shaped must be given the pointers _fwd_shaped
+ * saw.  Like the other two pairs: DMX_ERR_SHAPE for handles / lengths the fused kernels do not cover. */
+int dmx_audio_guidance_fwd_shaped(dmx_audio* a, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
+                                  float* mel_out, void* state, int batch, int L, int power2, int to_db, float lo, float hi, const float* add,
+                                  long long add_stride, const float* addmag, float noise_scale, const float* thr, void* stream);
+int dmx_audio_guidance_bwd_shaped(dmx_audio* a, const float* wav, long long wav_stride, const float* mask, const float* ref, long long ref_stride,
+                                  float gscale, float* loss, float* dwav, long long dwav_stride, int Lfull, void* state, int batch, int L,
+                                  int power2, int to_db, float lo, float hi, const float* add, long long add_stride, const float* addmag,
+                                  float noise_scale, const float* thr, void* stream);
+/* Hard clipping on materialised waveforms (csrc/waveshape.hip), thr (batch) per-clip thresholds c[b] > 0, every row stride >= its length:
+ *   clip_fwd        y[b, i]    = min(max(x[b, i], -c), c), i < L                          x (batch, >= L) -> y (batch, L)
+ *   clip_bwd        dwav[b, i] = dy[b, i] where -c <= wav[b, i] <= c, else 0, i < L; 0 for L <= i < Lfull
+ *   declip_project  out[b, i]  = meas where |meas| < c; max(xhat, c) where meas >= c; min(xhat, -c) where meas <= -c   (the output stage
+ *                   of declipping: reliable samples kept, clipped samples made consistent with the measurement)
+ * One launch each, no workspace; NaN samples stay NaN. */
+int dmx_clip_fwd(const float* x, long long x_stride, const float* thr, float* y, long long y_stride, int batch, int L, void* stream);
+int dmx_clip_bwd(const float* dy, long long dy_stride, const float* wav, long long wav_stride, const float* thr, float* dwav,
+                 long long dwav_stride, int batch, int L, int Lfull, void* stream);
+int dmx_declip_project(const float* xhat, long long xhat_stride, const float* meas, long long meas_stride, const float* thr, float* out,
+                       long long out_stride, int batch, int L, void* stream);
 /* out[i] = y[i] + scale * z[i], i < n (the noiser on a materialised measurement A(x): super-resolution, dereverberation, wav_form) */
 int dmx_noise_add(const float* y, const float* z, float* out, long long n, float scale, void* stream);
 /* PhaseRetrievalOperator.forward: |torch.stft(wav)| as (B, n_fft/2+1, frames) fp32 */

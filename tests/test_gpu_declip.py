@@ -1,0 +1,529 @@
+"""-m gpu: declipping -- the hard-clip operator A(x) = min(max(x, -c[b]), c[b]) inside the fused STFT -> mel guidance kernels
+(csrc/stft_mel.hip), the elementwise kernels beside it (csrc/waveshape.hip) and the DeclippingOperator through schedulers and pipeline.
+
+The reference has no declipping operator, so the oracle side is test-local: `OracleDeclip` below subclasses the oracle's BaseOperator
+with forward = noiser(torch.clamp(x, -c, c)) and transform = clamp(Wav2Mel, -80, 80); the oracle schedulers take it as it is.
+
+Covered: the fused pair against float64 torch autograd on the same fp32 waveform (shape cases and bounds of
+tests/test_gpu_noise.py::test_fused_guidance_with_additive_input_matches_float64_torch), the no-threshold path bit for bit, fused =
+composed, NaN, the three elementwise kernels against torch bit for bit, teacher-forced steps against the oracle loop (bounds of
+tests/test_gpu_step.py), the pipeline against hand-written loops (cold, warm-started, track mode, both bindings) and clips shorter than
+the fused kernels cover."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+from tests.test_gpu_stft_mel import CASES as STFT_CASES, _clips                     # noqa: E402
+from tests.test_gpu_step import HIFI, VAE, SCHED, H, W, LEN                        # noqa: E402
+
+_NEG, _POS = -3.0e38, 3.0e38
+QUANTILES = (0.5, 0.8, 0.5)                                 # per-clip thresholds: these quantiles of |wav|
+
+
+def _rel(a, b):
+    return float((a.double().cpu() - b.double().cpu()).norm() / b.double().cpu().norm().clamp_min(1e-300))
+
+
+def _thresholds(wav, L, q=QUANTILES):
+    a = wav[:, :L].abs().double().cpu()
+    return torch.stack([torch.quantile(a[b], q[b % len(q)]) for b in range(a.shape[0])]).float().cuda()
+
+
+def _fb():
+    from diffmusic_amd.inverse_problem import dsp
+    return torch.from_numpy(dsp.melscale_fbanks(513, 0.0, 8000.0, 64, 16000)).cuda()
+
+
+# ---- 1: the fused pair against float64 torch ----------------------------------------------------------------------------------------
+def _truth(wav, thr, mask, fb, ref, L, hop, hann, power2, to_db, lo, hi, add=None):
+    """clamp -> stft -> mel -> dB -> clamp -> L2 in float64 with torch.autograd: (loss (B), dwav (B, full), clipped (B, L) bool)."""
+    w = wav.double().clone().requires_grad_(True)
+    c = thr.double()[:, None]
+    pre = w[:, :L] * (mask.double() if mask is not None else 1.0)
+    y = torch.clamp(pre, -c, c)
+    if add is not None:
+        y = y + add.double()[:, :L]
+    win = torch.hann_window(1024, periodic=True, dtype=torch.float64, device=wav.device) if hann else torch.ones(1024, dtype=torch.float64, device=wav.device)
+    spec = torch.stft(y, 1024, hop, 1024, window=win, center=True, pad_mode="reflect", normalized=False, onesided=True, return_complex=True)
+    p = spec.real ** 2 + spec.imag ** 2
+    if not power2:
+        p = torch.sqrt(p)
+    mel_lin = torch.einsum("bkt,km->btm", p, fb.double())
+    mel = 10.0 * torch.log10(torch.clamp(mel_lin, min=1e-10)) if to_db else mel_lin
+    mel = torch.clamp(mel, lo, hi)
+    loss = torch.linalg.vector_norm((ref.double() - mel).flatten(1), dim=1)
+    (g,) = torch.autograd.grad(loss.sum(), w)
+    return loss.detach(), g, (pre.detach().abs() > c)
+
+
+def _kernel_problem(case):
+    from diffmusic_amd.inverse_problem.operator import SpectralFrontend
+    name, L, full, hop, hann, power2, to_db, lo, hi, masked, shared = case
+    B = 3
+    fe = SpectralFrontend(16000, 1024, hop, 64, "hann" if hann else "rect")
+    assert fe.fused(L)
+    wav = _clips(B, full, 1)
+    mask = None
+    if masked:
+        mask = torch.ones(L)
+        mask[L // 5: L // 5 + L // 10] = 0.0
+        mask[:300] = 0.0
+        mask = mask.cuda()
+    target = _clips(1 if shared else B, L, 2)
+    ref = fe.transform_fwd(target, L, power2, to_db, lo, hi).clone()
+    g = torch.Generator().manual_seed(11)
+    z = torch.randn(B, full if name == "ragged_length" else L, generator=g).cuda()     # `ragged_length`: a (B, full) tensor, row stride != L
+    return fe, wav, mask, ref, z, B
+
+
+@pytest.mark.parametrize("noisy", [False, True], ids=["quiet", "noisy"])
+@pytest.mark.parametrize("case", STFT_CASES, ids=[c[0] for c in STFT_CASES])
+def test_fused_clipped_guidance_matches_float64_torch(case, noisy):
+    """Bounds of test_fused_guidance_with_additive_input_matches_float64_torch (the same kernels; the clamp is exact in fp32): loss < 2e-5,
+    gradient < 2e-4, first / last 600 samples < 5e-4.  The cases hold a length that is no multiple of the hop, a row stride > L and
+    L < Lfull (`ragged_length`).  Between 2 % and 98 % of each clip's samples are clipped, and their gradient is exactly 0.0."""
+    name, L, full, hop, hann, power2, to_db, lo, hi, masked, shared = case
+    fe, wav, mask, ref, z, B = _kernel_problem(case)
+    thr = _thresholds(wav, L)
+    sigma = 0.05 if noisy else 0.0
+    add = sigma * z.double() if noisy else None
+    loss_t, g_t, clipped = _truth(wav, thr, mask, _fb(), ref, L, hop, hann, power2, to_db, max(lo, -1e300), min(hi, 1e300), add)
+    share = clipped.double().mean(dim=1)
+    print(f"\n  {name}: clipped share per clip {[round(float(s), 3) for s in share]}")
+    assert bool(((share > 0.02) & (share < 0.98)).all()), share
+    loss_0, _, _ = _truth(wav, torch.full_like(thr, 3e38), mask, _fb(), ref, L, hop, hann, power2, to_db, max(lo, -1e300), min(hi, 1e300), add)
+    # the clip matters in this case: on the float64 reference alone, every clip's loss with and without the clip differ by at least ten
+    # times the loss bound below, so a product that ignored the threshold could not meet that bound
+    assert float(((loss_t - loss_0).abs() / loss_0).min()) > 10 * 2e-5, (name, loss_t, loss_0)
+    kw = dict(noise=z, sigma=sigma) if noisy else {}
+    loss, dwav = fe.guidance(wav, L, ref, mask, power2, to_db, lo, hi, thr=thr, **kw)
+    assert loss.shape == (B,) and dwav.shape == (B, full)
+    rl = float(((loss.double() - loss_t).abs() / loss_t).max())
+    rg, r0, r1 = _rel(dwav[:, :L], g_t[:, :L]), _rel(dwav[:, :600], g_t[:, :600]), _rel(dwav[:, L - 600:L], g_t[:, L - 600:L])
+    print(f"  {name}: loss {rl:.2e} grad {rg:.2e} first600 {r0:.2e} last600 {r1:.2e}")
+    assert rl < 2e-5, (name, loss, loss_t)
+    assert rg < 2e-4, (name, rg)
+    assert r0 < 5e-4 and r1 < 5e-4, (name, r0, r1)
+    assert float(dwav[:, :L][clipped].abs().max()) == 0.0                              # no gradient through a clipped sample
+    assert float(g_t[:, :L][clipped].abs().max()) == 0.0
+    assert float(dwav[:, :L][~clipped].abs().max()) > 0.0
+    if full > L:
+        assert float(dwav[:, L:].abs().max()) == 0.0
+    if mask is not None:
+        assert float(dwav[:, :L][:, mask == 0].abs().max()) == 0.0
+    loss2, dwav2 = fe.guidance(wav, L, ref, mask, power2, to_db, lo, hi, thr=thr, **kw)
+    assert torch.equal(loss, loss2) and torch.equal(dwav, dwav2)
+
+
+# ---- 2: no-op cases, bit for bit ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", STFT_CASES, ids=[c[0] for c in STFT_CASES])
+def test_no_threshold_and_a_huge_threshold_are_bitwise_noops(case):
+    from diffmusic_amd import ops
+    name, L, full, hop, hann, power2, to_db, lo, hi, masked, shared = case
+    fe, wav, mask, ref, z, B = _kernel_problem(case)
+    st = fe._get_state(B, L, wav.device)
+    args = (fe._h.value, wav, mask, ref, st, L, full, power2, to_db, float(lo), float(hi), 1.0)
+    huge = torch.full((B,), 3e38, device="cuda")
+    for binding in (ops.load(), ops.ctypes_hip):
+        loss0, d0 = binding.mel_guidance(*args)
+        loss1, d1 = binding.mel_guidance_shaped(*args, None, None, 0.0, None)
+        assert torch.equal(loss0, loss1) and torch.equal(d0, d1), name
+        loss2, d2 = binding.mel_guidance_shaped(*args, None, None, 0.0, huge)
+        assert torch.equal(loss0, loss2) and torch.equal(d0, d2), name
+        lossn, dn = binding.mel_guidance_noisy(*args, z, None, 0.05)
+        loss3, d3 = binding.mel_guidance_shaped(*args, z, None, 0.05, None)
+        assert torch.equal(lossn, loss3) and torch.equal(dn, d3), name
+        loss4, d4 = binding.mel_guidance_shaped(*args, z, None, 0.05, huge)
+        assert torch.equal(lossn, loss4) and torch.equal(dn, d4), name
+        assert not torch.equal(loss0, lossn)
+    a, b = fe.guidance(wav, L, ref, mask, power2, to_db, lo, hi), fe.guidance(wav, L, ref, mask, power2, to_db, lo, hi, thr=huge)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+# ---- 3: fused = composed ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", [c for c in STFT_CASES if c[5] and not c[9]], ids=[c[0] for c in STFT_CASES if c[5] and not c[9]])
+def test_fused_equals_composed(case):
+    """clip_fwd -> mel_guidance -> clip_bwd against the one fused call: at sigma = 0 both sides do the same arithmetic on the same values
+    (bit for bit); with sigma > 0 the fused side adds the noise by FMA on load and the composed side by a separate noise_add: the bounds
+    of test_operators_with_noise_match_their_composed_path (1e-5 / 1e-5)."""
+    from diffmusic_amd import ops
+    name, L, full, hop, hann, power2, to_db, lo, hi, masked, shared = case
+    fe, wav, mask, ref, z, B = _kernel_problem(case)
+    thr = _thresholds(wav, L)
+    loss, dwav = fe.guidance(wav, L, ref, None, power2, to_db, lo, hi, thr=thr)
+    y = ops.hip.clip_fwd(wav, thr, L)
+    assert y.shape == (B, L) and y.is_contiguous()
+    loss_c, dy = fe.guidance(y, L, ref, None, power2, to_db, lo, hi)
+    d_c = ops.hip.clip_bwd(dy, wav, thr, full)
+    assert torch.equal(loss, loss_c) and torch.equal(dwav, d_c), name
+    sigma = 0.05
+    loss_n, dwav_n = fe.guidance(wav, L, ref, None, power2, to_db, lo, hi, noise=z, sigma=sigma, thr=thr)
+    yn = ops.hip.noise_add(y, z[:, :L].contiguous(), sigma)
+    loss_cn, dyn = fe.guidance(yn, L, ref, None, power2, to_db, lo, hi)
+    d_cn = ops.hip.clip_bwd(dyn, wav, thr, full)
+    rl, rg = float(((loss_n - loss_cn).abs() / loss_cn).max()), _rel(dwav_n, d_cn)
+    print(f"\n  {name}: sigma = {sigma}: loss {rl:.2e} grad {rg:.2e}")
+    assert rl < 1e-5 and rg < 1e-5, (name, rl, rg)
+    assert not torch.equal(loss, loss_n)
+
+
+def test_operator_routes_agree():
+    """DeclippingOperator.guidance: the fused mel branch equals the composed mel branch (the fused pair on the materialised y) bit for bit
+    at sigma = 0, and wav_form is ||y - clip(wav)|| with the gradient through the unclipped samples."""
+    from diffmusic_amd import inverse_problem as P
+    from diffmusic_amd.inverse_problem.operator import _MelOperator
+    L, full = 32000, 32032
+    wav, clean = _clips(2, full, 5), _clips(2, L, 6)
+    thr = _thresholds(wav, L)
+    op = P.DeclippingOperator(16000, thr)
+    meas = op.forward(clean)
+    assert torch.equal(meas, torch.clamp(clean, -thr[:, None], thr[:, None]))
+    loss, dwav = op.guidance(wav, L, meas, "mel_spectrogram")
+    loss_c, dwav_c = _MelOperator.guidance(op, wav, L, meas, "mel_spectrogram")                 # the parent's composed branches
+    assert torch.equal(loss, loss_c) and torch.equal(dwav, dwav_c)
+    loss_w, dwav_w = op.guidance(wav, L, meas, "wav_form")
+    w = wav.double().clone().requires_grad_(True)
+    lw = torch.linalg.vector_norm(meas.double() - torch.clamp(w[:, :L], -thr.double()[:, None], thr.double()[:, None]), dim=1)
+    (gw,) = torch.autograd.grad(lw.sum(), w)
+    assert float(((loss_w.double() - lw.detach()).abs() / lw.detach()).max()) < 1e-5 and _rel(dwav_w, gw) < 1e-5
+    assert dwav_w.shape == wav.shape and float(dwav_w[:, L:].abs().max()) == 0.0
+
+
+# ---- 4: NaN --------------------------------------------------------------------------------------------------------------------------------
+def test_a_nan_sample_stays_a_nan():
+    from diffmusic_amd import ops
+    case = STFT_CASES[1]
+    name, L, full, hop, hann, power2, to_db, lo, hi, masked, shared = case
+    fe, wav, mask, ref, z, B = _kernel_problem(case)
+    thr = _thresholds(wav, L)
+    wav = wav.clone()
+    wav[1, 7777] = float("nan")
+    loss, _ = fe.guidance(wav, L, ref, None, power2, to_db, lo, hi, thr=thr)
+    nan = torch.isnan(loss).cpu().tolist()
+    assert nan == [False, True, False], loss                 # fminf / fmaxf would have returned the bound: a finite loss
+    y = ops.hip.clip_fwd(wav, thr, L)
+    assert bool(torch.isnan(y[1, 7777])) and int(torch.isnan(y).sum()) == 1
+    proj = ops.hip.declip_project(wav, torch.clamp(wav[:, :L], -thr[:, None], thr[:, None]).contiguous(), thr, L)
+    assert bool(torch.isnan(proj[1, 7777])) and int(torch.isnan(proj).sum()) == 1
+
+
+# ---- 5: the elementwise kernels against torch, bit for bit ------------------------------------------------------------------------------
+@pytest.mark.parametrize("L,stride,off,full", [(6400, 6400, 0, 6432), (20037, 20101, 1, 20100), (1023, 1027, 3, 1023), (5, 9, 2, 7), (4096, 4100, 0, 4099)])
+def test_elementwise_kernels_match_torch_bitwise(L, stride, off, full):
+    """Rows with a stride that is no multiple of 4 and a start that is not 16-byte aligned (scalar path), aligned rows (float4 path),
+    lengths that end in a partial quad, and the zero tail of clip_bwd; both bindings."""
+    from diffmusic_amd import ops
+    B = 3
+    g = torch.Generator().manual_seed(L)
+    buf = (0.4 * torch.randn(B, stride + 8, generator=g)).cuda()
+    wav = buf[:, off:off + stride]                           # (B, stride) view: row stride stride + 8, start offset `off`
+    assert wav.stride(0) == stride + 8 and wav.shape[1] >= L
+    thr = torch.tensor([0.1, 0.3, 0.55])[:B].cuda()
+    wav[0, 0], wav[1, L - 1] = 0.1, -0.3                     # samples exactly on the threshold: inside (inclusive)
+    dy = torch.randn(B, L, generator=g).cuda()
+    c = thr[:, None]
+    x = wav[:, :L].clone().requires_grad_(True)
+    y_t = torch.clamp(x, -c, c)
+    (g_t,) = torch.autograd.grad((y_t * dy).sum(), x)
+    meas = y_t.detach().contiguous()
+    xhat = buf[:, off + 1:off + 1 + L] if stride + 8 - off - 1 >= L else wav[:, :L]      # another (strided) tensor as the restored audio
+    p_t = torch.where(meas.abs() < c, meas, torch.where(meas >= c, torch.maximum(xhat, c), torch.minimum(xhat, -c)))
+    for binding in (ops.load(), ops.ctypes_hip):
+        y = binding.clip_fwd(wav, thr, L)
+        assert y.shape == (B, L) and y.is_contiguous() and torch.equal(y, y_t.detach())
+        d = binding.clip_bwd(dy, wav, thr, full)
+        assert d.shape == (B, full) and torch.equal(d[:, :L], g_t)
+        if full > L:
+            assert float(d[:, L:].abs().max()) == 0.0
+        p = binding.declip_project(xhat, meas, thr, L)
+        assert p.shape == (B, L) and torch.equal(p, p_t)
+    assert float(g_t[0, 0]) == float(dy[0, 0]) and float(g_t[1, L - 1]) == float(dy[1, L - 1])
+    if L >= 1000:
+        share = float((wav[:, :L].abs() > c).float().mean())
+        assert 0.02 < share < 0.98
+    # the projection keeps every reliable sample and is consistent with the measurement everywhere
+    assert torch.equal(p_t[meas.abs() < c], meas[meas.abs() < c]) and torch.equal(torch.clamp(p_t, -c, c), meas)
+
+
+def test_elementwise_ops_refuse_bad_arguments():
+    from diffmusic_amd import ops
+    h = ops.load()
+    x, thr = torch.zeros(2, 100).cuda(), torch.tensor([0.1, 0.2]).cuda()
+    with pytest.raises(RuntimeError, match="GPU tensor"):
+        h.clip_fwd(torch.zeros(2, 100), thr, 100)
+    with pytest.raises(RuntimeError):
+        h.clip_fwd(x, thr[:1], 100)                           # one threshold per clip
+    with pytest.raises(RuntimeError):
+        h.clip_fwd(x, thr, 101)                               # L beyond the rows
+    with pytest.raises(RuntimeError):
+        h.clip_bwd(x, x, thr, 99)                             # Lfull < L
+    with pytest.raises(AssertionError):
+        ops.ctypes_hip.clip_fwd(x, thr, 101)
+
+
+# ---- 6: teacher-forced steps against the oracle loop ----------------------------------------------------------------------------------
+def _oracle_declip(sample_rate, thr, noiser=None):
+    from oracle import audio, operators as O
+
+    class OracleDeclip(O.BaseOperator):
+        def __init__(self):
+            self.wav2mel = audio.Wav2Mel(sample_rate)
+            self.c = thr.reshape(-1, 1)
+            self.noiser = noiser
+
+        def transform(self, a):
+            return torch.clamp(self.wav2mel(a), min=-80, max=80)
+
+        def forward(self, data, **k):
+            y = torch.clamp(data, -self.c, self.c)
+            return self.noiser(y) if self.noiser is not None else y
+    return OracleDeclip()
+
+
+class _FixedNoiser:
+    def __init__(self, sigma, z):
+        self.sigma, self.z = sigma, z
+
+    def __call__(self, data):
+        return data + self.sigma * self.z
+
+
+@pytest.fixture(scope="module")
+def nets():
+    from diffmusic_amd.engine import HifiGanEngine, VaeDecoderEngine
+    from oracle.models import HifiGan, VaeDecoder
+    voc, vae = HifiGanEngine(HIFI), VaeDecoderEngine(VAE)
+    sv, sa = voc.synth_state_dict(seed=1), vae.synth_state_dict(seed=2)
+    voc.load_state_dict(sv)
+    vae.load_state_dict(sa)
+    rvoc, rvae = HifiGan(**HIFI), VaeDecoder(**VAE)
+    rvoc.load_state_dict(sv, strict=False)
+    rvae.load_state_dict(sa, strict=True)
+    return voc, vae, rvoc.eval(), rvae.eval()
+
+
+STEP_CASES = [("dps", 0.0, 5e-4, "mel_spectrogram", 501, True, 0.0), ("dps", 0.0, 5e-4, "wav_form", 996, True, 0.0),
+              ("mpgd", 0.0, 5e-3, "mel_spectrogram", 251, True, 0.0), ("dsg", 1.0, 0.08, "mel_spectrogram", 501, False, 0.0),
+              ("dps", 0.0, 5e-4, "mel_spectrogram", 501, True, 0.05)]
+
+
+@pytest.mark.parametrize("name,eta,rate,space,t,per_clip,sigma", STEP_CASES,
+                         ids=[f"{c[0]}-{c[3]}-{'clip' if c[5] else 'batch'}-sigma{c[6]}" for c in STEP_CASES])
+def test_teacher_forced_declipping_step(nets, name, eta, rate, space, t, per_clip, sigma):
+    """The procedure of tests/test_gpu_step.py::_teacher_forced, restated, with its bounds: forward < 1e-4, loss < 1e-2, gradient cosine
+    > 0.98, prev_sample < 1e-2.  The threshold is the per-clip median of |.| of the ORACLE's predicted waveform rvoc(rvae(x0_hat)), so the
+    oracle clips half of the samples by construction; the product's clipped share must lie in (0.02, 0.98).  Samples whose clip state
+    differs between the fp16 product and the fp32 oracle switch the gradient at single positions: that moves the gradient's relative L2
+    (printed, not asserted -- tests/test_gpu_step.py does not assert it either) but not its cosine.
+    Measured on an MI355X (profiles/declip.json "teacher_forced"): see that file."""
+    from diffmusic_amd import inverse_problem as P
+    from diffmusic_amd.schedulers import get_scheduler
+    from oracle import schedulers as OS
+    voc, vae, rvoc, rvae = nets
+    B = 2
+    g = torch.Generator().manual_seed(77)
+    clean = 0.3 * torch.sin(torch.arange(LEN) * 0.05)[None] * torch.tensor([[1.0], [0.6]]) + 0.05 * torch.randn(B, LEN, generator=g)
+    x = torch.randn(B, 8, H, W, generator=g)
+    e = torch.randn(B, 8, H, W, generator=g)
+    z = torch.randn(B, 8, H, W, generator=g)
+    z_meas = torch.randn(B, LEN, generator=g)
+    z_step = torch.randn(B, LEN, generator=g)
+    rs = OS.get_scheduler(name)(operator=None, per_clip_norm=per_clip, **SCHED)
+    rs.set_timesteps(200)
+    with torch.no_grad():
+        _, x0 = rs.parent_step(e, t, x, 0.0, None, None)
+        wav_o = rvoc(rvae.decode(x0 / VAE["scaling_factor"]).sample.squeeze(1))[:, :LEN]
+    thr = wav_o.abs().median(dim=1).values                  # on the CPU, from the oracle's prediction
+    assert bool((thr > 0).all())
+    rop = _oracle_declip(16000, thr)
+    op = P.DeclippingOperator(16000, thr, noiser=None)
+    y_clean = rop.forward(clean)
+    assert _rel(op.forward(clean.cuda()), y_clean) < 1e-4, "operator.forward"
+    rop.noiser = _FixedNoiser(sigma, z_meas) if sigma > 0 else None
+    y_ref = rop.forward(clean)
+    y = y_ref.cuda()
+    op.noiser = P.GaussianNoise(sigma)
+    seen = {}
+    inner = op.guidance
+
+    def spy(wav, length, *a, **k):
+        seen["wav"] = wav[:, :length].detach().clone()
+        return inner(wav, length, *a, **k)
+    op.guidance = spy
+    sched = get_scheduler(name)(operator=op, per_clip_norm=per_clip, **SCHED)
+    sched.set_timesteps(200)
+    sched.debug_keep_grad = True
+    rs.operator = rop
+    rop.noiser = _FixedNoiser(sigma, z_step) if sigma > 0 else None
+    kw = dict(eta=eta, ip_guidance_rate=rate, original_waveform_length=LEN, supervised_space=space)
+    noise_kw = dict(sample_noise=z.cuda()) if name == "dsg" else dict(variance_noise=None)
+    opk = dict(noise=z_step.cuda()) if sigma > 0 else {}
+    out = sched.step(e.cuda(), t, x.cuda(), measurement=y, vae=vae, vocoder=voc, op_kwargs=opk, **kw, **noise_kw)
+    torch.cuda.synchronize()
+    rnoise = dict(sample_noise=z) if name == "dsg" else dict(variance_noise=None)
+    ro = rs.step(e, t, x, measurement=y_ref, vae=rvae, vocoder=rvoc, **kw, **rnoise)
+    c = thr[:, None]
+    clip_p, clip_o = seen["wav"].cpu().abs() > c, wav_o.abs() > c
+    share_p, share_o, flipped = float(clip_p.float().mean()), float(clip_o.float().mean()), float((clip_p != clip_o).float().mean())
+    rp = _rel(out.prev_sample, ro.prev_sample)
+    rl = _rel(out.loss.reshape(-1), ro.loss.reshape(-1))
+    rg = _rel(sched.last_grad, ro.sample)
+    cos = torch.nn.functional.cosine_similarity(sched.last_grad.cpu().flatten(), ro.sample.flatten(), dim=0).item()
+    msg = (f"declip {name}/{space}/{'clip' if per_clip else 'batch'}/sigma={sigma}: prev {rp:.2e} loss {rl:.2e} grad {rg:.2e} cos {cos:.4f} "
+           f"clipped product {share_p:.3f} oracle {share_o:.3f} flipped {flipped:.4f}")
+    print("\n  " + msg)
+    assert 0.02 < share_p < 0.98, msg
+    assert abs(share_o - 0.5) < 0.01, msg
+    assert _rel(out.pred_original_sample, ro.pred_original_sample) < 1e-4 or name == "mpgd"
+    assert rl < 1e-2, msg
+    assert cos > 0.98, msg
+    assert rp < 1e-2, msg
+
+
+# ---- 7: through the product -----------------------------------------------------------------------------------------------------------------
+N_CALL, SECONDS = 10, 0.4
+
+
+def _pipe(op, per_clip=True):
+    from diffmusic_amd.pipelines import MusicLDMPipeline
+    from diffmusic_amd.schedulers import get_scheduler
+    from tests.test_gpu_warm_start import HIFI as HIFI_SR, UNET, SCHED as SCHED_W
+    pipe = MusicLDMPipeline.from_pretrained("synthetic", seed=0, unet_config=UNET, vae_config=VAE, vocoder_config=HIFI_SR).to("cuda")
+    pipe.scheduler = get_scheduler("dps")(operator=op, per_clip_norm=per_clip, **SCHED_W)
+    pipe.assume_uncond_equals_cond = True
+    return pipe
+
+
+def _gens(n):
+    return [torch.Generator().manual_seed(100 + k) for k in range(n)]
+
+
+def _hand_loop(pipe, pe, y, n, timesteps=None, x=None, gens=None):
+    """`_unet_eps` + `scheduler.step`, written out; returns (latents, losses)."""
+    dev = torch.device("cuda")
+    s = pipe.scheduler
+    if x is None:
+        gens = _gens(n)
+        s.set_timesteps(N_CALL, device="cuda")
+        timesteps = list(s._timesteps_host)
+        x = pipe.prepare_latents(n, 8, 40, torch.float32, dev, gens, None)
+    cond = pipe._prepare_cond(pe, None, 1, True, dev)
+    losses = []
+    for t in timesteps:
+        eps = pipe._unet_eps(x, t, cond, pipe.default_guidance_scale, True)
+        o = s.step(eps, t, x, eta=0.0, generator=gens, measurement=y, vae=pipe.vae, vocoder=pipe.vocoder, original_waveform_length=LEN,
+                   ip_guidance_rate=5e-4, supervised_space="mel_spectrogram")
+        x = o.prev_sample
+        losses.append(o.loss)
+    return x, losses
+
+
+def _clip_problem(B=3, seed=11):
+    from diffmusic_amd import inverse_problem as P
+    g = torch.Generator().manual_seed(seed)
+    pe = torch.nn.functional.normalize(torch.randn(B, 512, generator=g), dim=-1)
+    clean = 0.3 * torch.sin(torch.arange(LEN) * 0.05)[None] * torch.linspace(1.0, 0.6, B)[:, None] + 0.05 * torch.randn(B, LEN, generator=g)
+    thr = torch.from_numpy(P.threshold_for_sdr(clean, 3.0)).float()
+    op = P.DeclippingOperator(16000, thr, noiser=P.GaussianNoise(0.0))
+    return op, pe, clean
+
+
+def test_declipping_call_equals_the_hand_written_loop(monkeypatch):
+    """`pipe(...)` with a DeclippingOperator against `_unet_eps` + `scheduler.step` written out: bit for bit, cold and warm-started from
+    the measurement (`init_audio=y`, strength 0.5); the ctypes binding (DMX_TORCH_OPS=0) gives the same bits; `project` on the result."""
+    from diffmusic_amd import ops
+    from diffmusic_amd.torch_utils import randn_tensor
+    B = 3
+    op, pe, clean = _clip_problem(B)
+    pipe = _pipe(op)
+    y = op.forward(clean.cuda())
+    share = (clean.abs() > op.threshold[:, None]).float().mean(dim=1)
+    assert bool(((share > 0.5) & (share < 0.98)).all()), share       # 3 dB input SDR: most samples are clipped
+    call = dict(prompt_embeds=pe, audio_length_in_s=SECONDS, num_inference_steps=N_CALL, show_progress=False, measurement=y, eta=0.0)
+    cold = pipe(generator=_gens(B), output_type="latent", **call).audios
+    assert len(pipe.last_losses) == N_CALL and pipe.nan_restarts == 0
+    cold_losses = [l.reshape(-1).clone() for l in pipe.last_losses]
+    x, losses = _hand_loop(pipe, pe, y, B)
+    assert torch.equal(cold, x)
+    assert all(torch.equal(a, b.reshape(-1)) for a, b in zip(cold_losses, losses))
+    assert all(bool(torch.isfinite(l).all()) and bool((l > 0).all()) for l in cold_losses)
+    # warm start from the clipped take itself
+    warm = pipe(generator=_gens(B), output_type="latent", init_audio=y, strength=0.5, **call).audios
+    assert len(pipe.last_losses) == N_CALL // 2 and not torch.equal(warm, cold)
+    s = pipe.scheduler
+    s.set_timesteps(N_CALL, device="cuda")
+    ts = s.timesteps_for_strength(0.5)
+    gens = _gens(B)
+    z0 = pipe._encode_init(y, True, "sample", gens, LEN, 40, torch.device("cuda"))             # mel front end -> encoder -> posterior draw
+    noise = randn_tensor(z0.shape, generator=gens, device=torch.device("cuda"), dtype=torch.float32)
+    xw = s.add_noise(z0, noise, ts[0])
+    xw, _ = _hand_loop(pipe, pe, y, B, timesteps=ts, x=xw, gens=gens)
+    assert torch.equal(warm, xw)
+    # the other binding
+    monkeypatch.setattr(ops, "USE_TORCH_OPS", False)
+    assert not ops.enabled()
+    y_ct = op.forward(clean.cuda())
+    cold_ct = pipe(generator=_gens(B), output_type="latent", **call).audios
+    monkeypatch.setattr(ops, "USE_TORCH_OPS", True)
+    assert torch.equal(y, y_ct) and torch.equal(cold, cold_ct)
+    # the opt-in output stage on the decoded audio
+    audio = pipe(generator=_gens(B), output_type="pt", **call).audios
+    assert audio.shape == (B, LEN)
+    proj = op.project(audio, y)
+    c = op.threshold[:, None].cuda()
+    assert proj.shape == (B, LEN) and torch.equal(torch.clamp(proj, -c, c), y)                 # consistent with the measurement
+    assert torch.equal(proj[y.abs() < c], y[y.abs() < c])
+
+
+def test_declipping_inside_a_track_equals_its_hand_loop():
+    """A TrackOperator of 3 windows around a DeclippingOperator with a scalar threshold, sigma = 0: the call equals the hand-written loop
+    of tests/test_gpu_track.py, restated."""
+    from diffmusic_amd import inverse_problem as P
+    T, R = 16000, 1600                                       # windows of 6400 at 0, 4800, 9600
+    lay = P.TrackLayout(T, LEN, R)
+    assert lay.num_windows == 3
+    g = torch.Generator().manual_seed(21)
+    n = torch.arange(T, dtype=torch.float32)
+    clean = (0.3 * torch.sin(n * 0.05) * (1.0 + 0.3 * torch.sin(n * 0.0007)) + 0.05 * torch.randn(T, generator=g))[None]
+    thr = float(P.threshold_for_sdr(clean, 5.0)[0])
+    inner = P.DeclippingOperator(16000, thr, noiser=P.GaussianNoise(0.0))
+    top = P.TrackOperator(inner, lay)
+    pipe = _pipe(top, per_clip=False)
+    pe = torch.nn.functional.normalize(torch.randn(3, 512, generator=g), dim=-1)
+    y = top.forward(clean.cuda())
+    assert y.shape == (1, T) and float(y.abs().max()) == pytest.approx(thr)
+    call = dict(prompt_embeds=pe, audio_length_in_s=SECONDS, num_inference_steps=N_CALL, show_progress=False, measurement=y, eta=0.0)
+    lat = pipe(generator=_gens(3), output_type="latent", **call).audios
+    assert lat.shape == (3, 8, 10, 16) and len(pipe.last_losses) == N_CALL and all(l.numel() == 1 for l in pipe.last_losses)
+    call_losses = [l.reshape(-1).clone() for l in pipe.last_losses]
+    out = pipe(generator=_gens(3), output_type="pt", **call).audios
+    x, losses = _hand_loop(pipe, pe, y, 3)
+    assert torch.equal(lat, x)
+    assert all(torch.equal(a, b.reshape(-1)) for a, b in zip(call_losses, losses))
+    wav = pipe.vocoder(pipe.vae.decode(x / pipe.vae.config.scaling_factor).sample.squeeze(1)).float()
+    assert out.shape == (1, T) and torch.equal(out, top.stitch(wav).cpu())
+    proj = inner.project(out, y)
+    assert torch.equal(torch.clamp(proj, -thr, thr), y)
+
+
+# ---- 8: clips the fused kernels do not cover ---------------------------------------------------------------------------------------------
+def test_unfused_lengths_take_the_composed_path():
+    """A clip shorter than 2048 samples: dense-DFT mel path around clip_fwd / clip_bwd, against the float64 chain with the bounds of item 1."""
+    from diffmusic_amd import inverse_problem as P
+    L, full, B = 1800, 1832, 3
+    wav, clean = _clips(B, full, 3), _clips(B, L, 4)
+    thr = _thresholds(wav, L)
+    op = P.DeclippingOperator(16000, thr)
+    assert not op.frontend.fused(L)
+    meas = op.forward(clean)
+    ref = op._mel(meas).clone()
+    loss, dwav = op.guidance(wav, L, meas, "mel_spectrogram")
+    loss_t, g_t, clipped = _truth(wav, thr, None, _fb(), ref, L, 160, True, True, True, -80.0, 80.0)
+    share = clipped.double().mean(dim=1)
+    assert bool(((share > 0.02) & (share < 0.98)).all()), share
+    rl = float(((loss.double() - loss_t).abs() / loss_t).max())
+    rg, r0, r1 = _rel(dwav[:, :L], g_t[:, :L]), _rel(dwav[:, :600], g_t[:, :600]), _rel(dwav[:, L - 600:L], g_t[:, L - 600:L])
+    print(f"\n  unfused L = {L}: loss {rl:.2e} grad {rg:.2e} first600 {r0:.2e} last600 {r1:.2e}")
+    assert rl < 2e-5 and rg < 2e-4 and r0 < 5e-4 and r1 < 5e-4, (rl, rg, r0, r1)
+    assert dwav.shape == (B, full) and float(dwav[:, L:].abs().max()) == 0.0
+    assert float(dwav[:, :L][clipped].abs().max()) == 0.0
