@@ -356,6 +356,24 @@ def hifigan_fwd(model, mel, ws):
     return wav
 
 
+def hifigan_fwd_dead(model, mel, s0, s1, ws):
+    """hifigan_fwd for a loss that never looks at the samples [s0, s1) of any clip: zeros there, the same bits elsewhere."""
+    B, T, _ = mel.shape
+    lib = _lib.lib()
+    wav = torch.empty(B, lib.dmx_hifigan_out_len(model, T), dtype=torch.float32, device=mel.device)
+    _lib.check(lib.dmx_hifigan_fwd_dead(model, _p(mel), _p(wav), B, T, int(s0), int(s1), _p(ws), ws.numel(), _stream()), "hifigan_fwd_dead")
+    return wav
+
+
+def hifigan_dead_plan(model, stages):
+    """What the last hifigan forward skipped -> [skipped, total, lo, hi] per stage, flat (dmx_hifigan_dead_plan)."""
+    n = int(stages)
+    arr = [(C.c_int * n)() for _ in range(4)]
+    if _lib.lib().dmx_hifigan_dead_plan(model, *arr, n) < 0:
+        _lib.check(-1, "hifigan_dead_plan")
+    return [int(a[s]) for s in range(n) for a in arr]
+
+
 def hifigan_bwd(model, dwav, frames, model_in_dim):
     dmel = torch.empty(dwav.shape[0], frames, model_in_dim, dtype=_lib.act_dtype(), device=dwav.device)
     _lib.check(_lib.lib().dmx_hifigan_bwd(model, _p(dwav), _p(dmel), _stream()), "hifigan_bwd")

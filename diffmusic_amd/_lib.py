@@ -83,6 +83,10 @@ _SIGS = {
     "dmx_hifigan_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "dmx_hifigan_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dmx_hifigan_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dmx_hifigan_fwd_dead": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]),
+    "dmx_hifigan_dead_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "dmx_conv_dead_rows": (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dmx_vae_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "dmx_vae_decode_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -176,7 +180,7 @@ _SIGS = {
 # loads, so their presence is checked by name
 ADDED_IN_V4 = ("dmx_vae_encoder_create", "dmx_vae_encoder_workspace_bytes", "dmx_vae_encode_fwd", "dmx_latent_init",
                "dmx_track_stitch_fwd", "dmx_track_stitch_bwd", "dmx_audio_guidance_fwd_shaped", "dmx_audio_guidance_bwd_shaped",
-               "dmx_clip_fwd", "dmx_clip_bwd", "dmx_declip_project")
+               "dmx_clip_fwd", "dmx_clip_bwd", "dmx_declip_project", "dmx_hifigan_fwd_dead", "dmx_hifigan_dead_plan", "dmx_conv_dead_rows")
 
 _lib = None
 

@@ -63,6 +63,21 @@ int dmx_hifigan_fwd(dmx_model* m, const uint16_t* mel, float* wav, int batch, in
   if (!ws) { dmx_set_error("null workspace"); return DMX_ERR_WORKSPACE; }
   return dmx_hifigan_fwd_impl(m->impl, mel, wav, batch, frames, ws, ws_bytes, ST(stream));
 }
+int dmx_hifigan_fwd_dead(dmx_model* m, const uint16_t* mel, float* wav, int batch, int frames, int s0, int s1, void* ws, size_t ws_bytes,
+                         void* stream) {
+  int rc = check(m, DMX_MODEL_HIFIGAN);
+  if (rc) return rc;
+  if (!ws || !mel || !wav) { dmx_set_error("hifigan_fwd_dead: null buffer"); return DMX_ERR_STATE; }
+  return dmx_hifigan_fwd_dead_impl(m->impl, mel, wav, batch, frames, s0, s1, ws, ws_bytes, ST(stream));
+}
+int dmx_hifigan_dead_plan(dmx_model* m, int* skipped, int* total, int* lo, int* hi, int n) {
+  if (!m || !m->impl || m->impl->kind != DMX_MODEL_HIFIGAN) { dmx_set_error("wrong model handle"); return -1; }
+  return dmx_hifigan_dead_plan_impl(m->impl, skipped, total, lo, hi, n);
+}
+int dmx_conv_dead_rows(int k, int dil, int pad, int stride, int transposed, int t_in, int t_out, int a, int b, int* lo, int* hi) {
+  if (!lo || !hi) return DMX_ERR_STATE;
+  return dmx_conv_dead_rows_impl(k, dil, pad, stride, transposed, t_in, t_out, a, b, lo, hi);
+}
 int dmx_hifigan_bwd(dmx_model* m, const float* dwav, uint16_t* dmel, void* stream) {
   int rc = check(m, DMX_MODEL_HIFIGAN);
   if (rc) return rc;

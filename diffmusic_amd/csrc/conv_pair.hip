@@ -33,6 +33,10 @@ struct PairParams {
   int single;
   int r_from_slab;                       // stage B's residual is stage A's input: take it from the LDS slab, not from HBM
   int a_tape_bits_only;                  // forward: the activated intermediate leaves the kernel as sign bits only (a.B2), not as a tensor
+  // dead rows (PairDead): workgroup tq of a clip is slab tq below skip_q0 and slab tq + skip_n from there on (nb counts the slabs that run);
+  // stage-A input rows [z0, z1) of every clip are taken as zeros, like the rows outside the clip
+  int skip_q0, skip_n;
+  int z0, z1;
 };
 
 #ifdef DMX_PAIR_STAMPS
@@ -147,7 +151,9 @@ __device__ __forceinline__ void pair_body(const PairParams& P, char* smem, int b
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
   }
   const int T = P.T;
-  const int b = bid / P.nb, tq = bid - b * P.nb;
+  const int b = bid / P.nb;
+  int tq = bid - b * P.nb;
+  if (tq >= P.skip_q0) tq += P.skip_n;                 // across the slabs nobody needs (skip_n == 0: every slab runs)
   const int t0 = tq * P.BMo;
   const bool single = P.single != 0;
   const int kA = single ? 0 : P.a.ntaps, kB = P.b.ntaps;
@@ -187,7 +193,7 @@ __device__ __forceinline__ void pair_body(const PairParams& P, char* smem, int b
     for (int it = 0; it < K::SLAB_IT; ++it) {
       const int c = tid + it * NT, row = c / CPR, piece = c % CPR, t = tfirst + row;
       sv[it] = make_uint4(0, 0, 0, 0);
-      if (row < nrows && t >= 0 && t < T) sv[it] = *reinterpret_cast<const uint4*>(src + ((long long)b * T + t) * C + piece * 8);
+      if (row < nrows && t >= 0 && t < T && !(t >= P.z0 && t < P.z1)) sv[it] = *reinterpret_cast<const uint4*>(src + ((long long)b * T + t) * C + piece * 8);
     }
     const bool masked = !single && (P.a.flags & EPI_MASK);
     const bool maskbits = !single && (P.a.flags & EPI_MASKBITS);
@@ -591,7 +597,17 @@ bool dmx_conv_pair_eligible(const GemmDesc* a, const GemmDesc& b) {
 
 namespace {
 // fills the kernel parameters of one pair; returns its workgroup count, FLOPs and algorithmic bytes
-long long pair_params(const GemmDesc* a, const GemmDesc& b, PairParams& P, double& fl, double& by) {
+// whole slabs of BMo rows inside the dead output rows [skip0, skip1) of a clip of T rows: slabs [q0, q1) (the last slab of a clip is the
+// partial one, dead when the interval reaches T); never all of them
+void pair_skip_slabs(const PairDead* dead, int T, int BMo, int& q0, int& q1) {
+  q0 = q1 = 0;
+  if (!dead || dead->skip1 <= dead->skip0) return;
+  const int nb = cdiv(T, BMo);
+  const int lo = cdiv(dead->skip0 > 0 ? dead->skip0 : 0, BMo), hi = dead->skip1 >= T ? nb : dead->skip1 / BMo;
+  if (hi > lo && hi - lo < nb) { q0 = lo; q1 = hi; }
+}
+
+long long pair_params(const GemmDesc* a, const GemmDesc& b, PairParams& P, double& fl, double& by, const PairDead* dead = nullptr) {
   memset(&P, 0, sizeof(P));
   P.b = b;
   P.single = a ? 0 : 1;
@@ -603,6 +619,14 @@ long long pair_params(const GemmDesc* a, const GemmDesc& b, PairParams& P, doubl
   P.T = b.Wq;
   P.BMo = a ? PAIR_ROWS - hb.lo - hb.hi : PAIR_ROWS;
   P.nb = cdiv(P.T, P.BMo);
+  const int nb_all = P.nb;
+  {
+    int q0, q1;
+    pair_skip_slabs(dead, P.T, P.BMo, q0, q1);
+    P.skip_q0 = q0; P.skip_n = q1 - q0;
+    P.nb -= P.skip_n;
+    if (dead && dead->zero1 > dead->zero0) { P.z0 = dead->zero0; P.z1 = dead->zero1; }
+  }
   // channel biases that nothing precedes in the epilogue order (no leaky-relu' mask: the forward pairs) become the INITIAL value of the
   // stage's accumulators (EPI_BIASINIT): stage A loses an L2 round trip between its K loop and its tail, stage B the epilogue's bias term
   static const bool bias_init = getenv("DMX_NO_BIAS_INIT") == nullptr;
@@ -630,20 +654,33 @@ long long pair_params(const GemmDesc* a, const GemmDesc& b, PairParams& P, doubl
   if (b.flags & EPI_BITS2) by += bits_by;
   if (b.flags & EPI_ACCUM) by += 2.0 * b.M * (double)C;
   if ((b.flags & EPI_LRELU2) && !(b.flags & EPI_NO_C)) by += 2.0 * b.M * (double)C;
+  fl *= (double)P.nb / nb_all; by *= (double)P.nb / nb_all;
   return (long long)nclips * P.nb;
 }
+// rows read as zeros must also be zeros where stage B takes them as its residual: from the slab, never from HBM
+bool pair_zero_ok(const PairParams& P) { return P.z1 <= P.z0 || !(P.b.flags & EPI_RESID) || P.r_from_slab; }
 }  // namespace
+
+void dmx_conv_pair_slabs(const GemmDesc* a, const GemmDesc& b, const PairDead* dead, int* skipped, int* total) {
+  const Halo hb = halo_of(b);
+  const int T = b.Wq, BMo = a ? PAIR_ROWS - hb.lo - hb.hi : PAIR_ROWS;
+  int q0, q1;
+  pair_skip_slabs(dead, T, BMo, q0, q1);
+  *skipped = q1 - q0;
+  *total = cdiv(T, BMo);
+}
 
 // a == nullptr: plain slab convolution of `b`.  Otherwise b.A must be the tensor stage `a` produces
 // (a.C2 when a carries EPI_LRELU2, else a.C); it is taken from LDS and, in the latter case, never written.
 // (DMX_PAIR_EXTRA_LDS: occupancy experiments only -- unused LDS bytes added to the request so that fewer workgroups share a CU)
 static int pair_extra_lds() { static const int v = [] { const char* e = getenv("DMX_PAIR_EXTRA_LDS"); return e ? atoi(e) : 0; }(); return v; }
-int dmx_conv_pair_launch(const GemmDesc* a, const GemmDesc& b, hipStream_t st) {
+int dmx_conv_pair_launch(const GemmDesc* a, const GemmDesc& b, hipStream_t st, const PairDead* dead) {
   if (!dmx_conv_pair_eligible(a, b)) return DMX_ERR_SHAPE;
   PairParams P;
   double fl, by;
-  const long long grid = pair_params(a, b, P, fl, by);
+  const long long grid = pair_params(a, b, P, fl, by, dead);
   if (grid > 0x7fffffffLL) return DMX_ERR_SHAPE;
+  if (!pair_zero_ok(P)) return DMX_ERR_SHAPE;
   const int C = b.N;
   const int rec = dmx_prof_open(st);
   auto launch = [&](auto tag) {
@@ -661,7 +698,7 @@ int dmx_conv_pair_launch(const GemmDesc* a, const GemmDesc& b, hipStream_t st) {
 
 // n (<= 3) independent fused pairs of the same width in one grid (see conv_pair_group_kernel).  The pairs must not depend on each
 // other's outputs and must not accumulate into the same tensor.  Falls back to n launches when the shapes differ in width.
-int dmx_conv_pair_group_launch(int n, const GemmDesc* const* a, const GemmDesc* const* b, hipStream_t st) {
+int dmx_conv_pair_group_launch(int n, const GemmDesc* const* a, const GemmDesc* const* b, hipStream_t st, const PairDead* dead) {
   if (n < 1 || n > DMX_PAIR_GROUP) return DMX_ERR_SHAPE;
   static const bool off = getenv("DMX_NO_PAIR_GROUP") != nullptr;
   bool same = !off && n > 1;
@@ -672,7 +709,7 @@ int dmx_conv_pair_group_launch(int n, const GemmDesc* const* a, const GemmDesc* 
       if (b[j]->C == b[i]->C || (b[j]->C2 && b[j]->C2 == b[i]->C2)) same = false;
   }
   if (!same) {
-    for (int j = 0; j < n; ++j) { const int rc = dmx_conv_pair_launch(a[j], *b[j], st); if (rc != DMX_OK) return rc; }
+    for (int j = 0; j < n; ++j) { const int rc = dmx_conv_pair_launch(a[j], *b[j], st, dead ? dead + j : nullptr); if (rc != DMX_OK) return rc; }
     return DMX_OK;
   }
   // longest problem first: order by K steps per workgroup (stage A + stage B)
@@ -689,8 +726,8 @@ int dmx_conv_pair_group_launch(int n, const GemmDesc* const* a, const GemmDesc* 
   for (int i = 0; i < n; ++i) {
     const int j = order[i];
     double f1, b1;
-    const long long g = pair_params(a[j], *b[j], G.p[i], f1, b1);
-    if (g > 0x7ffffff0LL) return DMX_ERR_SHAPE;
+    const long long g = pair_params(a[j], *b[j], G.p[i], f1, b1, dead ? dead + j : nullptr);
+    if (g > 0x7ffffff0LL || !pair_zero_ok(G.p[i])) return DMX_ERR_SHAPE;
     G.n[i] = (int)g;
     if (g > gmax) gmax = g;
     fl += f1; by += b1; Ksum += a[j]->K + b[j]->K;

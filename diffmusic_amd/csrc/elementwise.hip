@@ -1085,6 +1085,27 @@ __global__ void tanh_bwd_pad8_kernel(const float* __restrict__ dwav, const float
   const float g = dwav[idx] * (1.f - w * w);
   reinterpret_cast<uint4*>(gz)[idx] = make_uint4((uint32_t)f2a(g), 0u, 0u, 0u);
 }
+// The two kernels above for a waveform whose samples [s0, s1) of every clip (T samples each) are dead (hifigan.hip, DeadPlan): x / wav8
+// may hold anything there, NaN included, so the zeros are SELECTED, never produced by a multiplication
+__global__ void gather_col_f32_dead_kernel(const float* __restrict__ x, float* __restrict__ y, long long rows, int ld, int col, int T, int s0,
+                                           int s1) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows) return;
+  const int t = (int)(idx % T);
+  y[idx] = (t >= s0 && t < s1) ? 0.f : x[idx * ld + col];
+}
+__global__ void tanh_bwd_pad8_dead_kernel(const float* __restrict__ dwav, const float* __restrict__ wav8, act_t* __restrict__ gz,
+                                          long long rows, int T, int s0, int s1) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows) return;
+  const int t = (int)(idx % T);
+  float g = 0.f;
+  if (!(t >= s0 && t < s1)) {
+    const float w = wav8[idx * 8];
+    g = dwav[idx] * (1.f - w * w);
+  }
+  reinterpret_cast<uint4*>(gz)[idx] = make_uint4((uint32_t)f2a(g), 0u, 0u, 0u);
+}
 // v (rows) fp32 -> (rows, 8) bf16 with channel 0 = v*scale
 __global__ void scatter_col_pad8_kernel(const float* __restrict__ v, act_t* __restrict__ y, long long rows, float scale) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1405,6 +1426,14 @@ int dmx_scatter_col_pad8(const float* v, act_t* y, long long rows, float scale, 
   return CHECK_LAUNCH();
 }
 
+int dmx_gather_col_f32_dead(const float* x, float* y, long long rows, int ld, int col, int T, int s0, int s1, hipStream_t st) {
+  hipLaunchKernelGGL(gather_col_f32_dead_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, x, y, rows, ld, col, T, s0, s1);
+  return CHECK_LAUNCH();
+}
+int dmx_tanh_bwd_pad8_dead(const float* dwav, const float* wav8, act_t* gz, long long rows, int T, int s0, int s1, hipStream_t st) {
+  hipLaunchKernelGGL(tanh_bwd_pad8_dead_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, dwav, wav8, gz, rows, T, s0, s1);
+  return CHECK_LAUNCH();
+}
 int dmx_gather_col_f32_to_act(const float* x, act_t* y, long long rows, int ld, int col, hipStream_t st) {
   hipLaunchKernelGGL(gather_col_f32_to_act_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, x, y, rows, ld, col);
   return CHECK_LAUNCH();

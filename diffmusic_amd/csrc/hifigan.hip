@@ -21,8 +21,63 @@ struct SplitKScope {
   bool on_;
 };
 
+// ---- rows that an inpainting mask hides from the loss ("dead" rows)
+// The caller may name a span [s0, s1) of output samples, the same for every clip, that the loss never looks at (its gradient there is
+// exactly zero).  The vocoder is a chain of local 1-D convolutions without normalisation, so every activation has an interval of rows
+// that reach no sample outside the span -- and the gradient at exactly those rows is zero.  DeadPlan holds that interval for every
+// tensor of the executor, derived from the layers' own geometry by walking the layer list backwards; the narrow stages then run no
+// workgroup for the whole pair-kernel slabs inside it (conv_pair.h, PairDead).  Intervals are per clip, [a, b), empty when b <= a.
+struct Span { int a = 0, b = 0; bool empty() const { return b <= a; } };
+static inline Span span_meet(Span x, Span y) { Span r{x.a > y.a ? x.a : y.a, x.b < y.b ? x.b : y.b}; if (r.empty()) r = Span{}; return r; }
+static inline long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+static inline long long ceil_div(long long a, long long b) { return -floor_div(-a, b); }
+
+// Input rows (of t_in) of one convolution that feed nothing but the dead rows [a, b) of its output (of t_out).  Output rows outside the
+// clip do not exist, so an interval that touches an end of the clip extends past it.
+//   convolution (stride 1): out[t] reads in[t - pad + j * dil],            j < k  ->  in[u] feeds out[u + pad - j * dil]
+//   transposed convolution: in[u] feeds out[u * stride - pad + j],         j < k
+int dmx_conv_dead_rows_impl(int k, int dil, int pad, int stride, int transposed, int t_in, int t_out, int a, int b, int* lo, int* hi) {
+  *lo = *hi = 0;
+  if (k < 1 || dil < 1 || stride < 1 || pad < 0 || t_in < 1 || t_out < 1) return DMX_ERR_SHAPE;
+  if (!transposed && stride != 1) return DMX_ERR_SHAPE;
+  if (a < 0) a = 0;
+  if (b > t_out) b = t_out;
+  if (b <= a) return DMX_OK;
+  const long long INF = 1ll << 40;
+  const long long ea = a == 0 ? -INF : a, eb = b == t_out ? INF : b;
+  long long l, h;
+  if (!transposed) {
+    l = ea - pad + (long long)(k - 1) * dil;      // the farthest output row in[u] feeds downwards, u + pad - (k - 1) * dil, is dead
+    h = eb - pad;                                 // and so is the farthest upwards, u + pad
+  } else {
+    l = ceil_div(ea + pad, stride);               // u * stride - pad >= ea
+    h = ceil_div(eb - (k - 1) + pad, stride);     // u * stride - pad + k - 1 < eb
+  }
+  if (l < 0) l = 0;
+  if (h > t_in) h = t_in;
+  if (h > l) { *lo = (int)l; *hi = (int)h; }
+  return DMX_OK;
+}
+static Span dead_in(const ConvLayer& L, Span d, int t_in, int t_out) {
+  Span r;
+  (void)dmx_conv_dead_rows_impl(L.kw, L.dil, L.pad_w, L.stride, L.transposed ? 1 : 0, t_in, t_out, d.a, d.b, &r.a, &r.b);
+  return r;
+}
+
+struct DeadPlan {
+  int B = 0, T = 0, s0 = 0, s1 = 0;     // what it was made for
+  bool on = false;                      // some pair launch skips at least one slab (otherwise nothing in the executor changes)
+  Span wav;                             // the span itself, clipped to the output
+  std::vector<Span> out, xs;            // [stage] act_out / sum ; xs_a (met over the branches that read it)
+  std::vector<Span> xo, h, x;           // [stage][kernel][dil] the step's output (xa of the next step, or its share of sum), its
+                                        // intermediate lrelu(convs1 out), its input xa
+  std::vector<int> skipped, total;      // [stage] pair-kernel slabs per clip over the stage's forward and backward launches
+};
+
 struct HifiGan : Model {
   dmx_hifigan_config cfg;
+  DeadPlan plan;                       // kept from call to call: the span is fixed over a trajectory
+  bool use_dead = false;               // the last forward ran with it, and so will its backward
   // fp32 partial tiles for the few small-M / deep-K launches of the vocoder (conv_pre and its dgrad: M = B * frames, K = 7 * C0)
   static constexpr size_t kSplitKBytes = 32u << 20;
   float* splitk_ws = nullptr;
@@ -115,6 +170,95 @@ struct HifiGan : Model {
     return dmx_conv_pair_eligible(&da, db);
   }
 
+  // descriptors of resblock step `id` as the two directions launch it, with stand-in pointers: only their geometry is looked at
+  void step_slabs(int id, int To, bool bwd, const PairDead& pd, int& skipped, int& total) const {
+    GemmDesc da, db;
+    act_t* dummy = reinterpret_cast<act_t*>(size_t(256));
+    unsigned char* dummyb = reinterpret_cast<unsigned char*>(size_t(256));
+    skipped = total = 0;
+    if (!bwd) {
+      Epi ea; ea.flags = EPI_LRELU2 | EPI_NO_C | EPI_BITS2; ea.act_slope = cfg.leaky_relu_slope; ea.B2 = dummyb;
+      Epi eb; eb.flags = EPI_RESID | EPI_RESID_INV; eb.R = dummy; eb.resid_inv_slope = 1.f / cfg.leaky_relu_slope;
+      if (conv_fwd_1d_desc(c1[id], dummy, nullptr, B, To, ea, da) != DMX_OK || conv_fwd_1d_desc(c2[id], nullptr, dummy, B, To, eb, db) != DMX_OK) return;
+    } else {
+      Epi ea; ea.flags = EPI_MASKBITS; ea.mask_slope = cfg.leaky_relu_slope; ea.XB = dummyb;
+      Epi eb; eb.flags = EPI_RESID | EPI_MASKBITS; eb.mask_slope = cfg.leaky_relu_slope; eb.R = dummy; eb.XB = dummyb;
+      if (conv_bwd_1d_desc(c2[id], dummy, dummy, B, To, ea, da) != DMX_OK || conv_bwd_1d_desc(c1[id], dummy, dummy, B, To, eb, db) != DMX_OK) return;
+    }
+    dmx_conv_pair_slabs(&da, db, &pd, &skipped, &total);
+  }
+  bool stage_all_fused(int s, int To) const {
+    bool all = nk <= 3;
+    for (int k = 0; k < nk; ++k) for (int d = 0; d < nd; ++d) all = all && step_is_fused(idx(s, k, d), To);
+    return all;
+  }
+  // a forward slab owns two things: its rows of the step's output and, for the backward pass, the sign bits of the SAME rows of the
+  // intermediate -- whose dead interval is the narrower one (its edge rows still feed live output rows of the neighbouring slab)
+  PairDead dead_fwd(int id) const {
+    const Span w = span_meet(plan.xo[id], plan.h[id]);
+    PairDead pd; pd.skip0 = w.a; pd.skip1 = w.b;
+    return pd;
+  }
+  // the gradient this pair reads lives at the step's output, the one it writes at the step's input (d == 0: the tensor all branches share)
+  PairDead dead_bwd(int s, int id, int d) const {
+    const Span w = d == 0 ? plan.xs[s] : plan.x[id];
+    PairDead pd; pd.skip0 = w.a; pd.skip1 = w.b; pd.zero0 = plan.xo[id].a; pd.zero1 = plan.xo[id].b;
+    return pd;
+  }
+
+  // Walks the layer list backwards from "live = the samples outside [s0, s1)" (see DeadPlan).  One table for both directions: a
+  // forward value at a dead row reaches no live sample, and the gradient at a dead row is zero.  B must be set.
+  void make_plan(int T_, int s0, int s1) {
+    if (plan.B == B && plan.T == T_ && plan.s0 == s0 && plan.s1 == s1 && (int)plan.out.size() == ns) return;
+    plan = DeadPlan();
+    plan.B = B; plan.T = T_; plan.s0 = s0; plan.s1 = s1;
+    plan.out.assign(ns, Span{}); plan.xs.assign(ns, Span{});
+    plan.xo.assign(ns * nk * nd, Span{}); plan.h.assign(ns * nk * nd, Span{}); plan.x.assign(ns * nk * nd, Span{});
+    plan.skipped.assign(ns, 0); plan.total.assign(ns, 0);
+    std::vector<int> len(ns);
+    int t = T_;
+    for (int i = 0; i < ns; ++i) { t = conv_out_len(ups[i], t); len[i] = t; }
+    const int Tout = ns ? len[ns - 1] : T_;
+    plan.wav = span_meet(Span{s0, s1}, Span{0, Tout});
+    if (plan.wav.empty() || ns == 0) return;
+    Span cur = dead_in(conv_post, plan.wav, Tout, Tout);
+    for (int s = ns - 1; s >= 0; --s) {
+      const int To = len[s], Tin = s ? len[s - 1] : T_;
+      plan.out[s] = cur;
+      Span xs{0, To};
+      for (int k = 0; k < nk; ++k) {
+        Span o = cur;                                   // the branch's last step adds into sum: dead where sum is
+        for (int d = nd - 1; d >= 0; --d) {
+          const int id = idx(s, k, d);
+          plan.xo[id] = o;
+          plan.h[id] = dead_in(c2[id], o, To, To);
+          plan.x[id] = span_meet(dead_in(c1[id], plan.h[id], To, To), o);      // read by convs1 and, as the residual, by the output row itself
+          o = plan.x[id];
+        }
+        xs = span_meet(xs, o);
+      }
+      plan.xs[s] = xs;
+      cur = dead_in(ups[s], xs, Tin, To);
+    }
+    if (multi_wanted()) return;                          // (the per-branch streams launch pair by pair: left alone)
+    int any = 0;
+    for (int s = 0; s < ns; ++s) {
+      if (!stage_all_fused(s, len[s])) continue;
+      for (int k = 0; k < nk; ++k)
+        for (int d = 0; d < nd; ++d) {
+          const int id = idx(s, k, d);
+          int sk, tot;
+          step_slabs(id, len[s], false, dead_fwd(id), sk, tot);
+          plan.skipped[s] += sk; plan.total[s] += tot;
+          step_slabs(id, len[s], true, dead_bwd(s, id, d), sk, tot);
+          plan.skipped[s] += sk; plan.total[s] += tot;
+        }
+      any += plan.skipped[s];
+    }
+    plan.on = any > 0;
+    if (!plan.on) plan.skipped.assign(ns, 0);
+  }
+
   int out_len(int T_) const {
     int t = T_;
     for (int i = 0; i < ns; ++i) t = conv_out_len(ups[i], t);
@@ -122,12 +266,20 @@ struct HifiGan : Model {
   }
 
   // mel: (B, T, model_in_dim) bf16 ; wav: (B, Tout) fp32
-  int forward(const act_t* mel, float* wav, int B_, int T_, void* ws, size_t ws_bytes, hipStream_t st) {
+  // [s0, s1): output samples of every clip that the caller will not look at and whose dwav it will pass as zero (s1 <= s0: none).
+  // They come back as 0.0f; backward() uses the same plan.
+  int forward(const act_t* mel, float* wav, int B_, int T_, void* ws, size_t ws_bytes, hipStream_t st, int s0 = 0, int s1 = 0) {
     if (cfg.model_in_dim & 7) return DMX_ERR_SHAPE;
     dry = (ws == nullptr);
+    B = B_;
+    if (!dry) {                                          // (a sizing pass leaves the state of the last real call alone)
+      use_dead = false;
+      if (s1 > s0) { make_plan(T_, s0, s1); use_dead = plan.on; }
+    }
+    const bool dead = use_dead && !dry;
     SplitKScope sk_scope(splitk_ws, kSplitKBytes, !dry && !multi_wanted());
     arena.reset(ws, dry ? (size_t)-1 : ws_bytes);
-    B = B_; T = T_;
+    T = T_;
     Ts.assign(ns, 0);
     xs_a.assign(ns, nullptr); act_out.assign(ns, nullptr);
     ha.assign(ns * nk * nd, nullptr); xa.assign(ns * nk * nd, nullptr);
@@ -183,8 +335,10 @@ struct HifiGan : Model {
         for (int d = 0; d < nd; ++d) {
           GemmDesc da[DMX_MAX_STAGES], db[DMX_MAX_STAGES];
           const GemmDesc* pa[DMX_MAX_STAGES]; const GemmDesc* pb[DMX_MAX_STAGES];
+          PairDead pd[DMX_MAX_STAGES];
           for (int k = 0; k < nk; ++k) {
             const int id = idx(s, k, d);
+            if (dead) pd[k] = dead_fwd(id);
             {
               Epi e; e.flags = EPI_LRELU2 | EPI_NO_C | EPI_BITS2; e.act_slope = slope; e.B2 = hb[id];
               RUN(conv_fwd_1d_desc(c1[id], xa[id], ha[id], B, To, e, da[k]));
@@ -211,8 +365,8 @@ struct HifiGan : Model {
               dmx_set_error("hifigan: resblock step %d was planned as fused but the pair kernel refuses it", idx(s, k, d));
               return DMX_ERR_STATE;
             }
-          if (d < nd - 1) RUN(dmx_conv_pair_group_launch(nk, pa, pb, st));
-          else for (int k = 0; k < nk; ++k) RUN(conv_pair_run(da[k], db[k], st));
+          if (d < nd - 1) RUN(dmx_conv_pair_group_launch(nk, pa, pb, st, dead ? pd : nullptr));
+          else for (int k = 0; k < nk; ++k) RUN(conv_pair_run(da[k], db[k], st, dead ? &pd[k] : nullptr));
         }
         arena.release(mk);
         cur_act = act_out[s];
@@ -271,7 +425,9 @@ struct HifiGan : Model {
       Epi e; e.flags = EPI_F32OUT | EPI_TANH;
       RUN(conv_fwd_1d(conv_post, cur_act, wav8, B, Tout, e, st));
     }
-    RUN(dmx_gather_col_f32(wav8, wav, (long long)B * Tout, 8, 0, st));
+    // dead rows of act_out reach wav8 inside the span only; whatever stands there (stale memory included) must not reach the caller
+    if (dead) RUN(dmx_gather_col_f32_dead(wav8, wav, (long long)B * Tout, 8, 0, Tout, plan.wav.a, plan.wav.b, st));
+    else RUN(dmx_gather_col_f32(wav8, wav, (long long)B * Tout, 8, 0, st));
     have_tape = true;
     return DMX_OK;
   }
@@ -288,7 +444,9 @@ struct HifiGan : Model {
     const int Clast = ups[ns - 1].Cop;
     act_t* g = arena.bf((size_t)B * Tout * Clast);      // grad wrt each resblock output of the last stage
     CHECK_WS("hifigan");
-    RUN(dmx_tanh_bwd_pad8(dwav, wav8, gz, (long long)B * Tout, st));
+    const bool dead = use_dead && !dry;
+    if (dead) RUN(dmx_tanh_bwd_pad8_dead(dwav, wav8, gz, (long long)B * Tout, Tout, plan.wav.a, plan.wav.b, st));
+    else RUN(dmx_tanh_bwd_pad8(dwav, wav8, gz, (long long)B * Tout, st));
     {
       Epi e; e.flags = EPI_MASK; e.X = act_out[ns - 1]; e.mask_slope = 0.01f; e.alpha = 1.f / nk;
       RUN(conv_bwd_1d(conv_post, gz, g, B, Tout, e, st));
@@ -311,12 +469,21 @@ struct HifiGan : Model {
         // grouped launches as in forward(): step d of all branches at once; the last step (d = 0) accumulates into gxs in branch order
         const act_t* gcs[DMX_MAX_STAGES];
         for (int k = 0; k < nk; ++k) gcs[k] = g;
+        // the upsampler's dgrad below reads every row of gxs: the rows no pair launch writes hold their true value, zero
+        if (dead && !plan.xs[s].empty() &&
+            hipMemset2DAsync(gxs + (size_t)plan.xs[s].a * C, (size_t)To * C * sizeof(act_t), 0, (size_t)(plan.xs[s].b - plan.xs[s].a) * C * sizeof(act_t),
+                             (size_t)B, st) != hipSuccess) {
+          dmx_set_error("hifigan: clearing the dead rows of a stage gradient failed");
+          return DMX_ERR_LAUNCH;
+        }
         for (int d = nd - 1; d >= 0; --d) {
           GemmDesc da[DMX_MAX_STAGES], db[DMX_MAX_STAGES];
           const GemmDesc* pa[DMX_MAX_STAGES]; const GemmDesc* pb[DMX_MAX_STAGES];
           act_t* dsts[DMX_MAX_STAGES];
+          PairDead pd[DMX_MAX_STAGES];
           for (int k = 0; k < nk; ++k) {
             const int id = idx(s, k, d);
+            if (dead) pd[k] = dead_bwd(s, id, d);
             {
               Epi e; e.mask_slope = slope; e.flags = EPI_MASKBITS; e.XB = hb[id];
               RUN(conv_bwd_1d_desc(c2[id], gcs[k], ghk[k], B, To, e, da[k]));
@@ -328,8 +495,8 @@ struct HifiGan : Model {
             pa[k] = &da[k]; pb[k] = &db[k];
           }
           if (!dry) {
-            if (d > 0) RUN(dmx_conv_pair_group_launch(nk, pa, pb, st));
-            else for (int k = 0; k < nk; ++k) RUN(conv_pair_run(da[k], db[k], st));
+            if (d > 0) RUN(dmx_conv_pair_group_launch(nk, pa, pb, st, dead ? pd : nullptr));
+            else for (int k = 0; k < nk; ++k) RUN(conv_pair_run(da[k], db[k], st, dead ? &pd[k] : nullptr));
           }
           for (int k = 0; k < nk; ++k) gcs[k] = dsts[k];
         }
@@ -389,6 +556,20 @@ Model* dmx_make_hifigan(const dmx_hifigan_config* c) { return new HifiGan(*c); }
 int dmx_hifigan_out_len_impl(Model* m, int T) { return static_cast<HifiGan*>(m)->out_len(T); }
 int dmx_hifigan_fwd_impl(Model* m, const act_t* mel, float* wav, int B, int T, void* ws, size_t wsb, hipStream_t st) {
   return static_cast<HifiGan*>(m)->forward(mel, wav, B, T, ws, wsb, st);
+}
+int dmx_hifigan_fwd_dead_impl(Model* m, const act_t* mel, float* wav, int B, int T, int s0, int s1, void* ws, size_t wsb, hipStream_t st) {
+  return static_cast<HifiGan*>(m)->forward(mel, wav, B, T, ws, wsb, st, s0, s1);
+}
+int dmx_hifigan_dead_plan_impl(Model* m, int* skipped, int* total, int* lo, int* hi, int n) {
+  HifiGan* h = static_cast<HifiGan*>(m);
+  for (int s = 0; s < n && s < h->ns; ++s) {
+    const bool have = h->use_dead && s < (int)h->plan.out.size();
+    if (skipped) skipped[s] = have ? h->plan.skipped[s] : 0;
+    if (total) total[s] = have ? h->plan.total[s] : 0;
+    if (lo) lo[s] = have ? h->plan.out[s].a : 0;
+    if (hi) hi[s] = have ? h->plan.out[s].b : 0;
+  }
+  return h->ns;
 }
 int dmx_hifigan_bwd_impl(Model* m, const float* dwav, act_t* dmel, hipStream_t st) {
   return static_cast<HifiGan*>(m)->backward(dwav, dmel, st);

@@ -44,6 +44,9 @@ int dmx_bf16_to_f32(const act_t* x, float* y, long long n, float scale, hipStrea
 int dmx_extract_col(const act_t* x, float* y, long long rows, int ld, int col, hipStream_t st);
 int dmx_gather_col_f32(const float* x, float* y, long long rows, int ld, int col, hipStream_t st);
 int dmx_tanh_bwd_pad8(const float* dwav, const float* wav8, act_t* gz, long long rows, hipStream_t st);
+// the same two for clips of T samples whose samples [s0, s1) are dead: zeros there by select, x / wav8 not read
+int dmx_gather_col_f32_dead(const float* x, float* y, long long rows, int ld, int col, int T, int s0, int s1, hipStream_t st);
+int dmx_tanh_bwd_pad8_dead(const float* dwav, const float* wav8, act_t* gz, long long rows, int T, int s0, int s1, hipStream_t st);
 int dmx_scatter_col_pad8(const float* v, act_t* y, long long rows, float scale, hipStream_t st);
 int dmx_gather_col_f32_to_act(const float* x, act_t* y, long long rows, int ld, int col, hipStream_t st);
 int dmx_pad_col8_act(const act_t* v, act_t* y, long long rows, hipStream_t st);

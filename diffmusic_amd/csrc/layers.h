@@ -121,7 +121,8 @@ int conv_bwd_1d(const ConvLayer& L, const act_t* dout, void* din, int B, int Ti,
 // descriptor-only builders (stride-1, non-transposed) and the fused two-stage launch used by the HiFi-GAN resblocks
 int conv_fwd_1d_desc(const ConvLayer& L, const act_t* in, void* out, int B, int Ti, const Epi& e, GemmDesc& d);
 int conv_bwd_1d_desc(const ConvLayer& L, const act_t* dout, void* din, int B, int Ti, const Epi& e, GemmDesc& d);
-int conv_pair_run(const GemmDesc& a, const GemmDesc& b, hipStream_t st);
+struct PairDead;      // conv_pair.h
+int conv_pair_run(const GemmDesc& a, const GemmDesc& b, hipStream_t st, const PairDead* dead = nullptr);
 // gn_rows (optional, here and in conv_bwd_2d): rows per statistics slot of this launch, 0 = it carried none (dmx_gemm_launch)
 int conv_fwd_2d(const ConvLayer& L, const act_t* in, void* out, int B, int Hi, int Wi, const Epi& e, hipStream_t st, int* gn_rows = nullptr);
 // conv3x3(pad 1)(nearest_upsample_x2(in)) without the upsampled tensor: in (B, Hi, Wi, Cip) -> out (B, 2Hi, 2Wi, Cop), and its dgrad

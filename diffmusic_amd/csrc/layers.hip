@@ -410,8 +410,9 @@ int conv_bwd_1d(const ConvLayer& L, const act_t* dout, void* din, int B, int Ti,
 }
 
 // stage `a` then stage `b` (b.A is what a produces): one fused launch when the pair kernel takes the shape, else two launches
-int conv_pair_run(const GemmDesc& a, const GemmDesc& b, hipStream_t st) {
-  if (dmx_conv_pair_eligible(&a, b)) return dmx_conv_pair_launch(&a, b, st);
+int conv_pair_run(const GemmDesc& a, const GemmDesc& b, hipStream_t st, const PairDead* dead) {
+  if (dmx_conv_pair_eligible(&a, b)) return dmx_conv_pair_launch(&a, b, st, dead);
+  if (dead) { dmx_set_error("conv_pair_run: dead rows need the fused pair kernel"); return DMX_ERR_SHAPE; }
   const int rc = dmx_gemm_launch(a, st);
   return rc != DMX_OK ? rc : dmx_gemm_launch(b, st);
 }

@@ -24,6 +24,9 @@ Model* dmx_make_hifigan(const dmx_hifigan_config* c);
 int dmx_hifigan_out_len_impl(Model* m, int T);
 int dmx_hifigan_fwd_impl(Model* m, const act_t* mel, float* wav, int B, int T, void* ws, size_t wsb, hipStream_t st);
 int dmx_hifigan_bwd_impl(Model* m, const float* dwav, act_t* dmel, hipStream_t st);
+int dmx_hifigan_fwd_dead_impl(Model* m, const act_t* mel, float* wav, int B, int T, int s0, int s1, void* ws, size_t wsb, hipStream_t st);
+int dmx_hifigan_dead_plan_impl(Model* m, int* skipped, int* total, int* lo, int* hi, int n);
+int dmx_conv_dead_rows_impl(int k, int dil, int pad, int stride, int transposed, int t_in, int t_out, int a, int b, int* lo, int* hi);
 size_t dmx_hifigan_ws_impl(Model* m, int B, int T);
 
 Model* dmx_make_vae(const dmx_vae_config* c);

@@ -28,6 +28,8 @@
 #pragma weak dmx_clip_fwd
 #pragma weak dmx_clip_bwd
 #pragma weak dmx_declip_project
+#pragma weak dmx_hifigan_fwd_dead
+#pragma weak dmx_hifigan_dead_plan
 
 namespace {
 
@@ -435,6 +437,25 @@ at::Tensor hifigan_fwd(int64_t model, const at::Tensor& mel, at::Tensor ws) {
   ok(dmx_hifigan_fwd(m, (const uint16_t*)mel.data_ptr(), wav.data_ptr<float>(), B, T, ws.data_ptr(), ws.nbytes(), cur_stream()), "hifigan_fwd");
   return wav;
 }
+at::Tensor hifigan_fwd_dead(int64_t model, const at::Tensor& mel, int64_t s0, int64_t s1, at::Tensor ws) {
+  act_cuda(mel, "mel");
+  DMX_DEVICE_OF(mel);
+  dmx_model* m = reinterpret_cast<dmx_model*>(model);
+  const int B = (int)mel.size(0), T = (int)mel.size(1);
+  at::Tensor wav = at::empty({B, dmx_hifigan_out_len(m, T)}, mel.options().dtype(at::kFloat));
+  ok(dmx_hifigan_fwd_dead(m, (const uint16_t*)mel.data_ptr(), wav.data_ptr<float>(), B, T, (int)s0, (int)s1, ws.data_ptr(), ws.nbytes(), cur_stream()),
+     "hifigan_fwd_dead");
+  return wav;
+}
+std::vector<int64_t> hifigan_dead_plan(int64_t model, int64_t stages) {
+  const int n = (int)stages;
+  std::vector<int> a[4];
+  for (auto& v : a) v.assign(n > 0 ? n : 1, 0);
+  TORCH_CHECK(dmx_hifigan_dead_plan(reinterpret_cast<dmx_model*>(model), a[0].data(), a[1].data(), a[2].data(), a[3].data(), n) >= 0, "hifigan_dead_plan");
+  std::vector<int64_t> out;
+  for (int s = 0; s < n; ++s) for (auto& v : a) out.push_back(v[s]);
+  return out;
+}
 at::Tensor hifigan_bwd(int64_t model, const at::Tensor& dwav, int64_t frames, int64_t model_in_dim) {
   f32_cuda(dwav, "dwav");
   DMX_DEVICE_OF(dwav);
@@ -504,7 +525,9 @@ TORCH_LIBRARY(diffmusic_hip, m) {
                                                          {"dmx_audio_guidance_bwd_shaped", (const void*)&dmx_audio_guidance_bwd_shaped},
                                                          {"dmx_clip_fwd", (const void*)&dmx_clip_fwd},
                                                          {"dmx_clip_bwd", (const void*)&dmx_clip_bwd},
-                                                         {"dmx_declip_project", (const void*)&dmx_declip_project}};
+                                                         {"dmx_declip_project", (const void*)&dmx_declip_project},
+                                                         {"dmx_hifigan_fwd_dead", (const void*)&dmx_hifigan_fwd_dead},
+                                                         {"dmx_hifigan_dead_plan", (const void*)&dmx_hifigan_dead_plan}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
                   "` (a build from before the VAE encoder / track-mode / declipping entry points): rebuild with `python -m diffmusic_amd.build --force`");
@@ -550,6 +573,8 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("grad_normalize_(Tensor(a!) dwav, float target) -> Tensor", &grad_normalize_);
   m.def("hifigan_fwd(int model, Tensor mel, Tensor(a!) ws) -> Tensor", &hifigan_fwd);
   m.def("hifigan_bwd(int model, Tensor dwav, int frames, int model_in_dim) -> Tensor", &hifigan_bwd);
+  m.def("hifigan_fwd_dead(int model, Tensor mel, int s0, int s1, Tensor(a!) ws) -> Tensor", &hifigan_fwd_dead);
+  m.def("hifigan_dead_plan(int model, int stages) -> int[]", &hifigan_dead_plan);
   m.def("htsat_fwd(int model, Tensor mel, bool keep_state, Tensor(a!) ws) -> Tensor", &htsat_fwd);
   m.def("htsat_bwd(int model, Tensor dfeat, Tensor? scale, int frames, int bins) -> Tensor", &htsat_bwd);
   m.def("gram_fwd(Tensor feat) -> Tensor", &gram_fwd);

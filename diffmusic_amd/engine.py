@@ -4,6 +4,7 @@ Only plumbing lives here: handle life cycle, weights, workspace sizing and input
 `ops.hip.<name>` call (diffmusic_amd/ops.py), which picks the binding of the C ABI: the PyTorch custom ops
 `torch.ops.diffmusic_hip.*` (default) or ctypes, the same `extern "C"` launchers on torch's current HIP stream either way."""
 import ctypes as C
+import os
 import torch
 from . import _lib as L
 from . import ops
@@ -112,6 +113,9 @@ class HifiGanEngine(_Engine):
         _fill(c.resblock_dilation_sizes, [d for row in cfg["resblock_dilation_sizes"] for d in row])
         c.leaky_relu_slope = cfg["leaky_relu_slope"]
         super().__init__(L.lib().dmx_hifigan_create(C.byref(c)), cfg, device)
+        # forward(mel, dead=(s0, s1)) skips the rows that reach only those samples; False (or DMX_NO_DEAD_SPAN=1 at construction) ignores
+        # `dead` and runs every row, for A/B measurements and the equality tests
+        self.dead_span_enabled = os.environ.get("DMX_NO_DEAD_SPAN", "0") in ("", "0")
 
     def _stride_of(self, name):
         return self.cfg["upsample_rates"][int(name.split(".")[1])]
@@ -128,16 +132,29 @@ class HifiGanEngine(_Engine):
         """`vocoder(mel_spectrogram)` of the reference: (B, T, model_in_dim) any float dtype -> (B, samples) fp32."""
         return self.forward(mel.to(device=self.device, dtype=L.act_dtype()).contiguous())
 
-    def forward(self, mel):
-        """mel (B, T, model_in_dim) act-dtype cuda -> wav (B, out_len) fp32."""
+    def forward(self, mel, dead=None):
+        """mel (B, T, model_in_dim) act-dtype cuda -> wav (B, out_len) fp32.
+        dead = (s0, s1): the caller's loss ignores the samples [s0, s1) of every clip and its dwav is zero there (an operator's
+        `dead_span`).  wav is then 0 on the span and the same bits elsewhere, `backward` returns the same dmel, and the narrow stages
+        skip the rows that reach only the span (csrc/hifigan.hip, DeadPlan)."""
         assert mel.dtype == L.act_dtype() and mel.is_cuda and mel.is_contiguous()
         B, T, _ = mel.shape
         lib = L.lib()
         ws = self._workspace(("h", B, T), lib.dmx_hifigan_workspace_bytes(self._h, B, T))
         self._shape = (B, T)
+        if dead is not None and self.dead_span_enabled and int(dead[1]) > int(dead[0]):
+            return ops.hip.hifigan_fwd_dead(self._h.value, mel, int(dead[0]), int(dead[1]), ws)
         return ops.hip.hifigan_fwd(self._h.value, mel, ws)
 
+    def dead_plan(self):
+        """What the last forward skipped, per upsampling stage: dicts of pair-kernel slabs per clip `skipped` / `total` (forward and
+        backward launches together) and the dead rows `span` of the stage's output; all zero after a plain forward."""
+        n = len(self.cfg["upsample_rates"])
+        flat = list(ops.hip.hifigan_dead_plan(self._h.value, n))
+        return [dict(skipped=flat[4 * s], total=flat[4 * s + 1], span=(flat[4 * s + 2], flat[4 * s + 3])) for s in range(n)]
+
     def backward(self, dwav):
+        """dwav (B, out_len) fp32 -> dmel, with the tape (and the dead span) of the last forward."""
         _, T = self._shape
         assert dwav.dtype == torch.float32 and dwav.is_contiguous()
         return ops.hip.hifigan_bwd(self._h.value, dwav, T, self.cfg["model_in_dim"])

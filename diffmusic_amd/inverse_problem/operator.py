@@ -204,6 +204,13 @@ class BaseOperator:
     def guidance(self, wav, length, measurement, supervised_space, noise=None, step=None, generator=None):
         raise NotImplementedError
 
+    def dead_span(self, length):
+        """The longest run of samples [s0, s1) of a waveform of `length` samples on which, for EVERY clip of the batch, A(wav) does not
+        depend on wav and the gradient `guidance` returns is identically zero -- or None.  The guided step hands it to the vocoder,
+        which then skips the rows that reach only those samples (HifiGanEngine.forward, `dead=`).  Only an operator that can prove
+        it overrides this; measurement noise (sigma > 0) is added after A and changes nothing."""
+        return None
+
     def _step_noise(self, shape, device, noise, step, generator):
         """-> (z, sigma): the standard-normal tensor of shape `shape` = A(wav).shape that this step adds as sigma * z, or (None, 0.0).
         Decided by the noiser's explicit `additive_sigma` (noise.py); `noise` given = teacher forcing, else the noiser draws."""
@@ -275,6 +282,17 @@ class _MelOperator(BaseOperator):
         return loss, self._a_bwd(dy, wav.shape[1])
 
 
+def longest_zero_run(mask):
+    """(s0, s1) of the longest run of exact zeros in a 1-D host mask (the first of equally long ones), or None without a zero."""
+    z = np.concatenate(([0], (np.asarray(mask, dtype=np.float32).reshape(-1) == 0).astype(np.int8), [0]))
+    edges = np.flatnonzero(np.diff(z))                       # run starts at even positions, ends (exclusive) at odd ones
+    if edges.size == 0:
+        return None
+    starts, ends = edges[0::2], edges[1::2]
+    i = int(np.argmax(ends - starts))
+    return int(starts[i]), int(ends[i])
+
+
 class IdentityOperator(_MelOperator):                     # operator.py:17-45
     fused_mask = True
 
@@ -328,6 +346,16 @@ class MusicInpaintingOperator(_MelOperator):              # operator.py:48-133
             for start in range(0, mask.shape[1], interval):
                 mask[:, start:min(start + dur, mask.shape[1])] = 0.
         return mask
+
+    def dead_span(self, length):
+        """The longest run of zeros of the mask (one (1, n) mask for all clips, fixed at construction): found on the host once and kept
+        with the mask it was found in."""
+        if length != self.mask.shape[1]:
+            return None
+        cached = getattr(self, "_dead_span", None)
+        if cached is None or cached[0] is not self.mask or cached[1] != self.mask._version:
+            cached = self._dead_span = (self.mask, self.mask._version, longest_zero_run(self.mask[0]))
+        return cached[2]
 
     def _mask_on(self, device):
         if self._mask_dev is None or self._mask_dev.device != device:

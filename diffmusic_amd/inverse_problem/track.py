@@ -94,6 +94,11 @@ class TrackOperator:
     def cache_reference(self):
         return self.inner.cache_reference
 
+    def dead_span(self, length):
+        """None: the windows of a track overlap and are cross-faded into it, so a hole of the track is not one span shared by all
+        windows (BaseOperator.dead_span)."""
+        return None
+
     def forward(self, data, **kwargs):
         return self.inner.forward(data, **kwargs)
 

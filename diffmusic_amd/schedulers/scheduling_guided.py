@@ -175,7 +175,9 @@ class GuidedDDIMScheduler:
         with stage("vae_fwd"):
             mel = vae.decode_hip(x0, z_scale=zs, keep_state=True)              # (B, H, W) fp16
         with stage("hifigan_fwd"):
-            wav = vocoder.forward(mel)                                         # (B, Lfull) fp32
+            span = getattr(self.operator, "dead_span", None)                   # samples the loss never sees (an inpainting hole), or None
+            dead = span(length) if span is not None else None
+            wav = vocoder.forward(mel) if dead is None else vocoder.forward(mel, dead=dead)      # (B, Lfull) fp32
         with stage("operator_mel_loss_fwd_bwd"):
             loss, dwav = self.operator.guidance(wav, length, measurement, supervised_space, **(op_kwargs or {}))
             if not self.per_clip_norm and loss.numel() > 1:

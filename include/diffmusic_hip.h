@@ -107,6 +107,20 @@ int dmx_hifigan_fwd(dmx_model* m, const uint16_t* mel, float* wav, int batch, in
                     void* stream);
 /* dwav (B, out_len) fp32 -> dmel (B, frames, model_in_dim) f16; ws as left by the forward call */
 int dmx_hifigan_bwd(dmx_model* m, const float* dwav, uint16_t* dmel, void* stream);
+/* The same forward for a caller whose loss never looks at the output samples [s0, s1) of any clip (an inpainting hole) and whose
+   dwav is exactly zero there: wav comes back 0.0f on the span and bit-equal to dmx_hifigan_fwd elsewhere, and the dmx_hifigan_bwd call
+   that follows returns the dmel of the plain pair (whatever dwav holds on the span is taken as zero).  In between, the narrow
+   stages run no work for the rows that reach only the span.  A span too short to save a whole slab of rows anywhere (or s1 <= s0)
+   makes this call dmx_hifigan_fwd. */
+int dmx_hifigan_fwd_dead(dmx_model* m, const uint16_t* mel, float* wav, int batch, int frames, int s0, int s1, void* ws,
+                         size_t ws_bytes, void* stream);
+/* What the last forward call skipped, per upsampling stage (n = capacity of the arrays, any of them may be NULL): pair-kernel slabs
+   per clip skipped / in all over the stage's forward and backward launches, and the dead rows [lo, hi) of the stage's output.  All
+   zero after a plain forward or for a stage that skips nothing.  Returns the number of stages, or -1. */
+int dmx_hifigan_dead_plan(dmx_model* m, int* skipped, int* total, int* lo, int* hi, int n);
+/* Host arithmetic of that plan for ONE layer (no GPU): the input rows [*lo, *hi) of a 1-D convolution (kernel k, dilation, padding,
+   stride 1) or transposed convolution (stride) that feed only the output rows [a, b); t_in / t_out are the two lengths. */
+int dmx_conv_dead_rows(int k, int dil, int pad, int stride, int transposed, int t_in, int t_out, int a, int b, int* lo, int* hi);
 
 /* ---- VAE decoder: replaces `vae.decode(z).sample` (scheduling_dps.py:195-197) + backward ------- */
 size_t dmx_vae_workspace_bytes(dmx_model* m, int batch, int h, int w);
