@@ -10,6 +10,12 @@ chosen space) and its gradient with respect to the vocoder output, computed by h
 backward kernels (the reference gets the same quantity from torch.autograd.grad,
 scheduling_dps.py:202-212).
 
+An operator defines A once: `apply(x, length, **kw) -> (y, adjoint)` gives y = A(x[:, :length]) without measurement noise and a
+closure `adjoint(dy, full)`, the transpose of dA/dx at x.  The closure captures whatever the transpose needs (the input of a clip, the
+input length of a FIR, the impulse response of that call); nothing about one call is kept on the operator.  `forward` is `apply` plus
+the noiser, and `BaseOperator.guidance` is the one driver of the guided step: `apply`, the step's noise, the loss in the supervised
+space, `adjoint`.  In mel space `_MelOperator` first asks `_on_load` whether A can ride inside the fused STFT-mel kernels.
+
 Measurement noise inside the step: the reference's `forward` ends in `self.noiser(...)` and its schedulers call it on the
 predicted audio in every step, so with sigma > 0 the loss is taken on A(wav) + sigma * z.  `guidance(..., noise=None, step=None,
 generator=None)` does the same when the operator's noiser has `additive_sigma > 0`: z is `noise` when given (a standard-normal
@@ -92,16 +98,12 @@ class SpectralFrontend:
         noise (B, >= length) / noise_mag (B, bins, frames; power2 False): standard-normal draws entering as wav * mask + sigma * noise,
         resp. |STFT| + sigma * noise_mag, inside both kernels (dmx_audio_guidance_{fwd,bwd}_ex).
         thr (B) fp32: per-clip hard-clip thresholds, y = clip(wav * mask, thr) + sigma * noise inside both kernels
-        (dmx_audio_guidance_{fwd,bwd}_shaped); None takes the calls above."""
+        (dmx_audio_guidance_{fwd,bwd}_shaped, which the entry points above forward to with null pointers: one call serves all)."""
         assert wav.dtype == torch.float32 and wav.is_cuda and wav.stride(1) == 1 and ref.dtype == torch.float32 and ref.is_contiguous()
         B, full = wav.shape
         st = self._get_state(B, length, wav.device)
-        args = (self._h.value, wav, mask, ref, st, int(length), int(full), bool(power2), bool(to_db), float(lo), float(hi), float(gscale))
-        if thr is not None:
-            return ops.hip.mel_guidance_shaped(*args, noise, noise_mag, float(sigma), thr)
-        if noise is None and noise_mag is None:
-            return ops.hip.mel_guidance(*args)
-        return ops.hip.mel_guidance_noisy(*args, noise, noise_mag, float(sigma))
+        return ops.hip.mel_guidance_shaped(self._h.value, wav, mask, ref, st, int(length), int(full), bool(power2), bool(to_db), float(lo),
+                                           float(hi), float(gscale), noise, noise_mag, float(sigma), thr)
 
     def stft_mag(self, wav, length):
         B = wav.shape[0]
@@ -158,8 +160,13 @@ def _as_f32_cuda(x):
     return x.to(torch.float32)
 
 
+def _flat_rows(m):
+    return m.reshape(m.shape[0], -1).contiguous()
+
+
 class BaseOperator:
-    """forward(data) = A(data); transform(x) = supervised-space map; inverse_transform(mel, vocoder)."""
+    """forward(data) = noiser(A(data)); transform(x) = supervised-space map; inverse_transform(mel, vocoder)."""
+    noiser = None
 
     def transform(self, data, *args, **kwargs):
         raise NotImplementedError
@@ -169,8 +176,17 @@ class BaseOperator:
             mel_spectrogram = mel_spectrogram.squeeze(1)
         return vocoder(mel_spectrogram)
 
-    def forward(self, data, **kwargs):
+    def apply(self, x, length, **kw):
+        """x (B, >= length) fp32 on the GPU, any row stride -> (y, adjoint).
+        y = A(x[:, :length]), contiguous fp32, WITHOUT measurement noise.
+        adjoint(dy, full) -> (B, full) fp32: the transpose of dA/dx at x applied to dy, zeros past `length`."""
         raise NotImplementedError
+
+    def _measure(self, y):
+        return self.noiser(y) if self.noiser is not None else y
+
+    def forward(self, data, **kwargs):
+        return self._measure(self.apply(_as_f32_cuda(data), data.shape[-1], **kwargs)[0])
 
     # ---- guided-step extension -------------------------------------------------------------
     _ref_cache = None
@@ -180,7 +196,7 @@ class BaseOperator:
         """Forget the cached `transform(measurement)` and restart the noiser's step stream; called at the start of every trajectory
         (set_timesteps / __call__)."""
         self._ref_cache = None
-        reset = getattr(getattr(self, "noiser", None), "reset", None)
+        reset = getattr(self.noiser, "reset", None)
         if reset is not None:
             reset()
 
@@ -201,8 +217,27 @@ class BaseOperator:
         del cache[4:]
         return cache[0][3]
 
-    def guidance(self, wav, length, measurement, supervised_space, noise=None, step=None, generator=None):
+    def guidance(self, wav, length, measurement, supervised_space, noise=None, step=None, generator=None, **apply_kw):
+        """-> (loss (B), dwav (B, wav.shape[1])): ||transform(measurement) - transform(A(wav[:, :length]) + sigma * z)||_2 per clip and
+        its gradient; `apply_kw` goes to `apply` (`ir=` of the dereverberation)."""
+        if supervised_space == "mel_spectrogram":
+            return self._mel_guidance(wav, length, measurement, noise, step, generator, **apply_kw)
+        if supervised_space != "wav_form":
+            raise ValueError("supervised_space should be either 'wav_form' or 'mel_spectrogram")
+        y, adjoint = self._noisy_apply(wav, length, noise, step, generator, **apply_kw)
+        loss, dy = l2_loss(self._ref(measurement, "wav_form", _flat_rows), y.reshape(y.shape[0], -1))
+        return loss, adjoint(dy.reshape(y.shape), wav.shape[1])
+
+    def _mel_guidance(self, wav, length, measurement, noise, step, generator, **apply_kw):
         raise NotImplementedError
+
+    def _noisy_apply(self, wav, length, noise, step, generator, **apply_kw):
+        """`apply` with this step's measurement noise on the materialised y; the noise is additive, so the transpose is unchanged."""
+        y, adjoint = self.apply(wav, length, **apply_kw)
+        z, sigma = self._step_noise(y.shape, y.device, noise, step, generator)
+        if z is not None:
+            y = ops.hip.noise_add(y, z, sigma)
+        return y, adjoint
 
     def dead_span(self, length):
         """The longest run of samples [s0, s1) of a waveform of `length` samples on which, for EVERY clip of the batch, A(wav) does not
@@ -214,72 +249,63 @@ class BaseOperator:
     def _step_noise(self, shape, device, noise, step, generator):
         """-> (z, sigma): the standard-normal tensor of shape `shape` = A(wav).shape that this step adds as sigma * z, or (None, 0.0).
         Decided by the noiser's explicit `additive_sigma` (noise.py); `noise` given = teacher forcing, else the noiser draws."""
-        noiser = getattr(self, "noiser", None)
-        sigma = step_sigma(noiser)
+        sigma = step_sigma(self.noiser)
         if sigma <= 0.0:
             return None, 0.0
         if noise is None:
-            return noiser.draw(tuple(shape), device, step=step, generator=generator), sigma
+            return self.noiser.draw(tuple(shape), device, step=step, generator=generator), sigma
         if tuple(noise.shape) != tuple(shape):
             raise ValueError(f"noise must be shaped like A(x) = {tuple(shape)}, got {tuple(noise.shape)}")
         return _as_f32_cuda(noise).contiguous(), sigma
 
 
 class _MelOperator(BaseOperator):
-    """Shared mel plumbing: transform = wav2mel (dB) with optional clamp; returns (B, n_mels, T)."""
+    """Shared mel plumbing: transform = wav2mel (dB) between the `clamp` bounds; returns (B, n_mels, T)."""
     clamp = (-80.0, 80.0)
 
-    def _init_mel(self, sample_rate=16000):
-        self.frontend = SpectralFrontend(sample_rate, 1024, 160, 64, "hann")
+    def _init_mel(self, sample_rate=16000, lazy=False):
+        """lazy: the front end (GPU tables) is made on first use, so the operator can be built without a GPU."""
+        self._mel_rate, self._frontend = sample_rate, None
+        if not lazy:
+            self.frontend
+
+    @property
+    def frontend(self):
+        if self._frontend is None:
+            self._frontend = SpectralFrontend(self._mel_rate, 1024, 160, 64, "hann")
+        return self._frontend
 
     def _mel(self, audio, length=None):
-        lo, hi = self.clamp if self.clamp else (_NEG, _POS)
         audio = _as_f32_cuda(audio)
-        return self.frontend.transform_fwd(audio, length or audio.shape[-1], True, True, lo, hi)
+        return self.frontend.transform_fwd(audio, length or audio.shape[-1], True, True, *self.clamp)
 
     def transform(self, audio):
         return self._mel(audio).transpose(1, 2)             # torchaudio layout (B, n_mels, frames)
 
-    # A(.) on the vocoder output: subclasses override _a_fwd/_a_bwd
-    def _a_fwd(self, wav, length):
-        raise NotImplementedError
-
-    def _a_bwd(self, dy, wav_full_len):
-        raise NotImplementedError
-
-    def _fused_mask_tensor(self, device, length):
+    def _on_load(self, wav, length):
+        """The extra operands (`mask=`, `thr=` of SpectralFrontend.guidance) with which the fused mel kernels apply A themselves while they
+        load wav[:, :length], or None: A has to be materialised by `apply`."""
         return None
 
-    fused_mask = False        # True: A(.) is a per-sample mask (or the identity) that the fused mel kernels apply on load / on store
+    def _mel_ref(self, measurement):
+        return self._ref(measurement, "mel_spectrogram", lambda m: self._mel(m.reshape(m.shape[0], -1)).clone())
 
-    def guidance(self, wav, length, measurement, supervised_space, noise=None, step=None, generator=None):
-        if supervised_space == "mel_spectrogram" and self.fused_mask and self.frontend.fused(length):
-            # mask, noise, STFT, mel, dB, L2 and the whole backward in two launches; y = A(wav) is never materialised
-            lo, hi = self.clamp if self.clamp else (_NEG, _POS)
-            ref = self._ref(measurement, "mel_spectrogram", lambda m: self._mel(m.reshape(m.shape[0], -1)).clone())
+    def _mel_guidance(self, wav, length, measurement, noise, step, generator, **apply_kw):
+        lo, hi = self.clamp
+        operands = self._on_load(wav, length)
+        if operands is not None and self.frontend.fused(length):
+            # A, noise, STFT, mel, dB, L2 and the whole backward in two launches; y = A(wav) is never materialised
+            ref = self._mel_ref(measurement)
             z, sigma = self._step_noise((wav.shape[0], length), wav.device, noise, step, generator)
-            return self.frontend.guidance(wav, length, ref, self._fused_mask_tensor(wav.device, length), True, True, lo, hi, noise=z,
-                                          sigma=sigma)
-        y = self._a_fwd(wav, length)                                         # (B, L') contiguous fp32
-        z, sigma = self._step_noise(y.shape, y.device, noise, step, generator)
-        if z is not None:
-            y = ops.hip.noise_add(y, z, sigma)                               # the noiser on the materialised A(wav); A^T is unchanged
-        if supervised_space == "mel_spectrogram" and self.frontend.fused(y.shape[1]):
-            lo, hi = self.clamp if self.clamp else (_NEG, _POS)
-            ref = self._ref(measurement, "mel_spectrogram", lambda m: self._mel(m.reshape(m.shape[0], -1)).clone())
-            loss, dy = self.frontend.guidance(y, y.shape[1], ref, None, True, True, lo, hi)
-            return loss, self._a_bwd(dy, wav.shape[1])
-        if supervised_space == "wav_form":
-            m32 = self._ref(measurement, "wav_form", lambda m: m.reshape(m.shape[0], -1).contiguous())
-            loss, dy = l2_loss(m32, y)
-        elif supervised_space == "mel_spectrogram":
-            ref = self._ref(measurement, "mel_spectrogram", lambda m: self._mel(m.reshape(m.shape[0], -1)).clone())
-            pred = self._mel(y)
-            loss, dmel = l2_loss(ref, pred)
-            dy = self.frontend.transform_bwd(dmel)
+            return self.frontend.guidance(wav, length, ref, lo=lo, hi=hi, noise=z, sigma=sigma, **operands)
+        y, adjoint = self._noisy_apply(wav, length, noise, step, generator, **apply_kw)      # y (B, L') contiguous fp32
+        ref = self._mel_ref(measurement)
+        if self.frontend.fused(y.shape[1]):
+            loss, dy = self.frontend.guidance(y, y.shape[1], ref, lo=lo, hi=hi)
         else:
-            raise ValueError("supervised_space should be either 'wav_form' or 'mel_spectrogram")
-        return loss, self._a_bwd(dy, wav.shape[1])
+            loss, dmel = l2_loss(ref, self._mel(y))
+            dy = self.frontend.transform_bwd(dmel)
+        return loss, adjoint(dy, wav.shape[1])
 
 
 def longest_zero_run(mask):
@@ -293,30 +319,30 @@ def longest_zero_run(mask):
     return int(starts[i]), int(ends[i])
 
 
-class IdentityOperator(_MelOperator):                     # operator.py:17-45
-    fused_mask = True
+def _masked(x, length, mask):
+    """-> (x[:, :length] * mask, adjoint) for a (1, length) mask on x's device, or None for the plain crop: a per-sample mask is its own
+    transpose, and the transpose of the crop is the zero-pad."""
+    def adjoint(dy, full):
+        return ops.ctypes_hip.mask_mul(dy, mask, dy.shape[1], full)
+    return ops.ctypes_hip.mask_mul(x, mask, length, length), adjoint
 
+
+class IdentityOperator(_MelOperator):                     # operator.py:17-45
     def __init__(self, sample_rate):
         self._init_mel(sample_rate)
 
     def forward(self, data, **kwargs):
         return data
 
-    def _a_fwd(self, wav, length):
-        return ops.ctypes_hip.mask_mul(wav, None, length, length)
+    def apply(self, x, length, **kw):
+        return _masked(x, length, None)
 
-    def _a_bwd(self, dy, full):
-        return ops.ctypes_hip.mask_mul(dy, None, dy.shape[1], full)
+    def _on_load(self, wav, length):
+        return {}
 
 
 class MusicInpaintingOperator(_MelOperator):              # operator.py:48-133
-    clamp = None                                            # transform = wav2mel without clamp (operator.py:123-124)
-    fused_mask = True
-
-    def _fused_mask_tensor(self, device, length):
-        if length != self.mask.shape[1]:
-            raise ValueError(f"mask length {self.mask.shape[1]} != waveform length {length}")
-        return self._mask_on(device)
+    clamp = (_NEG, _POS)                                    # transform = wav2mel without clamp (operator.py:123-124)
 
     def __init__(self, audio_length_in_s, sample_rate, mask_type, start_inpainting_s, end_inpainting_s, mask_percentage,
                  mask_duration_s, interval_s, noiser=None):
@@ -362,19 +388,16 @@ class MusicInpaintingOperator(_MelOperator):              # operator.py:48-133
             self._mask_dev = self.mask.to(device=device, dtype=torch.float32).contiguous()
         return self._mask_dev
 
-    def forward(self, data, **kwargs):
-        data = _as_f32_cuda(data)
-        n = data.shape[1]
-        y = ops.ctypes_hip.mask_mul(data, self._mask_on(data.device), n, n)
-        return self.noiser(y) if self.noiser is not None else y
-
-    def _a_fwd(self, wav, length):
+    def _mask_for(self, device, length):
         if length != self.mask.shape[1]:
             raise ValueError(f"mask length {self.mask.shape[1]} != waveform length {length}")
-        return ops.ctypes_hip.mask_mul(wav, self._mask_on(wav.device), length, length)
+        return self._mask_on(device)
 
-    def _a_bwd(self, dy, full):
-        return ops.ctypes_hip.mask_mul(dy, self._mask_on(dy.device), dy.shape[1], full)
+    def apply(self, x, length, **kw):
+        return _masked(x, length, self._mask_for(x.device, length))
+
+    def _on_load(self, wav, length):
+        return dict(mask=self._mask_for(wav.device, length))
 
 
 class DeclippingOperator(_MelOperator):
@@ -397,14 +420,7 @@ class DeclippingOperator(_MelOperator):
         self.per_clip = torch.as_tensor(threshold).dim() > 0      # a scalar broadcasts over any batch
         self.threshold = thr.clone()                          # host copy: (1,) broadcast over the batch, or (B,)
         self._thr_dev = None
-        self._frontend = None
-        self._wav = None
-
-    @property
-    def frontend(self):
-        if self._frontend is None:
-            self._frontend = SpectralFrontend(self.sample_rate, 1024, 160, 64, "hann")
-        return self._frontend
+        self._init_mel(sample_rate, lazy=True)
 
     def _check_batch(self, batch):
         n = self.threshold.numel()
@@ -420,29 +436,18 @@ class DeclippingOperator(_MelOperator):
         return t
 
     def forward(self, data, **kwargs):
-        self._check_batch(data.shape[0])
-        data = _as_f32_cuda(data)
-        y = ops.hip.clip_fwd(data, self.thresholds(data.shape[0], data.device), data.shape[1])
-        return self.noiser(y) if self.noiser is not None else y
+        self._check_batch(data.shape[0])                      # before the tensor has to be on the GPU
+        return super().forward(data, **kwargs)
 
-    def _a_fwd(self, wav, length):
-        self._wav = wav                                       # the Jacobian of a nonlinear A needs the point it is taken at
-        return ops.hip.clip_fwd(wav, self.thresholds(wav.shape[0], wav.device), int(length))
+    def apply(self, x, length, **kw):
+        thr = self.thresholds(x.shape[0], x.device)
 
-    def _a_bwd(self, dy, full):
-        wav, self._wav = self._wav, None
-        return ops.hip.clip_bwd(dy.contiguous(), wav, self.thresholds(wav.shape[0], wav.device), int(full))
+        def adjoint(dy, full):                                # the Jacobian of a nonlinear A is taken at x
+            return ops.hip.clip_bwd(dy.contiguous(), x, thr, int(full))
+        return ops.hip.clip_fwd(x, thr, int(length)), adjoint
 
-    def guidance(self, wav, length, measurement, supervised_space, noise=None, step=None, generator=None):
-        self._check_batch(wav.shape[0])
-        if supervised_space == "mel_spectrogram" and self.frontend.fused(length):
-            # clip, noise, STFT, mel, dB, L2 and the whole backward in two launches; A(wav) is never materialised
-            lo, hi = self.clamp
-            ref = self._ref(measurement, "mel_spectrogram", lambda m: self._mel(m.reshape(m.shape[0], -1)).clone())
-            z, sigma = self._step_noise((wav.shape[0], length), wav.device, noise, step, generator)
-            return self.frontend.guidance(wav, length, ref, None, True, True, lo, hi, noise=z, sigma=sigma,
-                                          thr=self.thresholds(wav.shape[0], wav.device))
-        return super().guidance(wav, length, measurement, supervised_space, noise=noise, step=step, generator=generator)
+    def _on_load(self, wav, length):
+        return dict(thr=self.thresholds(wav.shape[0], wav.device))
 
     def project(self, wav, measurement):
         """The conventional output stage of declipping -> (B, L), L the measurement's length: reliable samples (|y| < c) are the
@@ -471,26 +476,17 @@ class PhaseRetrievalOperator(BaseOperator):               # operator.py:136-171
     def transform(self, magnitude):                        # clamp(MelScale(mag), -80, 80) -> (B, n_mels, T)
         return self.frontend.melscale(_as_f32_cuda(magnitude), -80.0, 80.0).transpose(1, 2)
 
-    def forward(self, data, **kwargs):
-        data = _as_f32_cuda(data)
-        mag = self.frontend.stft_mag(data, data.shape[-1])
-        return self.noiser(mag) if self.noiser is not None else mag
+    def apply(self, x, length, **kw):
+        """y = |STFT(x)| (B, bins, frames): the `wav_form` loss is taken on the raw magnitudes (scheduling_dps.py:199-201).  The transpose
+        divides by the clean |X| that the front end's state keeps until its next transform."""
+        def adjoint(dmag, full):
+            dwav = torch.zeros(x.shape[0], full, dtype=torch.float32, device=x.device)
+            self.frontend.stft_mag_bwd(dmag, length, dwav)
+            return dwav
+        return self.frontend.stft_mag(x, length), adjoint
 
-    def guidance(self, wav, length, measurement, supervised_space, noise=None, step=None, generator=None):
+    def _mel_guidance(self, wav, length, measurement, noise, step, generator, **apply_kw):
         bins_frames = (wav.shape[0], self.frontend.bins, self.frontend.frames(length))
-        if supervised_space == "wav_form":          # scheduling_dps.py:199-201: || y - |STFT(wav)| ||_2 on the raw magnitudes
-            mag = self.frontend.stft_mag(wav, length)
-            B = mag.shape[0]
-            z, sigma = self._step_noise(bins_frames, wav.device, noise, step, generator)
-            if z is not None:                       # the backward divides by the clean |X| kept in the front end's state
-                mag = ops.hip.noise_add(mag, z, sigma)
-            m32 = self._ref(measurement, "wav_form", lambda m: m.reshape(m.shape[0], -1).contiguous())
-            loss, dmag = l2_loss(m32, mag.reshape(B, -1))
-            dwav = torch.zeros(wav.shape[0], wav.shape[1], dtype=torch.float32, device=wav.device)
-            self.frontend.stft_mag_bwd(dmag.reshape(mag.shape), length, dwav)
-            return loss, dwav
-        if supervised_space != "mel_spectrogram":
-            raise ValueError("supervised_space should be either 'wav_form' or 'mel_spectrogram")
         ref = self._ref(measurement, "mel_spectrogram", lambda m: self.frontend.melscale(m, -80.0, 80.0))
         z, sigma = self._step_noise(bins_frames, wav.device, noise, step, generator)
         if self.frontend.fused(length):
@@ -534,17 +530,12 @@ class SuperResolutionOperator(_MelOperator):              # operator.py:174-205
     def _out_len(self, n):
         return int(math.ceil(self.new * n / self.orig))
 
-    def forward(self, data, **kwargs):
-        data = _as_f32_cuda(data)
-        y = _fir_fwd(data, data.shape[1], self._k(data.device), self._out_len(data.shape[1]), self.orig, self.new, self.width)
-        return self.noiser(y) if self.noiser is not None else y
+    def apply(self, x, length, **kw):
+        k = self._k(x.device)
 
-    def _a_fwd(self, wav, length):
-        self._in_len = length
-        return _fir_fwd(wav, length, self._k(wav.device), self._out_len(length), self.orig, self.new, self.width)
-
-    def _a_bwd(self, dy, full):
-        return _fir_bwd(dy, self._k(dy.device), None, self._in_len, full, self.orig, self.new, self.width)
+        def adjoint(dy, full):
+            return _fir_bwd(dy, k, None, length, full, self.orig, self.new, self.width)
+        return _fir_fwd(x, length, k, self._out_len(length), self.orig, self.new, self.width), adjoint
 
 
 class MusicDereverberationOperator(_MelOperator):         # operator.py:208-250
@@ -575,25 +566,14 @@ class MusicDereverberationOperator(_MelOperator):         # operator.py:208-250
         h = ir.reshape(1, -1).to(device=device, dtype=torch.float32).contiguous()
         return h, torch.flip(h, dims=[1]).contiguous()
 
-    def forward(self, data, ir=None, **kwargs):
-        data = _as_f32_cuda(data)
-        h, _ = self._get_ir(data.device, ir)
+    def apply(self, x, length, ir=None, **kw):
+        """ir: the response of this call; None draws one (or takes the kept one of `fixed_ir`) before anything else happens."""
+        h, h_rev = self._get_ir(x.device, ir)
         n = h.shape[1]
-        y = _fir_fwd(data, data.shape[1], h, data.shape[1] + 2 * (n // 2) - n + 1, 1, 1, n // 2)
-        return self.noiser(y) if self.noiser is not None else y
 
-    def guidance(self, wav, length, measurement, supervised_space, ir=None, noise=None, step=None, generator=None):
-        self._h, self._hrev = self._get_ir(wav.device, ir)
-        return super().guidance(wav, length, measurement, supervised_space, noise=noise, step=step, generator=generator)
-
-    def _a_fwd(self, wav, length):
-        n = self._h.shape[1]
-        self._in_len = length
-        return _fir_fwd(wav, length, self._h, length + 2 * (n // 2) - n + 1, 1, 1, n // 2)
-
-    def _a_bwd(self, dy, full):
-        n = self._h.shape[1]
-        return _fir_bwd(dy, self._h, self._hrev, self._in_len, full, 1, 1, n // 2)
+        def adjoint(dy, full):
+            return _fir_bwd(dy, h, h_rev, length, full, 1, 1, n // 2)
+        return _fir_fwd(x, length, h, length + 2 * (n // 2) - n + 1, 1, 1, n // 2), adjoint
 
 
 class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 (unrunnable in the reference: run.py:213-214)
@@ -639,9 +619,8 @@ class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 
             self._kern = self._kern_host.to(device)
         return self._kern
 
-    def forward(self, data, **kwargs):
-        data = _as_f32_cuda(data)
-        return self.noiser(data) if self.noiser is not None else data
+    def apply(self, x, length, **kw):
+        return _masked(x, length, None)
 
     def _features(self, wav, length):
         """(B, >= length) fp32 cuda -> CLAP input features (B, 1, frames, 64) (HIP) and the 48 kHz length."""
@@ -675,19 +654,11 @@ class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 
         feats, _ = self._features(audio.contiguous(), audio.shape[-1])
         return self._gram(feats)
 
-    def guidance(self, wav, length, measurement, supervised_space, noise=None, step=None, generator=None):
-        y = wav                                                                    # forward = noiser(identity) on the vocoder output
+    def _mel_guidance(self, wav, length, measurement, noise, step, generator, **apply_kw):
+        y = wav                                                    # the resampler reads wav[:, :length] in place: only the noise needs the crop
         z, sigma = self._step_noise((wav.shape[0], length), wav.device, noise, step, generator)
         if z is not None:
-            y = ops.hip.noise_add(ops.ctypes_hip.mask_mul(wav, None, length, length), z, sigma)
-        if supervised_space == "wav_form":
-            m32 = self._ref(measurement, "wav_form", lambda m: m.reshape(m.shape[0], -1).contiguous())
-            loss, dy = l2_loss(m32, y if z is not None else ops.ctypes_hip.mask_mul(wav, None, length, length))
-            d = torch.zeros(wav.shape[0], wav.shape[1], dtype=torch.float32, device=wav.device)
-            d[:, :length] = dy
-            return loss, d
-        if supervised_space != "mel_spectrogram":
-            raise ValueError("supervised_space should be either 'wav_form' or 'mel_spectrogram")
+            y = ops.hip.noise_add(self.apply(wav, length)[0], z, sigma)
         ref = self._ref(measurement, "mel_spectrogram", lambda m: self.transform(m.reshape(m.shape[0], -1)))
         feats, n48 = self._features(y, length)
         if self.engine is not None:

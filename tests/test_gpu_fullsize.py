@@ -33,13 +33,11 @@ def test_fullsize_operator_adjoint(task):
     x = torch.randn(B, L_FULL, generator=g).cuda()
     if task.startswith("super"):
         op = P.SuperResolutionOperator(SR, int(task[-1]), noiser=None)
-        y = op._a_fwd(x, L_FULL)
     else:
         op = P.MusicDereverberationOperator(ir_length=5000, decay_factor=0.99, noiser=None, fixed_ir=True)
-        op._h, op._hrev = op._get_ir(x.device)
-        y = op._a_fwd(x, L_FULL)
+    y, adj = op.apply(x, L_FULL)
     w = torch.randn(y.shape, generator=g).cuda()
-    xt = op._a_bwd(w.contiguous(), L_FULL)
+    xt = adj(w.contiguous(), L_FULL)
     lhs, rhs = _dot(y, w), _dot(x, xt)
     assert abs(lhs - rhs) <= 2e-4 * max(abs(lhs), abs(rhs), math.sqrt(y.numel())), (lhs, rhs)
 

@@ -144,11 +144,12 @@ def test_operators_with_noise_match_their_composed_path():
             d2 = torch.zeros_like(wav)
             fe.stft_mag_bwd(dmag, L, d2)
         else:
-            y = (op._a_fwd(wav, L) + sigma * z).contiguous()
+            y, adj = op.apply(wav, L)
+            y = (y + sigma * z).contiguous()
             ref = op._mel(meas).clone()
             pred = op._mel(y)
             l2, dmel = l2_loss(ref, pred)
-            d2 = op._a_bwd(fe.transform_bwd(dmel), full)
+            d2 = adj(fe.transform_bwd(dmel), full)
         rl, rg = float(((loss - l2).abs() / l2).max()), _rel(dwav, d2)
         print(f"\n  {type(op).__name__}: loss {rl:.2e} grad {rg:.2e}")
         assert rl < 1e-5, type(op).__name__

@@ -150,11 +150,11 @@ def test_operators_take_the_fused_route_and_match_their_composed_path():
             d2 = torch.zeros_like(wav)
             fe.transform_bwd(dmel, d2)
         else:
-            y = op._a_fwd(wav, L)
+            y, adj = op.apply(wav, L)
             ref = op._mel(meas).clone()
             pred = op._mel(y)
             l2, dmel = l2_loss(ref, pred)
-            d2 = op._a_bwd(fe.transform_bwd(dmel), full)
+            d2 = adj(fe.transform_bwd(dmel), full)
         assert float(((loss - l2).abs() / l2).max()) < 1e-5, type(op).__name__
         assert _rel(dwav, d2) < 1e-5, (type(op).__name__, _rel(dwav, d2))
         assert math.isfinite(float(dwav.abs().max()))

@@ -67,12 +67,12 @@ def test_measurement_ops_equal_facade(monkeypatch):
     loss2, dp2 = h.l2norm(mel, (mel2 * 0.9).contiguous(), 1.0)
     assert torch.equal(loss, loss2) and torch.equal(dp, dp2)
     sr = P.SuperResolutionOperator(16000, 4, noiser=None)
-    y = sr._a_fwd(wav, L_)
+    y, adj = sr.apply(wav, L_)
     y2 = h.resample_fwd(wav, sr._k(wav.device), L_, y.shape[1], sr.orig, sr.new, sr.width)
     assert torch.equal(y, y2)
-    assert torch.equal(sr._a_bwd(y.contiguous(), wav.shape[1]), h.resample_bwd(y.contiguous(), sr._k(wav.device), None, L_, wav.shape[1], sr.orig, sr.new, sr.width))
+    assert torch.equal(adj(y.contiguous(), wav.shape[1]), h.resample_bwd(y.contiguous(), sr._k(wav.device), None, L_, wav.shape[1], sr.orig, sr.new, sr.width))
     inp = P.MusicInpaintingOperator(1, L_, "box", 0.25, 0.5, 0.3, 0.1, 0.2, noiser=None)
-    assert torch.equal(inp._a_fwd(wav, L_), h.mask_mul(wav, inp._mask_on(wav.device), L_, L_))
+    assert torch.equal(inp.apply(wav, L_)[0], h.mask_mul(wav, inp._mask_on(wav.device), L_, L_))
 
 
 def test_network_ops_through_handles_equal_engines(monkeypatch):
