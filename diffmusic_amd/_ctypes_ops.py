@@ -107,6 +107,67 @@ def resample_bwd(dy, h, h_rev, Lin, Lfull, orig, new_, off):
     return d
 
 
+def _rows(name, x, L):
+    if not x.is_cuda:
+        raise RuntimeError(f"{name}: tensors must be on the GPU (no CPU fallback)")
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] >= L >= 1, (name, x.shape, L)
+
+
+def _taps(name, h, B):
+    assert h.is_cuda and h.dtype == torch.float32 and h.dim() == 2 and h.is_contiguous() and h.shape[0] == B and h.shape[1] >= 1, \
+        (name, h.shape, B)
+    return h.shape[1]
+
+
+def fir_clip_fwd(x, h, Lin):
+    """x (B, >= Lin) with any row stride, h (B, n) one response per clip -> (B, Lin + 2 * (n // 2) - n + 1): conv1d with padding n // 2."""
+    _rows("fir_clip_fwd", x, Lin)
+    B = x.shape[0]
+    n = _taps("fir_clip_fwd", h, B)
+    Lout = Lin + 2 * (n // 2) - n + 1
+    y = torch.empty(B, Lout, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_fir_clip_fwd(_p(x), x.stride(0), _p(h), _p(y), Lout, B, Lin, Lout, n, _stream()), "fir_clip_fwd")
+    return y
+
+
+def fir_clip_bwd(dy, h, h_rev, Lin, Lfull):
+    """The transpose in x: dy (B, Lout) contiguous, h and its time reverse h_rev (B, n) -> (B, Lfull), zeros past Lin."""
+    _rows("fir_clip_bwd", dy, dy.shape[1] if dy.dim() == 2 else 1)
+    B, Lout = dy.shape
+    n = _taps("fir_clip_bwd", h, B)
+    assert _taps("fir_clip_bwd", h_rev, B) == n and dy.is_contiguous() and Lfull >= Lin >= 1 and Lout == Lin + 2 * (n // 2) - n + 1, \
+        (dy.shape, h.shape, h_rev.shape, Lin, Lfull)
+    d = torch.zeros(B, Lfull, dtype=torch.float32, device=dy.device)
+    _lib.check(_lib.lib().dmx_fir_clip_bwd(_p(dy), Lout, _p(h), _p(h_rev), _p(d), Lfull, B, Lin, Lout, n, _stream()), "fir_clip_bwd")
+    return d
+
+
+def fir_wgrad(dy, x, L, taps):
+    """The gradient in h as partial sums: dy (B, Lout) contiguous, x (B, >= L) with any row stride -> (B, segments, taps); row s holds the
+    terms of outputs [4096 s, 4096 (s + 1)), dh = the sum over s (`ir_update` adds the rows in order)."""
+    _rows("fir_wgrad", x, L)
+    _rows("fir_wgrad", dy, dy.shape[1] if dy.dim() == 2 else 1)
+    B, Lout = dy.shape
+    assert x.shape[0] == B and dy.is_contiguous() and taps >= 1 and Lout == L + 2 * (taps // 2) - taps + 1, (dy.shape, x.shape, L, taps)
+    lib = _lib.lib()
+    segments = lib.dmx_fir_wgrad_workspace_floats(B, Lout, taps) // (B * taps)
+    part = torch.empty(B, segments, taps, dtype=torch.float32, device=dy.device)
+    _lib.check(lib.dmx_fir_wgrad(_p(dy), Lout, _p(x), x.stride(0), _p(part), part.numel(), B, L, Lout, taps, _stream()), "fir_wgrad")
+    return part
+
+
+def ir_update(partials, h, h_rev, m, v, k, lr, beta1, beta2, eps):
+    """One Adam step on the responses from the partial rows of `fir_wgrad`, then h <- h' / max|h'| per clip; h, h_rev, m, v (B, n) are
+    updated IN PLACE, k is the 1-based count of updates since the last reset.  A clip whose gradient or step is not finite keeps its
+    state."""
+    assert partials.is_cuda and partials.dtype == torch.float32 and partials.dim() == 3 and partials.is_contiguous(), partials.shape
+    B, segments, n = partials.shape
+    for t in (h, h_rev, m, v):
+        assert _taps("ir_update", t, B) == n, (t.shape, partials.shape)
+    _lib.check(_lib.lib().dmx_ir_update(_p(partials), segments, _p(h), _p(h_rev), _p(m), _p(v), B, n, float(lr), float(beta1), float(beta2),
+                                        float(eps), int(k), _stream()), "ir_update")
+
+
 def logmel_fwd(audio, wav, state, L, power2, to_db, lo, hi, *, out=None, n_mels=64):
     """out: caller-owned (B, frames, n_mels) result; n_mels: the handle's mel width (the op allocates 64 columns)."""
     lib = _lib.lib()

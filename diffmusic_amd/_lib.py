@@ -168,6 +168,11 @@ _SIGS = {
     "dmx_grad_normalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_void_p]),
     "dmx_fir_fwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 7 + [C.c_void_p]),
     "dmx_fir_bwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 7 + [C.c_void_p]),
+    "dmx_fir_clip_fwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 4 + [C.c_void_p]),
+    "dmx_fir_clip_bwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 4 + [C.c_void_p]),
+    "dmx_fir_wgrad_workspace_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dmx_fir_wgrad": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_size_t] + [C.c_int] * 4 + [C.c_void_p]),
+    "dmx_ir_update": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_void_p]),
     "dmx_sched_pred_x0": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_void_p]),
     "dmx_sched_pred_x0_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_int, C.c_float, C.c_void_p]),
     "dmx_sched_step_ex": (C.c_int, [C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_int] + [C.c_float] * 5 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
@@ -180,7 +185,8 @@ _SIGS = {
 # loads, so their presence is checked by name
 ADDED_IN_V4 = ("dmx_vae_encoder_create", "dmx_vae_encoder_workspace_bytes", "dmx_vae_encode_fwd", "dmx_latent_init",
                "dmx_track_stitch_fwd", "dmx_track_stitch_bwd", "dmx_audio_guidance_fwd_shaped", "dmx_audio_guidance_bwd_shaped",
-               "dmx_clip_fwd", "dmx_clip_bwd", "dmx_declip_project", "dmx_hifigan_fwd_dead", "dmx_hifigan_dead_plan", "dmx_conv_dead_rows")
+               "dmx_clip_fwd", "dmx_clip_bwd", "dmx_declip_project", "dmx_hifigan_fwd_dead", "dmx_hifigan_dead_plan", "dmx_conv_dead_rows",
+               "dmx_fir_clip_fwd", "dmx_fir_clip_bwd", "dmx_fir_wgrad", "dmx_fir_wgrad_workspace_floats", "dmx_ir_update")
 
 _lib = None
 
@@ -190,7 +196,7 @@ def check_symbols(h, path=LIB_PATH):
     for name in ADDED_IN_V4:
         if not hasattr(h, name):
             raise RuntimeError(f"{path} reports ABI version {ABI_VERSION} but does not export `{name}` (a build from before the VAE "
-                               "encoder / track-mode / declipping entry points): rebuild it (python -m diffmusic_amd.build --force)")
+                               "encoder / track-mode / declipping / blind-dereverberation entry points): rebuild it (python -m diffmusic_amd.build --force)")
 
 
 def lib():

@@ -30,6 +30,11 @@
 #pragma weak dmx_declip_project
 #pragma weak dmx_hifigan_fwd_dead
 #pragma weak dmx_hifigan_dead_plan
+#pragma weak dmx_fir_clip_fwd
+#pragma weak dmx_fir_clip_bwd
+#pragma weak dmx_fir_wgrad
+#pragma weak dmx_fir_wgrad_workspace_floats
+#pragma weak dmx_ir_update
 
 namespace {
 
@@ -144,6 +149,61 @@ at::Tensor resample_bwd(const at::Tensor& dy, const at::Tensor& h, const std::op
   ok(dmx_fir_bwd(dy.data_ptr<float>(), dy.size(1), h.data_ptr<float>(), fp(h_rev), d.data_ptr<float>(), Lfull, (int)dy.size(0), (int)Lin,
                  (int)dy.size(1), (int)h.size(-1), (int)orig, (int)new_, (int)off, cur_stream()), "resample_bwd");
   return d;
+}
+// blind dereverberation (include/diffmusic_hip.h dmx_fir_clip_{fwd,bwd} / dmx_fir_wgrad / dmx_ir_update): one response per clip
+inline void wave_rows(const at::Tensor& x, int64_t L, const char* name) {
+  TORCH_CHECK(x.is_cuda(), name, " must be a GPU tensor (the diffmusic_hip ops have no CPU fallback)");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.dim() == 2 && x.stride(1) == 1 && L >= 1 && x.size(1) >= L, name, " must be (B, >= L) fp32");
+}
+inline int64_t taps_of(const at::Tensor& h, const at::Tensor& like, int64_t B, const char* name) {
+  f32_cuda(h, name);
+  TORCH_CHECK(h.dim() == 2 && h.size(0) == B && h.size(1) >= 1 && h.device() == like.device(), name, " must hold one response per clip, (B, taps)");
+  return h.size(1);
+}
+at::Tensor fir_clip_fwd(const at::Tensor& x, const at::Tensor& h, int64_t Lin) {
+  wave_rows(x, Lin, "x");
+  DMX_DEVICE_OF(x);
+  const int64_t B = x.size(0), n = taps_of(h, x, B, "h"), Lout = Lin + 2 * (n / 2) - n + 1;
+  at::Tensor y = at::empty({B, Lout}, x.options());
+  ok(dmx_fir_clip_fwd(x.data_ptr<float>(), x.stride(0), h.data_ptr<float>(), y.data_ptr<float>(), Lout, (int)B, (int)Lin, (int)Lout, (int)n,
+                      cur_stream()), "fir_clip_fwd");
+  return y;
+}
+at::Tensor fir_clip_bwd(const at::Tensor& dy, const at::Tensor& h, const at::Tensor& h_rev, int64_t Lin, int64_t Lfull) {
+  f32_cuda(dy, "dy");
+  TORCH_CHECK(dy.dim() == 2, "dy must be (B, Lout)");
+  DMX_DEVICE_OF(dy);
+  const int64_t B = dy.size(0), Lout = dy.size(1), n = taps_of(h, dy, B, "h");
+  TORCH_CHECK(taps_of(h_rev, dy, B, "h_rev") == n && Lfull >= Lin && Lin >= 1 && Lout == Lin + 2 * (n / 2) - n + 1,
+              "fir_clip_bwd: h_rev like h, Lout = Lin + 2 * (taps / 2) - taps + 1, Lfull >= Lin");
+  at::Tensor d = at::zeros({B, Lfull}, dy.options());
+  ok(dmx_fir_clip_bwd(dy.data_ptr<float>(), Lout, h.data_ptr<float>(), h_rev.data_ptr<float>(), d.data_ptr<float>(), Lfull, (int)B, (int)Lin,
+                      (int)Lout, (int)n, cur_stream()), "fir_clip_bwd");
+  return d;
+}
+at::Tensor fir_wgrad(const at::Tensor& dy, const at::Tensor& x, int64_t L, int64_t taps) {
+  f32_cuda(dy, "dy");
+  wave_rows(x, L, "x");
+  TORCH_CHECK(dy.dim() == 2 && x.size(0) == dy.size(0) && x.device() == dy.device() && taps >= 1 &&
+              dy.size(1) == L + 2 * (taps / 2) - taps + 1, "fir_wgrad: dy (B, Lout) with Lout = L + 2 * (taps / 2) - taps + 1, x (B, >= L)");
+  DMX_DEVICE_OF(dy);
+  const int64_t B = dy.size(0), Lout = dy.size(1);
+  const int64_t segments = (int64_t)(dmx_fir_wgrad_workspace_floats((int)B, (int)Lout, (int)taps) / (size_t)(B * taps));
+  at::Tensor part = at::empty({B, segments, taps}, dy.options());
+  ok(dmx_fir_wgrad(dy.data_ptr<float>(), Lout, x.data_ptr<float>(), x.stride(0), part.data_ptr<float>(), (size_t)part.numel(), (int)B, (int)L,
+                   (int)Lout, (int)taps, cur_stream()), "fir_wgrad");
+  return part;
+}
+void ir_update(const at::Tensor& partials, at::Tensor h, at::Tensor h_rev, at::Tensor m, at::Tensor v, int64_t k, double lr, double beta1,
+               double beta2, double eps) {
+  f32_cuda(partials, "partials");
+  TORCH_CHECK(partials.dim() == 3, "partials must be (B, segments, taps)");
+  DMX_DEVICE_OF(partials);
+  const int64_t B = partials.size(0), n = partials.size(2);
+  TORCH_CHECK(taps_of(h, partials, B, "h") == n && taps_of(h_rev, partials, B, "h_rev") == n && taps_of(m, partials, B, "m") == n &&
+              taps_of(v, partials, B, "v") == n, "ir_update: h, h_rev, m and v must be (B, taps) like the partial rows");
+  ok(dmx_ir_update(partials.data_ptr<float>(), (int)partials.size(1), h.data_ptr<float>(), h_rev.data_ptr<float>(), m.data_ptr<float>(),
+                   v.data_ptr<float>(), (int)B, (int)n, lr, beta1, beta2, eps, (int)k, cur_stream()), "ir_update");
 }
 at::Tensor logmel_fwd(int64_t audio, const at::Tensor& wav, const at::Tensor& state, int64_t L, bool power2, bool to_db, double lo, double hi) {
   dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
@@ -527,10 +587,15 @@ TORCH_LIBRARY(diffmusic_hip, m) {
                                                          {"dmx_clip_bwd", (const void*)&dmx_clip_bwd},
                                                          {"dmx_declip_project", (const void*)&dmx_declip_project},
                                                          {"dmx_hifigan_fwd_dead", (const void*)&dmx_hifigan_fwd_dead},
-                                                         {"dmx_hifigan_dead_plan", (const void*)&dmx_hifigan_dead_plan}};
+                                                         {"dmx_hifigan_dead_plan", (const void*)&dmx_hifigan_dead_plan},
+                                                         {"dmx_fir_clip_fwd", (const void*)&dmx_fir_clip_fwd},
+                                                         {"dmx_fir_clip_bwd", (const void*)&dmx_fir_clip_bwd},
+                                                         {"dmx_fir_wgrad", (const void*)&dmx_fir_wgrad},
+                                                         {"dmx_fir_wgrad_workspace_floats", (const void*)&dmx_fir_wgrad_workspace_floats},
+                                                         {"dmx_ir_update", (const void*)&dmx_ir_update}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
-                  "` (a build from before the VAE encoder / track-mode / declipping entry points): rebuild with `python -m diffmusic_amd.build --force`");
+                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation entry points): rebuild with `python -m diffmusic_amd.build --force`");
   }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
@@ -546,6 +611,11 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("l2norm(Tensor ref, Tensor pred, float gscale) -> (Tensor, Tensor)", &l2norm);
   m.def("resample_fwd(Tensor x, Tensor h, int Lin, int Lout, int orig, int new_, int off) -> Tensor", &resample_fwd);
   m.def("resample_bwd(Tensor dy, Tensor h, Tensor? h_rev, int Lin, int Lfull, int orig, int new_, int off) -> Tensor", &resample_bwd);
+  m.def("fir_clip_fwd(Tensor x, Tensor h, int Lin) -> Tensor", &fir_clip_fwd);
+  m.def("fir_clip_bwd(Tensor dy, Tensor h, Tensor h_rev, int Lin, int Lfull) -> Tensor", &fir_clip_bwd);
+  m.def("fir_wgrad(Tensor dy, Tensor x, int L, int taps) -> Tensor", &fir_wgrad);
+  m.def("ir_update(Tensor partials, Tensor(a!) h, Tensor(b!) h_rev, Tensor(c!) m, Tensor(d!) v, int k, float lr, float beta1, float beta2, "
+        "float eps) -> ()", &ir_update);
   m.def("logmel_fwd(int audio, Tensor wav, Tensor(a!) state, int L, bool power2, bool to_db, float lo, float hi) -> Tensor", &logmel_fwd);
   m.def("logmel_bwd(int audio, Tensor dmel, Tensor state, int L, bool power2, bool to_db, float lo, float hi) -> Tensor", &logmel_bwd);
   m.def("mel_guidance(int audio, Tensor wav, Tensor? mask, Tensor ref, Tensor(a!) state, int L, int Lfull, bool power2, bool to_db, float lo, float hi, "

@@ -1,6 +1,7 @@
 from .noise import GaussianNoise, PoissonNoise
 from .operator import (BaseOperator, IdentityOperator, MusicInpaintingOperator, PhaseRetrievalOperator,
-                       SuperResolutionOperator, MusicDereverberationOperator, StyleGuidanceOperator, DeclippingOperator)
+                       SuperResolutionOperator, MusicDereverberationOperator, StyleGuidanceOperator, DeclippingOperator,
+                       BlindDereverberationOperator)
 from .dsp import threshold_for_sdr
 from .track import TrackLayout, TrackOperator, seconds_for_samples
 

@@ -226,7 +226,22 @@ class BaseOperator:
             raise ValueError("supervised_space should be either 'wav_form' or 'mel_spectrogram")
         y, adjoint = self._noisy_apply(wav, length, noise, step, generator, **apply_kw)
         loss, dy = l2_loss(self._ref(measurement, "wav_form", _flat_rows), y.reshape(y.shape[0], -1))
-        return loss, adjoint(dy.reshape(y.shape), wav.shape[1])
+        return loss, self._pull_back(adjoint, wav, length, dy.reshape(y.shape), apply_kw)
+
+    def _pull_back(self, adjoint, x, length, dy, apply_kw):
+        """dwav = adjoint(dy), then the operator's look at the step's cotangent: the gradient is the one of the operator `apply` used."""
+        dwav = adjoint(dy, x.shape[1])
+        self.after_cotangent(x, length, dy, **apply_kw)
+        return dwav
+
+    def after_cotangent(self, x, length, dy, **apply_kw):
+        """Called by `guidance` once per step with dy = d loss / d y at y = A(x[:, :length]) (+ noise), y materialised by `apply`, after
+        the gradient w.r.t. x has been taken: an operator with parameters of its own updates them here (BlindDereverberationOperator).
+        Not called where A rides inside the fused mel kernels (`_on_load`): no dy exists there.  No-op by default."""
+
+    def restart(self):
+        """The pipeline restarts the current trajectory from fresh latents (NaN-retry): state that a trajectory builds up goes back to
+        its start.  Nothing by default -- the cached reference and the noiser's stream are kept, as they always were."""
 
     def _mel_guidance(self, wav, length, measurement, noise, step, generator, **apply_kw):
         raise NotImplementedError
@@ -305,7 +320,7 @@ class _MelOperator(BaseOperator):
         else:
             loss, dmel = l2_loss(ref, self._mel(y))
             dy = self.frontend.transform_bwd(dmel)
-        return loss, adjoint(dy, wav.shape[1])
+        return loss, self._pull_back(adjoint, wav, length, dy, apply_kw)
 
 
 def longest_zero_run(mask):
@@ -574,6 +589,136 @@ class MusicDereverberationOperator(_MelOperator):         # operator.py:208-250
         def adjoint(dy, full):
             return _fir_bwd(dy, h, h_rev, length, full, 1, 1, n // 2)
         return _fir_fwd(x, length, h, length + 2 * (n // 2) - n + 1, 1, 1, n // 2), adjoint
+
+
+MAX_BLIND_TAPS = 8192     # csrc/fir_blind.hip: the update is one workgroup per clip
+
+
+class BlindDereverberationOperator(_MelOperator):
+    """Dereverberation with an UNKNOWN impulse response (extension; the reference's operator always knows the response it drew): every
+    clip b has its own estimate h[b] (`ir_estimate`, (B, n) fp32 on the GPU), fitted inside the guided loop in the alternating scheme of
+    blind DPS / BUDDy.  One `guidance` call computes the loss and the gradient w.r.t. the audio with the current estimate h_k, then takes
+    one Adam step on the taps from the same cotangent dy, g[b, t] = sum_o dy[b, o] x[b, o + t - n // 2], followed by the peak normalisation
+    h <- h' / max|h'| of `generate_impulse_response`, which pins the scale ambiguity between h and x.  All of it is HIP: `fir_clip_fwd` /
+    `fir_clip_bwd` (one response per clip), `fir_wgrad` and `ir_update` (csrc/fir_blind.hip); a clip whose g or step is not finite keeps its
+    estimate and moments, and the pipeline's NaN-retry restarts the trajectory (`restart`).
+
+    forward(data, ir=None) makes the measurement with the TRUE response: `ir` ((n,) or (B, n)), or one draw of
+    `generate_impulse_response(ir_length, decay_factor)` per clip on the first call, kept as `true_ir` (B, n).
+    init: "impulse" (h[n // 2] = 1: A = identity) or an (n,) / (B, n) tensor, peak-normalised per row.
+    reset_cache() (every `set_timesteps`) and restart() (NaN-retry) put the estimate back to `init`, zero the moments and set k = 0, so two
+    identical pipeline calls give the same bits.  `guidance(..., update_ir=False)` (through the scheduler: `op_kwargs=dict(update_ir=False)`)
+    freezes the estimate; `ir=` pins the response of one call and never updates.
+
+    Norms: the update uses the cotangent of the PER-CLIP loss ||.||_2 that `guidance` returns.  A scheduler with per_clip_norm=False rescales
+    dwav afterwards by loss_b / ||loss||; for the taps that would only scale g per clip, which Adam's step ignores up to `adam_eps`.
+
+    The state is indexed by batch position, so the pipelines refuse `lanes > 1` and `shard=True` with this operator; inside a TrackOperator
+    the batch is the one track.  k, the count of updates since the last reset, is kept on the host and shared by the clips: a clip whose
+    update was refused is at most a restart away from k = 0 again."""
+
+    def __init__(self, ir_length=800, decay_factor=0.85, noiser=None, lr=0.05, betas=(0.9, 0.999), adam_eps=1e-8, init="impulse"):
+        n = int(ir_length)
+        if n < 1 or n > MAX_BLIND_TAPS:
+            raise ValueError(f"ir_length = {ir_length!r}: 1 .. {MAX_BLIND_TAPS} taps (the update kernel holds one clip per workgroup)")
+        if not (isinstance(lr, (int, float)) and math.isfinite(lr) and lr > 0):
+            raise ValueError(f"lr = {lr!r}: a positive number")
+        if len(betas) != 2 or not all(isinstance(b, (int, float)) and 0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"betas = {betas!r}: two numbers in [0, 1)")
+        if not (isinstance(adam_eps, (int, float)) and math.isfinite(adam_eps) and adam_eps >= 0):
+            raise ValueError(f"adam_eps = {adam_eps!r}: a non-negative number")
+        self.ir_length, self.decay_factor, self.noiser = n, decay_factor, noiser
+        self.lr, self.betas, self.adam_eps = float(lr), (float(betas[0]), float(betas[1])), float(adam_eps)
+        if isinstance(init, str):
+            if init != "impulse":
+                raise ValueError(f"init = {init!r}: 'impulse' or an (n,) / (B, n) tensor")
+            start = torch.zeros(1, n)
+            start[0, n // 2] = 1.0
+        else:
+            start = torch.as_tensor(init, dtype=torch.float32).detach().cpu()
+            if start.dim() not in (1, 2) or start.shape[-1] != n or start.numel() == 0:
+                raise ValueError(f"init has shape {tuple(start.shape)}: ({n},) or (B, {n}) for ir_length = {n}")
+            start = start.reshape(-1, n).clone()
+            peak = start.abs().amax(dim=1, keepdim=True)
+            if not bool(torch.isfinite(start).all()) or not bool((peak > 0).all()):
+                raise ValueError("init: finite responses with a non-zero peak")
+            start = start / peak
+        self._start = start                                   # host, (1, n) for every clip or (B, n)
+        self.true_ir = None
+        self._h = self._h_rev = self._m = self._v = None
+        self.k = 0
+        self._init_mel(16000, lazy=True)
+
+    generate_impulse_response = MusicDereverberationOperator.generate_impulse_response
+
+    # ---- the estimate and its optimiser state
+    def _rows(self, ir, batch, what):
+        """(n,) / (1, n) / (batch, n) -> host (batch, n) fp32."""
+        ir = torch.as_tensor(ir).detach().to(device="cpu", dtype=torch.float32).reshape(-1, self.ir_length)
+        if ir.shape[0] not in (1, batch):
+            raise ValueError(f"{what} holds {ir.shape[0]} response(s), the batch has {batch} clip(s)")
+        return ir.expand(batch, self.ir_length)
+
+    def _state(self, batch, device):
+        """The (batch, n) estimate with its reverse and Adam moments on `device`; made from `init` on first use and when the batch changes."""
+        if self._h is None or self._h.shape[0] != batch or self._h.device != device:
+            self._h = self._rows(self._start, batch, "init").to(device).contiguous()
+            self._h_rev = torch.flip(self._h, dims=[1]).contiguous()
+            self._m, self._v = torch.zeros_like(self._h), torch.zeros_like(self._h)
+            self.k = 0
+        return self._h, self._h_rev
+
+    @property
+    def ir_estimate(self):
+        """(B, n) fp32 on the GPU, updated in place by every guided step; None before the first call has fixed the batch."""
+        return self._h
+
+    def _to_start(self):
+        if self._h is not None:
+            self._h.copy_(self._rows(self._start, self._h.shape[0], "init"))
+            self._h_rev.copy_(torch.flip(self._h, dims=[1]))
+            self._m.zero_()
+            self._v.zero_()
+        self.k = 0
+
+    def reset_cache(self):
+        super().reset_cache()
+        self._to_start()
+
+    def restart(self):
+        self._to_start()
+
+    # ---- A
+    def forward(self, data, ir=None, **kwargs):
+        B = data.shape[0]
+        if ir is None:
+            if self.true_ir is None or self.true_ir.shape[0] != B:
+                self.true_ir = torch.cat([self.generate_impulse_response(self.ir_length, self.decay_factor) for _ in range(B)], dim=0)
+            ir = self.true_ir
+        else:
+            ir = self.true_ir = self._rows(ir, B, "ir").clone()
+        return super().forward(data, ir=ir, **kwargs)
+
+    def apply(self, x, length, ir=None, update_ir=True, **kw):
+        """ir: the response(s) of this call instead of the estimate ((n,) or (B, n)); the estimate is then neither used nor updated."""
+        B, n = x.shape[0], self.ir_length
+        if ir is None:
+            h, h_rev = self._state(B, x.device)
+        else:
+            h = self._rows(ir, B, "ir").to(x.device).contiguous()
+            h_rev = torch.flip(h, dims=[1]).contiguous()
+
+        def adjoint(dy, full):
+            return ops.hip.fir_clip_bwd(dy.contiguous(), h, h_rev, int(length), int(full))
+        return ops.hip.fir_clip_fwd(x, h, int(length)), adjoint
+
+    def after_cotangent(self, x, length, dy, ir=None, update_ir=True, **kw):
+        """h_k -> h_{k+1}: the weight gradient of this step's cotangent and one Adam + projection step, two launches, no host sync."""
+        if ir is not None or not update_ir:
+            return
+        part = ops.hip.fir_wgrad(dy.contiguous(), x, int(length), self.ir_length)
+        self.k += 1
+        ops.hip.ir_update(part, self._h, self._h_rev, self._m, self._v, self.k, self.lr, self.betas[0], self.betas[1], self.adam_eps)
 
 
 class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 (unrunnable in the reference: run.py:213-214)

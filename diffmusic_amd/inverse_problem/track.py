@@ -111,6 +111,11 @@ class TrackOperator:
     def reset_cache(self):
         self.inner.reset_cache()
 
+    def restart(self):
+        restart = getattr(self.inner, "restart", None)
+        if restart is not None:
+            restart()
+
     def stitch(self, wav):
         """(W, >= L) fp32 windows on the GPU, any row stride -> the (1, T) track."""
         lay = self.layout

@@ -21,6 +21,7 @@ from ..torch_utils import randn_tensor
 from ..profiling import stage
 from ..inverse_problem.noise import step_sigma
 from ..inverse_problem.track import TrackOperator
+from ..inverse_problem.operator import BlindDereverberationOperator
 from .. import parallel
 
 
@@ -227,6 +228,7 @@ class MusicLDMPipeline:
         track = self.scheduler.operator if isinstance(self.scheduler.operator, TrackOperator) else None
         if track is not None:
             self._check_track(track, B_all, original_waveform_length, shard, group, lanes)
+        self._check_positional_state(shard, group, lanes)
         init = self._check_init(init_audio, init_mel, strength, init_posterior, latents, B_all, height, original_waveform_length)
         if init is not None:
             timesteps = self.scheduler.timesteps_for_strength(strength)      # the tail of the full list; num_inference_steps stays N
@@ -331,6 +333,7 @@ class MusicLDMPipeline:
                                 if bad:                                                             # NaN-retry (:741-756)
                                     retry -= 1
                                     self.nan_restarts += 1
+                                    self._restart_operator()
                                     latents = fresh_latents()
                                     is_done = False
                                     pe = init_pe
@@ -427,7 +430,28 @@ class MusicLDMPipeline:
                 return torch.cat([ln.latents for ln in lanes], dim=0)
             retry -= 1                                                                  # NaN-retry (:741-756): all clips restart
             self.nan_restarts += 1
+            self._restart_operator()
             latents = fresh_latents()
+
+    def _restart_operator(self):
+        """NaN-retry: the trajectory begins again, and so does whatever the operator fits along it (`BaseOperator.restart`)."""
+        restart = getattr(self.scheduler.operator, "restart", None)
+        if restart is not None:
+            restart()
+
+    def _check_positional_state(self, shard, group, lanes):
+        """An operator that keeps per-clip state by batch position (the blind dereverberation's response estimates) sees every clip of the
+        call in one batch, in call order: no clip lanes, no clip sharding."""
+        op = self.scheduler.operator
+        op = getattr(op, "inner", op)                            # the inner operator of a track
+        if not isinstance(op, BlindDereverberationOperator):
+            return
+        if int(self.lanes if lanes is None else lanes) > 1:
+            raise ValueError("BlindDereverberationOperator cannot run as clip lanes (lanes > 1): its response estimates are indexed by batch "
+                             "position, and a lane sees only its own clips")
+        if shard or group is not None:
+            raise ValueError("BlindDereverberationOperator cannot be sharded over ranks (shard / group): its response estimates are indexed "
+                             "by batch position, and a rank sees only its own clips")
 
     # ---- track mode -------------------------------------------------------------------------
     def _check_track(self, track, B_all, length, shard, group, lanes):

@@ -9,6 +9,7 @@ embedding file (`--prompt_embeds x.npy`, (B, 512) CLAP text embeddings for Music
     python examples/run_inverse_problem.py -c mpgd -t super_resolution --num_inference_steps 20      # synthetic clips + weights
     python examples/run_inverse_problem.py -c dps -t music_dereverberation --wav take.wav --track_overlap_s 1.28   # a long take, whole
     python examples/run_inverse_problem.py -c dps -t music_declipping --clip_sdr_db 3 --init measurement --strength 0.5 --project
+    python examples/run_inverse_problem.py -c dps -t music_blind_dereverberation --wav room.wav        # the response is fitted, not given
 
 `--track_overlap_s S` restores a recording longer than the model window whole (track mode, inverse_problem/track.py): the first `--wav`
 (or a synthetic 2.5-window signal) becomes overlapping windows under one loss and one stitched file is written.  Without the flag a
@@ -31,7 +32,8 @@ from diffmusic_amd.metrics import LogSpectralDistance, MeanSquaredError         
 from diffmusic_amd.pipelines import get_pipeline                                    # noqa: E402
 from diffmusic_amd.schedulers import get_scheduler                                  # noqa: E402
 
-TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation", "music_declipping")
+TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation", "music_declipping",
+         "music_blind_dereverberation")
 
 
 def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None):
@@ -54,6 +56,8 @@ def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=
         op = P.PhaseRetrievalOperator(n_fft=d.n_fft, hop_length=d.hop_length, win_length=d.win_length, noiser=noiser)
     elif task == "music_dereverberation":
         op = P.MusicDereverberationOperator(ir_length=5000, decay_factor=0.99, noiser=noiser)
+    elif task == "music_blind_dereverberation":
+        op = P.BlindDereverberationOperator(ir_length=5000, decay_factor=0.99, noiser=noiser, lr=cfg.inverse_problem.get("lr") or 0.05)
     elif task == "music_declipping":
         if clip_threshold is None:
             raise ValueError("music_declipping needs clip_threshold (e.g. inverse_problem.threshold_for_sdr(clean, sdr_db))")
@@ -134,9 +138,9 @@ def parse_args(argv=None):
 def main(argv=None):
     args = parse_args(argv)
     overrides = [f"data={args.data}", f"model={args.model}"]
-    if args.task == "music_declipping":
-        overrides.append("inverse_problem=music_declipping")
-    elif args.project:
+    if args.task in ("music_declipping", "music_blind_dereverberation"):
+        overrides.append(f"inverse_problem={args.task}")
+    if args.project and args.task != "music_declipping":
         raise SystemExit("--project is the output stage of -t music_declipping")
     cfg = compose(args.config_name, overrides=overrides)
     if args.model != "musicldm":
@@ -197,6 +201,11 @@ def main(argv=None):
         scipy.io.wavfile.write(out / "wav_recon" / f"{name}.wav", sr, audio[i])
         mel = to_mel.transform(torch.from_numpy(audio[i:i + 1]).to(device))[0].T      # (frames, 64)
         pipe.save_mel_spectrogram(mel[: length * 100 // sr], out / "mel_recon" / f"{name}.png")
+    blind = op.inner if layout is not None else op
+    if isinstance(blind, P.BlindDereverberationOperator) and blind.true_ir is not None and blind.ir_estimate is not None:
+        est, true = blind.ir_estimate.cpu(), blind.true_ir                         # the synthetic measurement knows its response
+        err = torch.linalg.vector_norm(est - true, dim=1) / torch.linalg.vector_norm(true, dim=1)
+        print("impulse response estimate, relative error per clip: " + " ".join(f"{e:.3f}" for e in err.tolist()))
     ref = gt.cpu().numpy()
     print(f"wrote {B} clip(s) to {out}; LSD {LogSpectralDistance().score(ref, audio[:, :length]):.4f}  MSE {MeanSquaredError().score(ref, audio[:, :length]):.6f}")
 

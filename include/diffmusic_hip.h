@@ -30,8 +30,9 @@ extern "C" {
 /* Additive changes do not bump the version: dmx_audio_guidance_{fwd,bwd}_ex and dmx_noise_add (measurement noise inside the guided
  * step), dmx_vae_encoder_* / dmx_vae_encode_fwd / dmx_latent_init / dmx_conv2d_raw (VAE encoder, warm-started sampling),
  * dmx_track_stitch_fwd / dmx_track_stitch_bwd (track mode: overlapping windows as one sample) and dmx_audio_guidance_{fwd,bwd}_shaped /
- * dmx_clip_fwd / dmx_clip_bwd / dmx_declip_project (declipping: a hard clip inside and beside the guidance pair) are new symbols, and every
- * earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * dmx_clip_fwd / dmx_clip_bwd / dmx_declip_project (declipping: a hard clip inside and beside the guidance pair) and dmx_fir_clip_fwd /
+ * dmx_fir_clip_bwd / dmx_fir_wgrad / dmx_fir_wgrad_workspace_floats / dmx_ir_update (blind dereverberation: one fitted response per clip)
+ * are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
  * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
@@ -297,6 +298,31 @@ int dmx_fir_fwd(const float* in, long long in_stride, const float* h, float* out
 /* transpose of dmx_fir_fwd (gradient w.r.t. `in`); h_rev = time-reversed taps, required only for the dense 1:1 case */
 int dmx_fir_bwd(const float* dout, long long dout_stride, const float* h, const float* h_rev, float* din, long long din_stride, int batch,
                 int Lin, int Lout, int taps, int orig, int new_, int off, void* stream);
+/* Blind dereverberation (csrc/fir.hip, csrc/fir_blind.hip; no counterpart in the reference, whose dereverberation always knows its
+ * response): one response per clip, h (batch, taps), fitted inside the guided loop.  Geometry of the dense 1:1 dmx_fir_fwd: off = taps / 2,
+ * Lout = L + 2 * (taps / 2) - taps + 1, x zero outside [0, L); taps may exceed L.
+ *   fir_clip_fwd  y[b, o]  = sum_t h[b, t] * x[b, o + t - off]                     = dmx_fir_fwd of clip b alone with h[b], bit for bit
+ *   fir_clip_bwd  dx[b, i] = sum_t h[b, t] * dy[b, i - t + off], i < Lin           = dmx_fir_bwd of clip b alone; h_rev[b, t] = h[b, taps-1-t]
+ *   fir_wgrad     dh[b, t] = sum_o dy[b, o] * x[b, o + t - off]                    as `segments` partial rows, partials (batch, segments, taps):
+ *                 row s holds the terms o in [4096 s, 4096 (s + 1)), dh is their sum over s.  segments = ceil(Lout / 4096) =
+ *                 dmx_fir_wgrad_workspace_floats(batch, Lout, taps) / (batch * taps).  No atomics: the same bits on every call, and a
+ *                 clip's rows depend neither on the batch nor on its place in it.
+ *   ir_update     g = sum_s partials[b, s, :] in increasing s, then per clip, k the 1-based count of updates since the last reset:
+ *                   m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) g g;  h' = h - lr (m / (1 - b1^k)) / (sqrt(v / (1 - b2^k)) + eps)
+ *                   h <- h' / max_t |h'|  (the peak normalisation of generate_impulse_response), h_rev <- its reverse
+ *                 in fp32, the scalars 1 - b, 1 - b^k taken in double on the host and rounded once.  A clip with a non-finite element in g
+ *                 or h', or with max|h'| = 0, keeps its h, h_rev, m and v untouched (decided on the device).  One workgroup per clip:
+ *                 taps <= 8192, DMX_ERR_SHAPE above.
+ * One launch each. */
+int dmx_fir_clip_fwd(const float* in, long long in_stride, const float* h, float* out, long long out_stride, int batch, int Lin, int Lout,
+                     int taps, void* stream);
+int dmx_fir_clip_bwd(const float* dout, long long dout_stride, const float* h, const float* h_rev, float* din, long long din_stride, int batch,
+                     int Lin, int Lout, int taps, void* stream);
+size_t dmx_fir_wgrad_workspace_floats(int batch, int Lout, int taps);
+int dmx_fir_wgrad(const float* dy, long long dy_stride, const float* x, long long x_stride, float* partials, size_t partial_floats, int batch,
+                  int L, int Lout, int taps, void* stream);
+int dmx_ir_update(const float* partials, int segments, float* h, float* h_rev, float* m, float* v, int batch, int taps, double lr, double beta1,
+                  double beta2, double eps, int k, void* stream);
 
 /* ---- scheduler arithmetic (diffmusic/schedulers/scheduling_{ddim,dps,mpgd,dsg,diffmusic}.py step bodies) -------------- */
 #define DMX_SCHED_DDIM 0
