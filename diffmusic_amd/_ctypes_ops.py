@@ -320,6 +320,56 @@ def track_stitch_bwd(dtrack, starts, L, R, Lfull):
     return dwav
 
 
+def _gains_arg(what, gains, K):
+    """gains (None = all ones, else K numbers) -> the host float array the launchers take (NULL for None)."""
+    if gains is None:
+        return None
+    if len(gains) != K:
+        raise RuntimeError(f"{what}: {len(gains)} gains for {K} stems")
+    return (C.c_float * len(gains))(*[float(g) for g in gains])
+
+
+def _stem_rows(what, x, rows, L):
+    if not x.is_cuda:
+        raise RuntimeError(f"{what}: a GPU tensor is required (no CPU fallback)")
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or x.shape[0] != rows or x.shape[1] < L:
+        raise RuntimeError(f"{what}: expected ({rows}, >= {L}) fp32 with unit column stride, got {tuple(x.shape)} {x.dtype}")
+
+
+def stem_mix_fwd(wav, gains, K, G, L):
+    """wav (K * G, >= L), rows stem-major, any row stride -> the (G, L) mixtures ((g_0 x_0 + g_1 x_1) + ...); gains None = all ones."""
+    _stem_rows("stem_mix_fwd", wav, K * G, L)
+    arr = _gains_arg("stem_mix_fwd", gains, K)
+    mix = torch.empty(max(G, 0), max(L, 0), dtype=torch.float32, device=wav.device)
+    _lib.check(_lib.lib().dmx_stem_mix_fwd(_p(wav), wav.stride(0), _p(mix), arr, K, G, L, _stream()), "stem_mix_fwd")
+    return mix
+
+
+def stem_mix_bwd(dmix, gains, K, Lfull):
+    """The transpose: dmix (G, L) contiguous -> (K * G, Lfull), row k * G + w = g_k * dmix[w], zeros past L."""
+    if not dmix.is_cuda:
+        raise RuntimeError("stem_mix_bwd: dmix must be a GPU tensor (no CPU fallback)")
+    if dmix.dtype != torch.float32 or dmix.dim() != 2 or not dmix.is_contiguous():
+        raise RuntimeError(f"stem_mix_bwd: dmix must be contiguous (G, L) fp32, got {tuple(dmix.shape)} {dmix.dtype}")
+    G, L = dmix.shape
+    arr = _gains_arg("stem_mix_bwd", gains, K)
+    dwav = torch.empty(max(K, 0) * G, max(Lfull, 0), dtype=torch.float32, device=dmix.device)
+    _lib.check(_lib.lib().dmx_stem_mix_bwd(_p(dmix), _p(dwav), Lfull, arr, K, G, L, Lfull, _stream()), "stem_mix_bwd")
+    return dwav
+
+
+def stem_project(x, y, gains, L):
+    """x (K, >= L) stems, y (1, L) mixture -> (K, L): x_k + c_k (y - mix(x)), c_k = g_k / sum g^2; afterwards the stems sum to y."""
+    K = x.shape[0] if x.dim() == 2 else 0
+    _stem_rows("stem_project", x, K, L)
+    if not y.is_cuda or y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != L or y.device != x.device:
+        raise RuntimeError(f"stem_project: y must be a contiguous (1, {L}) fp32 tensor on x's device, got {tuple(y.shape)}")
+    arr = _gains_arg("stem_project", gains, K)
+    out = torch.empty(K, L, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_stem_project(_p(x), x.stride(0), _p(y), _p(out), arr, K, L, _stream()), "stem_project")
+    return out
+
+
 def stft_mag_fwd(audio, wav, state, L):
     lib = _lib.lib()
     B = wav.shape[0]

@@ -165,6 +165,9 @@ _SIGS = {
     "dmx_l2_loss": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_void_p]),
     "dmx_track_stitch_fwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.POINTER(C.c_int)] + [C.c_int] * 4 + [C.c_void_p]),
     "dmx_track_stitch_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_int)] + [C.c_int] * 5 + [C.c_void_p]),
+    "dmx_stem_mix_fwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.POINTER(C.c_float)] + [C.c_int] * 3 + [C.c_void_p]),
+    "dmx_stem_mix_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_float)] + [C.c_int] * 4 + [C.c_void_p]),
+    "dmx_stem_project": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p]),
     "dmx_grad_normalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_void_p]),
     "dmx_fir_fwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 7 + [C.c_void_p]),
     "dmx_fir_bwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong] + [C.c_int] * 7 + [C.c_void_p]),
@@ -186,7 +189,8 @@ _SIGS = {
 ADDED_IN_V4 = ("dmx_vae_encoder_create", "dmx_vae_encoder_workspace_bytes", "dmx_vae_encode_fwd", "dmx_latent_init",
                "dmx_track_stitch_fwd", "dmx_track_stitch_bwd", "dmx_audio_guidance_fwd_shaped", "dmx_audio_guidance_bwd_shaped",
                "dmx_clip_fwd", "dmx_clip_bwd", "dmx_declip_project", "dmx_hifigan_fwd_dead", "dmx_hifigan_dead_plan", "dmx_conv_dead_rows",
-               "dmx_fir_clip_fwd", "dmx_fir_clip_bwd", "dmx_fir_wgrad", "dmx_fir_wgrad_workspace_floats", "dmx_ir_update")
+               "dmx_fir_clip_fwd", "dmx_fir_clip_bwd", "dmx_fir_wgrad", "dmx_fir_wgrad_workspace_floats", "dmx_ir_update",
+               "dmx_stem_mix_fwd", "dmx_stem_mix_bwd", "dmx_stem_project")
 
 _lib = None
 
@@ -196,7 +200,7 @@ def check_symbols(h, path=LIB_PATH):
     for name in ADDED_IN_V4:
         if not hasattr(h, name):
             raise RuntimeError(f"{path} reports ABI version {ABI_VERSION} but does not export `{name}` (a build from before the VAE "
-                               "encoder / track-mode / declipping / blind-dereverberation entry points): rebuild it (python -m diffmusic_amd.build --force)")
+                               "encoder / track-mode / declipping / blind-dereverberation / source-separation entry points): rebuild it (python -m diffmusic_amd.build --force)")
 
 
 def lib():

@@ -35,6 +35,9 @@
 #pragma weak dmx_fir_wgrad
 #pragma weak dmx_fir_wgrad_workspace_floats
 #pragma weak dmx_ir_update
+#pragma weak dmx_stem_mix_fwd
+#pragma weak dmx_stem_mix_bwd
+#pragma weak dmx_stem_project
 
 namespace {
 
@@ -380,6 +383,53 @@ at::Tensor track_stitch_bwd(const at::Tensor& dtrack, at::IntArrayRef starts, in
                           cur_stream()), "track_stitch_bwd");
   return dwav;
 }
+// source separation (include/diffmusic_hip.h dmx_stem_mix_{fwd,bwd} / dmx_stem_project): K stems as the batch, rows stem-major; the launchers
+// refuse what they can see (stem count, lengths, strides, gains), the wrappers what only they can (row count, gain count, devices)
+struct StemGainsArg {
+  std::vector<float> g;
+  bool given = false;
+  StemGainsArg(const std::optional<at::ArrayRef<double>>& gains, int64_t K, const char* what) {
+    if (!gains.has_value()) return;
+    TORCH_CHECK((int64_t)gains->size() == K, what, ": ", gains->size(), " gains for ", K, " stems");
+    given = true;
+    for (double v : *gains) g.push_back((float)v);
+  }
+  const float* ptr() const { return given ? g.data() : nullptr; }
+};
+inline void stem_rows_ok(const at::Tensor& x, int64_t rows, int64_t L, const char* what) {
+  TORCH_CHECK(x.is_cuda(), what, ": a GPU tensor is required (the diffmusic_hip ops have no CPU fallback)");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.dim() == 2 && x.stride(1) == 1 && x.size(0) == rows && x.size(1) >= L, what, ": expected (", rows,
+              ", >= ", L, ") fp32 with unit column stride");
+}
+at::Tensor stem_mix_fwd(const at::Tensor& wav, std::optional<at::ArrayRef<double>> gains, int64_t K, int64_t G, int64_t L) {
+  stem_rows_ok(wav, K * G, L, "stem_mix_fwd");
+  const StemGainsArg g(gains, K, "stem_mix_fwd");
+  DMX_DEVICE_OF(wav);
+  at::Tensor mix = at::empty({std::max<int64_t>(G, 0), std::max<int64_t>(L, 0)}, wav.options());
+  ok(dmx_stem_mix_fwd(wav.data_ptr<float>(), wav.stride(0), mix.data_ptr<float>(), g.ptr(), (int)K, (int)G, (int)L, cur_stream()), "stem_mix_fwd");
+  return mix;
+}
+at::Tensor stem_mix_bwd(const at::Tensor& dmix, std::optional<at::ArrayRef<double>> gains, int64_t K, int64_t Lfull) {
+  TORCH_CHECK(dmix.is_cuda(), "stem_mix_bwd: dmix must be a GPU tensor (the diffmusic_hip ops have no CPU fallback)");
+  TORCH_CHECK(dmix.scalar_type() == at::kFloat && dmix.dim() == 2 && dmix.is_contiguous(), "stem_mix_bwd: dmix must be contiguous (G, L) fp32");
+  const StemGainsArg g(gains, K, "stem_mix_bwd");
+  DMX_DEVICE_OF(dmix);
+  const int64_t G = dmix.size(0), L = dmix.size(1);
+  at::Tensor dwav = at::empty({std::max<int64_t>(K, 0) * G, std::max<int64_t>(Lfull, 0)}, dmix.options());
+  ok(dmx_stem_mix_bwd(dmix.data_ptr<float>(), dwav.data_ptr<float>(), Lfull, g.ptr(), (int)K, (int)G, (int)L, (int)Lfull, cur_stream()), "stem_mix_bwd");
+  return dwav;
+}
+at::Tensor stem_project(const at::Tensor& x, const at::Tensor& y, std::optional<at::ArrayRef<double>> gains, int64_t L) {
+  const int64_t K = x.dim() == 2 ? x.size(0) : 0;
+  stem_rows_ok(x, K, L, "stem_project");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kFloat && y.is_contiguous() && y.numel() == L && y.device() == x.device(),
+              "stem_project: y must be a contiguous (1, L) fp32 tensor on x's device");
+  const StemGainsArg g(gains, K, "stem_project");
+  DMX_DEVICE_OF(x);
+  at::Tensor out = at::empty({K, L}, x.options());
+  ok(dmx_stem_project(x.data_ptr<float>(), x.stride(0), y.data_ptr<float>(), out.data_ptr<float>(), g.ptr(), (int)K, (int)L, cur_stream()), "stem_project");
+  return out;
+}
 at::Tensor stft_mag_fwd(int64_t audio, const at::Tensor& wav, const at::Tensor& state, int64_t L) {
   dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
   TORCH_CHECK(wav.is_cuda() && wav.scalar_type() == at::kFloat && wav.dim() == 2 && wav.stride(1) == 1, "wav must be (B, >= L) fp32 on the GPU");
@@ -592,10 +642,13 @@ TORCH_LIBRARY(diffmusic_hip, m) {
                                                          {"dmx_fir_clip_bwd", (const void*)&dmx_fir_clip_bwd},
                                                          {"dmx_fir_wgrad", (const void*)&dmx_fir_wgrad},
                                                          {"dmx_fir_wgrad_workspace_floats", (const void*)&dmx_fir_wgrad_workspace_floats},
-                                                         {"dmx_ir_update", (const void*)&dmx_ir_update}};
+                                                         {"dmx_ir_update", (const void*)&dmx_ir_update},
+                                                         {"dmx_stem_mix_fwd", (const void*)&dmx_stem_mix_fwd},
+                                                         {"dmx_stem_mix_bwd", (const void*)&dmx_stem_mix_bwd},
+                                                         {"dmx_stem_project", (const void*)&dmx_stem_project}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
-                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation entry points): rebuild with `python -m diffmusic_amd.build --force`");
+                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation entry points): rebuild with `python -m diffmusic_amd.build --force`");
   }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
@@ -630,6 +683,9 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("noise_add(Tensor y, Tensor noise, float sigma) -> Tensor", &noise_add);
   m.def("track_stitch_fwd(Tensor wav, int[] starts, int L, int R, int T) -> Tensor", &track_stitch_fwd);
   m.def("track_stitch_bwd(Tensor dtrack, int[] starts, int L, int R, int Lfull) -> Tensor", &track_stitch_bwd);
+  m.def("stem_mix_fwd(Tensor wav, float[]? gains, int K, int G, int L) -> Tensor", &stem_mix_fwd);
+  m.def("stem_mix_bwd(Tensor dmix, float[]? gains, int K, int Lfull) -> Tensor", &stem_mix_bwd);
+  m.def("stem_project(Tensor x, Tensor y, float[]? gains, int L) -> Tensor", &stem_project);
   m.def("stft_mag_fwd(int audio, Tensor wav, Tensor(a!) state, int L) -> Tensor", &stft_mag_fwd);
   m.def("stft_mag_bwd(int audio, Tensor dmag, Tensor state, int L, int Lfull) -> Tensor", &stft_mag_bwd);
   m.def("melscale_fwd(int audio, Tensor mag, float lo, float hi) -> Tensor", &melscale_fwd);

@@ -4,6 +4,7 @@ from .operator import (BaseOperator, IdentityOperator, MusicInpaintingOperator, 
                        BlindDereverberationOperator)
 from .dsp import threshold_for_sdr
 from .track import TrackLayout, TrackOperator, seconds_for_samples
+from .mixture import MixtureOperator
 
 
 def get_noiser(name, sigma, stream="global"):  # reference: inverse_problem/__init__.py:4-11; `stream`: GaussianNoise's per-step stream

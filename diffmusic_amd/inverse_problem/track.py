@@ -69,6 +69,9 @@ class TrackOperator:
     guidance(wav (W, full), length, measurement, space, **kw) -> ((1,) loss, (W, full) gradient): stitch, `inner.guidance` on the
     (1, T) track with every keyword passed through (`ir=`, `noise=`, `step=`, ...), then S^T."""
 
+    # why the batch is ONE sample: a wrapper that carries this is refused per-clip norms, sharding and lanes (MixtureOperator has its own)
+    one_sample = "a TrackOperator makes the batch one sample (the windows of a track under one loss)"
+
     def __init__(self, inner, layout):
         if isinstance(inner, TrackOperator):
             raise ValueError("TrackOperator around a TrackOperator: wrap the measurement operator itself")

@@ -20,7 +20,7 @@ from ..engine import HifiGanEngine, UNetEngine, VaeDecoderEngine, VaeEncoderEngi
 from ..torch_utils import randn_tensor
 from ..profiling import stage
 from ..inverse_problem.noise import step_sigma
-from ..inverse_problem.track import TrackOperator
+from ..inverse_problem.mixture import MixtureOperator
 from ..inverse_problem.operator import BlindDereverberationOperator
 from .. import parallel
 
@@ -225,8 +225,14 @@ class MusicLDMPipeline:
         timesteps = list(self.scheduler._timesteps_host)
         nlat = self.unet.cfg["in_channels"]
         B_all = B = batch_size * num_waveforms_per_prompt
-        track = self.scheduler.operator if isinstance(self.scheduler.operator, TrackOperator) else None
-        if track is not None:
+        # an operator that makes the batch ONE sample (`one_sample`: the windows of a track, the stems of a mixture, or both nested)
+        one = self.scheduler.operator if getattr(self.scheduler.operator, "one_sample", None) else None
+        track = mixture = None
+        if isinstance(one, MixtureOperator):
+            mixture, track = one, one.track
+            self._check_mixture(mixture, B_all, original_waveform_length, shard, group, lanes)
+        elif one is not None:
+            track = one
             self._check_track(track, B_all, original_waveform_length, shard, group, lanes)
         self._check_positional_state(shard, group, lanes)
         init = self._check_init(init_audio, init_mel, strength, init_posterior, latents, B_all, height, original_waveform_length)
@@ -358,8 +364,10 @@ class MusicLDMPipeline:
                 mel = self.vae.decode(latents / self.vae.config.scaling_factor).sample                 # (B,1,H,W) fp32
                 if track is None:
                     audio = self.vocoder(mel.squeeze(1))[:, :original_waveform_length].float()     # :428-435, on the device
-                else:
+                elif mixture is None:
                     audio = track.stitch(self.vocoder(mel.squeeze(1)).float())                     # the W windows -> the (1, T) track
+                else:
+                    audio = mixture.stitch_stems(self.vocoder(mel.squeeze(1)).float())             # K x W windows -> the (K, T) stems
         else:
             audio = torch.zeros(0, original_waveform_length, dtype=torch.float32, device=device)
         if sel is not None:
@@ -443,7 +451,8 @@ class MusicLDMPipeline:
         """An operator that keeps per-clip state by batch position (the blind dereverberation's response estimates) sees every clip of the
         call in one batch, in call order: no clip lanes, no clip sharding."""
         op = self.scheduler.operator
-        op = getattr(op, "inner", op)                            # the inner operator of a track
+        while hasattr(op, "inner"):                              # the measurement operator inside a track, a mixture, or both
+            op = op.inner
         if not isinstance(op, BlindDereverberationOperator):
             return
         if int(self.lanes if lanes is None else lanes) > 1:
@@ -471,6 +480,26 @@ class MusicLDMPipeline:
         if getattr(self.scheduler, "per_clip_norm", False):
             raise ValueError("track mode needs whole-batch norms: construct the scheduler with per_clip_norm=False")
         track.check_noise_stream()
+
+    # ---- source separation ------------------------------------------------------------------
+    def _check_mixture(self, mixture, B_all, length, shard, group, lanes):
+        """Argument rules of a call whose operator is a MixtureOperator (inverse_problem/mixture.py): the batch is the K stems of one
+        mixture (K * W rows, stem-major, around a track), one sample under one loss."""
+        K, track = mixture.num_stems, mixture.track
+        if B_all != mixture.num_clips:
+            of = f"{K} stems" if track is None else f"{K} stems of {track.layout.num_windows} windows ({track.layout!r}), stem-major"
+            raise ValueError(f"source separation: the call holds {B_all} clips, but the mixture has {of}: pass one prompt embedding per "
+                             "stem" + ("" if track is None else " and window") + " (one mixture per call)")
+        if track is not None and length != track.layout.window_len:
+            raise ValueError(f"source separation: audio_length_in_s gives windows of {length} samples, but the layout's window_len is "
+                             f"{track.layout.window_len}")
+        if shard or group is not None:
+            raise ValueError("source separation cannot be sharded over ranks (shard / group): the stems are coupled in every step")
+        if int(self.lanes if lanes is None else lanes) > 1:
+            raise ValueError("source separation cannot run as clip lanes (lanes > 1): the stems are coupled in every step")
+        if getattr(self.scheduler, "per_clip_norm", False):
+            raise ValueError("source separation needs whole-batch norms: construct the scheduler with per_clip_norm=False")
+        mixture.check_noise_stream()
 
     # ---- warm start -------------------------------------------------------------------------
     def _check_init(self, init_audio, init_mel, strength, init_posterior, latents, B_all, height, length):

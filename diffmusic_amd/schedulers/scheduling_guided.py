@@ -15,7 +15,6 @@ from .. import ops
 from ..torch_utils import randn_tensor, randn_philox
 from ..profiling import stage
 from ..inverse_problem.noise import step_sigma
-from ..inverse_problem.track import TrackOperator
 from .utils import InverseProblemSchedulerOutput
 
 _MODE = dict(ddim=0, dps=1, mpgd=2, dsg=3, diffmusic=4)
@@ -202,9 +201,9 @@ class GuidedDDIMScheduler:
         if variance_noise is not None and generator is not None and eta > 0:
             raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
                              " `variance_noise` stays `None`.")
-        if self.per_clip_norm and self.mode != "ddim" and isinstance(self.operator, TrackOperator):
-            raise ValueError("a TrackOperator makes the batch one sample (the windows of a track under one loss): construct the scheduler "
-                             "with per_clip_norm=False")
+        one_sample = getattr(self.operator, "one_sample", None)          # TrackOperator, MixtureOperator: the reason, as a sentence
+        if self.per_clip_norm and self.mode != "ddim" and one_sample:
+            raise ValueError(f"{one_sample}: construct the scheduler with per_clip_norm=False")
         if not sample.is_cuda:
             raise RuntimeError("diffmusic_amd schedulers run on the GPU only (no CPU fallback)")
         if self._ptype == 1 and self.mode in ("dps", "dsg", "diffmusic"):

@@ -10,10 +10,16 @@ embedding file (`--prompt_embeds x.npy`, (B, 512) CLAP text embeddings for Music
     python examples/run_inverse_problem.py -c dps -t music_dereverberation --wav take.wav --track_overlap_s 1.28   # a long take, whole
     python examples/run_inverse_problem.py -c dps -t music_declipping --clip_sdr_db 3 --init measurement --strength 0.5 --project
     python examples/run_inverse_problem.py -c dps -t music_blind_dereverberation --wav room.wav        # the response is fitted, not given
+    python examples/run_inverse_problem.py -c dps -t music_source_separation --wav drums.wav bass.wav --gains 1 0.5 --project
+    python examples/run_inverse_problem.py -c dps -t music_source_separation --mixture song.wav --stems 4 --track_overlap_s 1.28
 
 `--track_overlap_s S` restores a recording longer than the model window whole (track mode, inverse_problem/track.py): the first `--wav`
 (or a synthetic 2.5-window signal) becomes overlapping windows under one loss and one stitched file is written.  Without the flag a
 long `--wav` is cropped to the window as before.
+
+`-t music_source_separation` restores K stems from their mixture under one loss (inverse_problem/mixture.py), one prompt embedding per
+stem: `--wav` names the stems whose gain-weighted sum (`--gains`) is the measurement (SI-SDR per stem is printed), `--mixture mix.wav
+--stems K` separates a real mixture.  One file per stem is written; `--project` makes the stems sum to the mixture exactly.
 """
 import argparse
 import math
@@ -28,12 +34,13 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from diffmusic_amd.config import compose                                            # noqa: E402
 from diffmusic_amd import inverse_problem as P                                      # noqa: E402
-from diffmusic_amd.metrics import LogSpectralDistance, MeanSquaredError             # noqa: E402
+from diffmusic_amd.metrics import LogSpectralDistance, MeanSquaredError, ScaleInvariantSDR   # noqa: E402
 from diffmusic_amd.pipelines import get_pipeline                                    # noqa: E402
 from diffmusic_amd.schedulers import get_scheduler                                  # noqa: E402
 
 TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation", "music_declipping",
-         "music_blind_dereverberation")
+         "music_blind_dereverberation", "music_source_separation")
+SEPARATION = "music_source_separation"
 
 
 def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None):
@@ -131,18 +138,111 @@ def parse_args(argv=None):
                     help="music_declipping: input SDR in dB of the clipped measurement (each clip's threshold is found from it)")
     ap.add_argument("--project", action="store_true",
                     help="music_declipping: finish with the consistency projection (measurement kept where it is unclipped)")
+    ap.add_argument("--gains", type=float, nargs="*", default=None, help="music_source_separation: one mixing gain per stem (default: all 1)")
+    ap.add_argument("--mixture", default=None, help="music_source_separation: a real mixture to separate (then --stems K, no --wav)")
+    ap.add_argument("--stems", type=int, default=None, help="music_source_separation: number of stems K (default: the number of --wav, else 2)")
     ap.add_argument("--strength", type=float, default=1.0, help="share of num_inference_steps a warm start runs (diffusers' img2img rule)")
     return ap.parse_args(argv)
+
+
+def separation_stems(args):
+    """The argument rules of -t music_source_separation -> K, the number of stems; any other task refuses the separation flags."""
+    if args.task != SEPARATION:
+        for flag in ("gains", "mixture", "stems"):
+            if getattr(args, flag) is not None:
+                raise SystemExit(f"--{flag} belongs to -t {SEPARATION}")
+        return None
+    if args.mixture is not None and args.wav:
+        raise SystemExit("--mixture is a real mixture and --wav names the stems of a synthetic one: pass one of them")
+    if args.mixture is not None and args.stems is None:
+        raise SystemExit("--mixture needs --stems K: the number of stems to restore")
+    if args.stems is not None and args.wav and args.stems != len(args.wav):
+        raise SystemExit(f"--stems {args.stems} with {len(args.wav)} --wav files: every --wav is one stem")
+    K = args.stems if args.stems is not None else (len(args.wav) or 2)
+    if not 1 <= K <= 16:
+        raise SystemExit(f"{K} stems: a mixture holds 1 .. 16")
+    if args.gains is not None and len(args.gains) != K:
+        raise SystemExit(f"--gains has {len(args.gains)} values for {K} stems")
+    if args.batch != 1:
+        raise SystemExit("--batch: one mixture per call, its stems are the batch (--stems)")
+    return K
+
+
+def run_separation(args, cfg, K):
+    """-t music_source_separation: K stems from their mixture, MixtureOperator(IdentityOperator) or, with --track_overlap_s, around a track."""
+    device = torch.device("cuda")
+    pipe_kw = dict(cfg.model.pipe)
+    if args.num_inference_steps:
+        pipe_kw["num_inference_steps"] = args.num_inference_steps
+    sr, length = cfg.data.sample_rate, int(pipe_kw["audio_length_in_s"] * cfg.data.sample_rate)
+    whole = args.track_overlap_s is not None
+    if args.mixture is not None:
+        gt, y = None, load_clips([args.mixture], 1, sr, length, args.seed, whole=whole).to(device)
+    elif whole:
+        stems = [load_clips(args.wav[k:k + 1], 1, sr, length, args.seed + k, whole=True)[0] for k in range(K)]
+        gt = torch.stack([x[:min(len(x) for x in stems)] for x in stems]).to(device)              # the stems end together
+    else:
+        gt = torch.cat([load_clips(args.wav[k:k + 1], 1, sr, length, args.seed + k) for k in range(K)]).to(device)
+    T = (y if gt is None else gt).shape[1]
+    inner = P.IdentityOperator(sample_rate=sr)
+    noiser = P.get_noiser(**cfg.inverse_problem.noise)
+    if getattr(noiser, "additive_sigma", 0.0) > 0:
+        inner.noiser = noiser                                                       # drawn inside every guided step too
+    layout = P.TrackLayout(T, length, int(round(args.track_overlap_s * sr))) if whole else None
+    op = P.MixtureOperator(inner if layout is None else P.TrackOperator(inner, layout), K, args.gains)
+    G = op.groups
+    if gt is not None:
+        y = op.forward(gt)
+        y = noiser(y) if inner.noiser is not None else y
+    print(f"source separation: {K} stems, gains {args.gains or [1.0] * K}, {T / sr:.2f} s" + (f" as {G} windows per stem" if layout else ""))
+    pipe = get_pipeline(cfg.model.name).from_pretrained(args.weights, seed=args.seed).to(device)
+    pipe.scheduler = get_scheduler(cfg.name)(operator=op, **dict(cfg.model.scheduler, per_clip_norm=False))
+    if args.prompt_embeds:
+        pe = torch.from_numpy(np.load(args.prompt_embeds)).float()                  # (K, 512): one prompt per stem
+        if pe.shape[0] != K:
+            raise SystemExit(f"--prompt_embeds holds {pe.shape[0]} rows, the mixture has {K} stems")
+    else:
+        pe = torch.nn.functional.normalize(torch.randn(K, 512, generator=torch.Generator().manual_seed(args.seed)), dim=-1)
+    pe = pe.repeat_interleave(G, dim=0)                                             # stem-major rows: stem k's windows are contiguous
+    gens = [torch.Generator().manual_seed(args.seed + i) for i in range(K * G)]
+    if args.init == "measurement":
+        init = (y[:, :T] / K).repeat(K, 1)                                          # every stem starts from its share of the mixture
+        pipe_kw.update(init_audio=init if layout is None else torch.cat([layout.cut(r) for r in init]), strength=args.strength)
+    elif args.strength != 1.0:
+        raise SystemExit("--strength needs --init measurement (a cold start runs every step)")
+    audio = pipe(prompt_embeds=pe, measurement=y, eta=cfg.scheduler.eta, ip_guidance_rate=cfg.scheduler.ip_guidance_rate, generator=gens,
+                 show_progress=args.show_progress, supervised_space=args.supervised_space, **pipe_kw).audios          # (K, T)
+    if args.project:
+        audio = op.project(torch.from_numpy(audio[:, :T]), y).cpu().numpy()
+    out = Path(args.output_dir, cfg.model.name, cfg.data.name, args.config_name, args.task)
+    for d in ("wav_input", "wav_recon", "wav_label"):
+        os.makedirs(out / d, exist_ok=True)
+    scipy.io.wavfile.write(out / "wav_input" / "mixture.wav", sr, y[0].float().cpu().numpy())
+    names = [Path(args.wav[k]).stem if k < len(args.wav) else f"stem_{k}" for k in range(K)]
+    for k in range(K):
+        scipy.io.wavfile.write(out / "wav_recon" / f"{names[k]}.wav", sr, audio[k, :T])
+        if gt is not None:
+            scipy.io.wavfile.write(out / "wav_label" / f"{names[k]}.wav", sr, gt[k].cpu().numpy())
+    line = f"wrote {K} stem(s) to {out}"
+    if gt is not None:
+        db = ScaleInvariantSDR().score(gt.cpu().numpy(), audio[:, :T])
+        line += "; SI-SDR (dB) per stem: " + " ".join(f"{names[k]} {db[k]:.2f}" for k in range(K))
+    print(line)
 
 
 def main(argv=None):
     args = parse_args(argv)
     overrides = [f"data={args.data}", f"model={args.model}"]
-    if args.task in ("music_declipping", "music_blind_dereverberation"):
+    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION):
         overrides.append(f"inverse_problem={args.task}")
-    if args.project and args.task != "music_declipping":
-        raise SystemExit("--project is the output stage of -t music_declipping")
+    stems = separation_stems(args)
+    if args.project and args.task not in ("music_declipping", SEPARATION):
+        raise SystemExit("--project is the output stage of -t music_declipping and -t music_source_separation")
     cfg = compose(args.config_name, overrides=overrides)
+    if stems is not None:
+        if args.model != "musicldm":
+            raise SystemExit("this driver feeds MusicLDM's class-embedding conditioning; AudioLDM2 needs its T5 / GPT-2 states (see bench.py --workload)")
+        return run_separation(args, cfg, stems)
     if args.model != "musicldm":
         raise SystemExit("this driver feeds MusicLDM's class-embedding conditioning; AudioLDM2 needs its T5 / GPT-2 states (see bench.py --workload)")
     device = torch.device("cuda")

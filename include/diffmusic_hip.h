@@ -32,7 +32,7 @@ extern "C" {
  * dmx_track_stitch_fwd / dmx_track_stitch_bwd (track mode: overlapping windows as one sample) and dmx_audio_guidance_{fwd,bwd}_shaped /
  * dmx_clip_fwd / dmx_clip_bwd / dmx_declip_project (declipping: a hard clip inside and beside the guidance pair) and dmx_fir_clip_fwd /
  * dmx_fir_clip_bwd / dmx_fir_wgrad / dmx_fir_wgrad_workspace_floats / dmx_ir_update (blind dereverberation: one fitted response per clip)
- * are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * and dmx_stem_mix_fwd / dmx_stem_mix_bwd / dmx_stem_project (source separation: the stems of a mixture as the batch) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
  * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
@@ -287,6 +287,21 @@ int dmx_track_stitch_fwd(const float* wav, long long wav_stride, float* track, c
                          void* stream);
 int dmx_track_stitch_bwd(const float* dtrack, float* dwav, long long dwav_stride, const int* starts_host, int windows, int L, int R, int T,
                          int full, void* stream);
+/* Source separation (diffmusic_amd/inverse_problem/mixture.py, csrc/mix.hip; no counterpart in the reference): `stems` K <= 16 stems as
+ * the batch, rows stem-major (row k * groups + w is stem k of group w; groups = 1 for one window, = W for the windows of a track), gains
+ * g_k as a HOST array of `stems` finite floats, NULL = all ones.
+ *   mix_fwd  M:    mix[w, n]             = ((g_0 x[0 G + w, n] + g_1 x[1 G + w, n]) + ...)  ascending k; wav (K G, >= L), row stride
+ *                  wav_stride; mix (G, L) contiguous
+ *   mix_bwd  M^T:  dwav[k G + w, i]      = g_k dmix[w, i] for i < L, +0.0f for L <= i < full; dmix (G, L) contiguous, row stride dwav_stride
+ *   project  P:    out[k, n]             = x[k, n] + c_k (y[n] - mix(x)[n]), c_k = g_k / sum_j g_j^2 taken in double and rounded once
+ *                  (groups = 1): the minimum-norm correction after which the stems sum to the mixture y (1, L); out (K, L) contiguous
+ * Every product and sum is rounded on its own and a sum's first term is taken as it is, so a plain fp32 loop restates each bit for bit and
+ * K = 1, g = 1 copies.  One launch each, no workspace.  Refused without a launch: stems outside 1..16, groups < 1, L < 1, a row stride
+ * below its length, full < L, a non-finite gain (DMX_ERR_PARAM), more than 65535 rows in the grid. */
+int dmx_stem_mix_fwd(const float* wav, long long wav_stride, float* mix, const float* gains_host, int stems, int groups, int L, void* stream);
+int dmx_stem_mix_bwd(const float* dmix, float* dwav, long long dwav_stride, const float* gains_host, int stems, int groups, int L, int full,
+                     void* stream);
+int dmx_stem_project(const float* x, long long x_stride, const float* y, float* out, const float* gains_host, int stems, int L, void* stream);
 /* per-clip x *= target/max|x| ; inv_scale[b] = max|x|/target  (keeps the fp16 backward sweep in range) */
 int dmx_grad_normalize(float* x, float* inv_scale, int batch, long long n, float target, void* stream);
 
