@@ -115,6 +115,14 @@ _SIGS = {
     "dmx_prof_begin": (None, []),
     "dmx_prof_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dmx_flash_attn_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_void_p]),
+    "dmx_flash_attn_ld_raw": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_float, C.POINTER(C.c_int), C.c_void_p]),
+    "dmx_softmax_raw": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p]),
+    "dmx_softmax_act_raw": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_void_p]),
+    "dmx_transpose_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int] + [C.c_longlong] * 4
+                          + [C.c_void_p]),
+    "dmx_rowdot_raw": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]),
+    "dmx_layernorm_raw": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "dmx_geglu_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
     "dmx_gemm_splitk_workspace": (C.c_int, [C.c_void_p, C.c_size_t]),
     "dmx_conv_pair_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dmx_conv_pair_group_raw": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -218,6 +218,50 @@ int dmx_flash_attn_raw(const void* q, const void* k, const void* v, void* o, con
   return rc;
 }
 
+int dmx_flash_attn_ld_raw(const void* q, const void* k, const void* v, void* o, const float* colbias, int B, int Nq, int Nk, int ldq, int ldk,
+                          int ldv, int C, int heads, float scale, int* qt_out, void* stream) {
+  if (qt_out) *qt_out = 0;
+  if (B < 1 || heads < 1 || C < heads || C % heads) { dmx_set_error("flash attention: C %d is not heads %d x head_dim", C, heads); return DMX_ERR_SHAPE; }
+  const int rc = dmx_flash_attn_fwd((const act_t*)q, (const act_t*)k, (const act_t*)v, (act_t*)o, colbias, B, Nq, Nk, C, heads, scale,
+                                    ST(stream), ldq, ldk, ldv, qt_out);
+  if (rc == DMX_ERR_SHAPE)
+    dmx_set_error("flash attention: head_dim %d (multiples of 8 up to 96), Nq %d, Nk %d (>= 1) or row strides %d / %d / %d (multiples of 8) unsupported",
+                  C / heads, Nq, Nk, ldq, ldk, ldv);
+  return rc;
+}
+
+// test hooks of the row kernels around the attention (elementwise.hip): the internal launcher's parameters plus a stream
+int dmx_softmax_raw(const float* S, void* P, const float* colbias, long long rows, int N, long long lds, long long ldp, int rows_per_bias,
+                    void* stream) {
+  const int rc = dmx_softmax_fwd(S, (act_t*)P, colbias, rows, N, lds, ldp, rows_per_bias, ST(stream));
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("softmax: N %d (a multiple of 4, <= 4096), lds %lld, ldp %lld (multiples of 4) unsupported", N, lds, ldp);
+  return rc;
+}
+int dmx_softmax_act_raw(const void* S, void* P, const float* colbias, long long rows, int N, long long ldp, int rows_per_bias, void* stream) {
+  const int rc = dmx_softmax_act((const act_t*)S, (act_t*)P, colbias, rows, N, ldp, rows_per_bias, ST(stream));
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("softmax: N %d (a multiple of 4, <= 4096), ldp %lld (a multiple of 4) unsupported", N, ldp);
+  return rc;
+}
+int dmx_transpose_raw(const void* in, void* out, int R, int C, long long ldi, long long ldo, int Z, int Zi, long long sIo, long long sIi,
+                      long long sOo, long long sOi, void* stream) {
+  return dmx_transpose((const act_t*)in, (act_t*)out, R, C, ldi, ldo, Z, Zi, sIo, sIi, sOo, sOi, ST(stream));
+}
+int dmx_rowdot_raw(const void* a, const void* b, float* out, long long rows, int C, long long lda, long long ldb, void* stream) {
+  const int rc = dmx_rowdot((const act_t*)a, (const act_t*)b, out, rows, C, lda, ldb, ST(stream));
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("rowdot: C %d, lda %lld, ldb %lld must be multiples of 8", C, lda, ldb);
+  return rc;
+}
+int dmx_layernorm_raw(const void* x, void* y, const float* gamma, const float* beta, int rows, int C, float eps, void* stream) {
+  const int rc = dmx_layernorm_fwd((const act_t*)x, (act_t*)y, gamma, beta, rows, C, eps, ST(stream));
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("layernorm: C %d must be a multiple of 8", C);
+  return rc;
+}
+int dmx_geglu_raw(const void* x, void* y, long long rows, int I, void* stream) {
+  const int rc = dmx_geglu((const act_t*)x, (act_t*)y, rows, I, ST(stream));
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("geglu: I %d must be a multiple of 8", I);
+  return rc;
+}
+
 int dmx_gemm_splitk_workspace(void* ws, size_t bytes) {
   dmx_gemm_set_splitk_workspace(reinterpret_cast<float*>(ws), ws ? bytes : 0);
   return DMX_OK;

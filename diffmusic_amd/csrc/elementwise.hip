@@ -803,7 +803,8 @@ __global__ void geglu_kernel(const act_t* __restrict__ x, act_t* __restrict__ y,
   unpack8(*reinterpret_cast<const uint4*>(x + r * 2 * I + c), a);
   unpack8(*reinterpret_cast<const uint4*>(x + r * 2 * I + I + c), g);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) a[i] *= 0.5f * g[i] * (1.f + erff(g[i] * 0.70710678118654752f));
+  // gelu_erf(g) = g / 2 * erfc(-g / sqrt 2): 1 + erf cancels for negative gates (1 + erff(-3.8) keeps 3 of its 24 bits), erfc does not
+  for (int i = 0; i < 8; ++i) a[i] *= 0.5f * g[i] * erfcf(g[i] * -0.70710678118654752f);
   *reinterpret_cast<uint4*>(y + r * I + c) = pack8(a);
 }
 

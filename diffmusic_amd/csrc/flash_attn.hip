@@ -265,12 +265,13 @@ __global__ __launch_bounds__(256, (DK == 1 ? 4 : 2)) void flash_attn_fwd_kernel(
 }
 
 template <int DK, int DT>
-int launch_fa(const FaParams& P, int Z, hipStream_t st) {
+int launch_fa(const FaParams& P, int Z, hipStream_t st, int* qt_out) {
   using F = FaCfg<DK, DT>;
   static const int force_qt = [] { const char* e = getenv("DMX_FLASH_QT"); return e ? atoi(e) : 0; }();
   // at most one workgroup per CU at 128 queries each (or half-empty workgroups): halve the query tile.  Measured, 2B = 16 / 8 U-Net shapes:
   // 256 workgroups 27.7 -> 25.0 us, 96 workgroups 8.4 -> 6.6 us, but 384 workgroups 9.0 -> 11.5 us
   const bool small = force_qt ? force_qt == 1 : ((long long)cdiv(P.Nq, 128) * Z <= 256 || P.Nq <= 64);
+  if (qt_out) *qt_out = small ? 1 : 2;      // host-side report of the query-tile form taken (test hook dmx_flash_attn_ld_raw)
   if (small) {
     dim3 grid((unsigned)cdiv(P.Nq, 64), (unsigned)Z, 1);
     hipLaunchKernelGGL((flash_attn_fwd_kernel<DK, DT, 1>), grid, dim3(256), F::LDS, st, P);
@@ -287,8 +288,9 @@ bool dmx_flash_attn_ok(int dh, int C) { return dh >= 8 && dh <= 96 && (dh & 7) =
 
 // q (B, Nq, ldq), k (B, Nk, ldk), v (B, Nk, ldv) channels-last (row strides >= C; 0 = C) with `heads` heads of dh = C / heads; o (B, Nq, C).
 // colbias: optional additive key bias (B, Nk) fp32.  V is transposed by the LDS read (ds_read_b64_tr_b16): no V^T tensor, no transpose launch.
+// qt_out (host, optional): the query-tile form the launch took (1 or 2), for the tests that must keep covering both.
 int dmx_flash_attn_fwd(const act_t* q, const act_t* k, const act_t* v, act_t* o, const float* colbias, int B, int Nq, int Nk,
-                       int C, int heads, float scale, hipStream_t st, int ldq, int ldk, int ldv) {
+                       int C, int heads, float scale, hipStream_t st, int ldq, int ldk, int ldv, int* qt_out) {
   const int dh = C / heads;
   if (ldq <= 0) ldq = C;
   if (ldk <= 0) ldk = C;
@@ -301,11 +303,11 @@ int dmx_flash_attn_fwd(const act_t* q, const act_t* k, const act_t* v, act_t* o,
   const int Z = B * heads;
   const int rec = dmx_prof_open(st);
   int rc;
-  if (dh <= 32) rc = launch_fa<1, 2>(P, Z, st);
-  else if (dh <= 48) rc = launch_fa<2, 3>(P, Z, st);
-  else if (dh <= 64) rc = launch_fa<2, 4>(P, Z, st);
-  else if (dh <= 80) rc = launch_fa<3, 5>(P, Z, st);
-  else rc = launch_fa<3, 6>(P, Z, st);
+  if (dh <= 32) rc = launch_fa<1, 2>(P, Z, st, qt_out);
+  else if (dh <= 48) rc = launch_fa<2, 3>(P, Z, st, qt_out);
+  else if (dh <= 64) rc = launch_fa<2, 4>(P, Z, st, qt_out);
+  else if (dh <= 80) rc = launch_fa<3, 5>(P, Z, st, qt_out);
+  else rc = launch_fa<3, 6>(P, Z, st, qt_out);
   dmx_prof_close(rec, st, 4.0 * Z * (double)Nq * Nk * dh, 2.0 * Z * (2.0 * Nq + 2.0 * Nk) * dh, Nq, Nk, dh, 1, 0, 30);
   return rc;
 }

@@ -385,6 +385,27 @@ int dmx_gemm_raw(const void* desc, size_t desc_bytes, void* stream);
  * (B,Nk) fp32 additive key bias. */
 int dmx_flash_attn_raw(const void* q, const void* k, const void* v, void* o, const float* colbias, int B, int Nq, int Nk, int ldv,
                        int C, int heads, float scale, void* stream);
+/* test hook: the same kernel with all three row strides, as the U-Net's attention layers call it (q / k / v as slices of one fused QKV
+ * buffer: ldq = ldk = ldv = 3C; pre-projected context: ldq = C, ldk = ldv = the context buffer's row stride; 0 = C).  *qt_out (HOST
+ * pointer, may be NULL) receives the query-tile form the launch took: 1 = 64 queries per workgroup, 2 = 128; 0 when nothing was launched. */
+int dmx_flash_attn_ld_raw(const void* q, const void* k, const void* v, void* o, const float* colbias, int B, int Nq, int Nk, int ldq,
+                          int ldk, int ldv, int C, int heads, float scale, int* qt_out, void* stream);
+/* test hooks: the row kernels around the attention, each with its internal launcher's parameters.
+ * softmax: S (rows, N) fp32 (ld = lds) or 16-bit (ld = ldp, in place allowed) -> P (rows, N) 16-bit (ld = ldp, columns [N, ldp) zeroed);
+ *   colbias optional (rows / rows_per_bias, N) fp32 additive; N % 4 == 0, N <= 4096, lds % 4 == 0, ldp % 4 == 0.
+ * transpose: in[z][r][c] (R x C, row stride ldi) -> out[z][c][r] (row stride ldo) for z = zo * Zi + zi < Z with batch strides
+ *   sIo / sIi / sOo / sOi (elements).
+ * rowdot: out[r] = sum_c a[r, c] b[r, c] in fp32; C, lda, ldb multiples of 8.
+ * layernorm: y = (x - mean) * rstd * gamma + beta over rows of C (a multiple of 8) 16-bit values; gamma / beta fp32.
+ * geglu: x (rows, 2I) = [value | gate] -> y (rows, I) = value * gelu_erf(gate); I a multiple of 8. */
+int dmx_softmax_raw(const float* S, void* P, const float* colbias, long long rows, int N, long long lds, long long ldp, int rows_per_bias,
+                    void* stream);
+int dmx_softmax_act_raw(const void* S, void* P, const float* colbias, long long rows, int N, long long ldp, int rows_per_bias, void* stream);
+int dmx_transpose_raw(const void* in, void* out, int R, int C, long long ldi, long long ldo, int Z, int Zi, long long sIo, long long sIi,
+                      long long sOo, long long sOi, void* stream);
+int dmx_rowdot_raw(const void* a, const void* b, float* out, long long rows, int C, long long lda, long long ldb, void* stream);
+int dmx_layernorm_raw(const void* x, void* y, const float* gamma, const float* beta, int rows, int C, float eps, void* stream);
+int dmx_geglu_raw(const void* x, void* y, long long rows, int I, void* stream);
 /* test hook: fp32 scratch that lets small-M / deep-K launches run split-K (NULL disables it); the U-Net executor
  * installs its own */
 int dmx_gemm_splitk_workspace(void* ws, size_t bytes);

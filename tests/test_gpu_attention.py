@@ -1,4 +1,6 @@
-"""-m gpu: the fused forward attention kernel (C-ABI hook dmx_flash_attn_raw) against torch fp32 softmax attention."""
+"""-m gpu: the fused forward attention kernel (C-ABI hook dmx_flash_attn_raw) against torch fp32 softmax attention (whole-tensor
+relative L2) and, element by element, against float64 attention under the bound of tests/attention_cases.py (validated from the
+reference alone by tests/test_attention_bound_host.py)."""
 import ctypes as C
 import math
 import pytest
@@ -42,3 +44,9 @@ def test_flash_attention_forward(B, heads, dh, Nq, Nk, bias):
     ref = (torch.softmax(s, dim=-1) @ vf).transpose(1, 2).reshape(B, Nq, Cc)
     err = ((o.float() - ref).norm() / ref.norm()).item()
     assert err < 3e-3, err       # fp16 probabilities and outputs; statistics and accumulation in fp32
+    # every element against float64 attention on the same 16-bit inputs (computed on the device: the largest case has 44 M logits)
+    from tests import attention_cases as AC
+    ref64, bound = AC.reference(q, k, v, cb, heads, adt)
+    ratio = ((o.double() - ref64).abs() / bound).max().item()
+    print(f"B {B} heads {heads} dh {dh} Nq {Nq} Nk {Nk} bias {bias}: rel L2 {err:.2e}, max |o - ref| / (3u + sub) = {ratio:.3f}")
+    assert torch.isfinite(o).all() and ratio <= 1.0, ratio
