@@ -341,6 +341,8 @@ int dmx_gemm_launch(const GemmDesc& d, hipStream_t stream, int* gn_rows) {
   if (d.flags & EPI_GEGLU) {
     // fused GEGLU: bias only, 16-bit half-width output through the LDS-staged epilogue, interleaved blocks of 32 weight rows
     if ((d.flags & ~(EPI_GEGLU | EPI_BIAS | EPI_LNFOLD)) || (d.N & 31) || (d.ldc & 7) || d.ldc < d.N / 2 || d.alpha != 1.f) return DMX_ERR_SHAPE;
+    // (the tiles pick the direct epilogue, which knows no GEGLU and would store all N columns, from ANY row stride that is not 16-byte granular)
+    if ((d.ldr | d.ldx | d.ldc2) & 7) return DMX_ERR_SHAPE;
     if (!(d.osy == 1 && d.osx == 1 && d.ooy == 0 && d.oox == 0 && d.Ho == d.Hq && d.Wo == d.Wq)) return DMX_ERR_SHAPE;
   }
   if (d.flags & (EPI_MASKBITS | EPI_BITS2)) {

@@ -438,7 +438,8 @@ __device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmDesc& p, f32x4 
       }
     }
     if constexpr (GEGLU) {
-      // value * gelu_erf(gate): fragment j holds the values, j + 1 the gates of the same 16 channels (fp32, before any rounding)
+      // value * gelu_erf(gate): fragment j holds the values, j + 1 the gates of the same 16 channels (fp32, before any rounding).
+      // gelu_erf(g) = g / 2 * erfc(-g / sqrt 2) as in geglu_kernel (elementwise.hip): 1 + erf cancels for negative gates
 #pragma unroll
       for (int ii = 0; ii < IB; ++ii)
 #pragma unroll
@@ -446,7 +447,7 @@ __device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmDesc& p, f32x4 
           f32x4& a = acc[h * IB + ii][j];
           const f32x4& g = acc[h * IB + ii][j + 1];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) a[e] *= 0.5f * g[e] * (1.f + erff(g[e] * 0.70710678118654752f));
+          for (int e = 0; e < 4; ++e) a[e] *= 0.5f * g[e] * erfcf(g[e] * -0.70710678118654752f);
         }
     }
     if ((flags & EPI_RESID) && use_rpre) {
