@@ -126,6 +126,8 @@ _SIGS = {
     "dmx_gemm_splitk_workspace": (C.c_int, [C.c_void_p, C.c_size_t]),
     "dmx_conv_pair_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dmx_conv_pair_group_raw": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dmx_conv_pair_dead_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
+    "dmx_conv_pair_group_dead_raw": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.c_void_p]),
     "dmx_groupnorm_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "dmx_groupnorm_raw": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_void_p]),
     "dmx_groupnorm_part_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -210,6 +210,39 @@ int dmx_conv_pair_group_raw(int n, const void* descs_a, const void* descs_b, siz
   return rc;
 }
 
+static PairDead pair_dead_of(const int* d) { PairDead pd; pd.skip0 = d[0]; pd.skip1 = d[1]; pd.zero0 = d[2]; pd.zero1 = d[3]; return pd; }
+
+int dmx_conv_pair_dead_raw(const void* desc_a, const void* desc_b, size_t desc_bytes, const int* dead, int* skipped, int* total, void* stream) {
+  if (skipped) *skipped = 0;
+  if (total) *total = 0;
+  if (desc_bytes != sizeof(GemmDesc)) { dmx_set_error("GemmDesc size mismatch: %zu vs %zu", desc_bytes, sizeof(GemmDesc)); return DMX_ERR_SHAPE; }
+  const GemmDesc* a = reinterpret_cast<const GemmDesc*>(desc_a);
+  const GemmDesc& b = *reinterpret_cast<const GemmDesc*>(desc_b);
+  if (!dmx_conv_pair_eligible(a, b)) { dmx_set_error("shape not handled by the fused convolution-pair kernel"); return DMX_ERR_SHAPE; }
+  PairDead pd;
+  if (dead) pd = pair_dead_of(dead);
+  int sk = 0, tot = 0;
+  dmx_conv_pair_slabs(a, b, dead ? &pd : nullptr, &sk, &tot);
+  if (skipped) *skipped = sk;
+  if (total) *total = tot;
+  const int rc = dmx_conv_pair_launch(a, b, ST(stream), dead ? &pd : nullptr);
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("dead rows not handled by the fused convolution-pair kernel (zero rows need the residual to be stage a's input)");
+  return rc;
+}
+
+int dmx_conv_pair_group_dead_raw(int n, const void* descs_a, const void* descs_b, size_t desc_bytes, const int* dead, void* stream) {
+  if (desc_bytes != sizeof(GemmDesc)) { dmx_set_error("GemmDesc size mismatch: %zu vs %zu", desc_bytes, sizeof(GemmDesc)); return DMX_ERR_SHAPE; }
+  if (n < 1 || n > 3) { dmx_set_error("conv pair group: 1..3 problems"); return DMX_ERR_SHAPE; }
+  const GemmDesc* a = reinterpret_cast<const GemmDesc*>(descs_a);
+  const GemmDesc* b = reinterpret_cast<const GemmDesc*>(descs_b);
+  const GemmDesc* pa[3]; const GemmDesc* pb[3];
+  PairDead pd[3];
+  for (int j = 0; j < n; ++j) { pa[j] = a + j; pb[j] = b + j; if (dead) pd[j] = pair_dead_of(dead + 4 * j); }
+  const int rc = dmx_conv_pair_group_launch(n, pa, pb, ST(stream), dead ? pd : nullptr);
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("shape not handled by the fused convolution-pair kernel");
+  return rc;
+}
+
 int dmx_flash_attn_raw(const void* q, const void* k, const void* v, void* o, const float* colbias, int B, int Nq, int Nk, int ldv, int C,
                        int heads, float scale, void* stream) {
   const int rc = dmx_flash_attn_fwd((const act_t*)q, (const act_t*)k, (const act_t*)v, (act_t*)o, colbias, B, Nq, Nk, C, heads, scale,

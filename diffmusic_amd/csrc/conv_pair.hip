@@ -579,7 +579,8 @@ bool dmx_conv_pair_eligible(const GemmDesc* a, const GemmDesc& b) {
   if ((b.flags & EPI_RESID_INV) && !(b.resid_inv_slope >= 1.f)) return false;
   if (b.ldc != C || ((b.flags & EPI_RESID) && b.ldr != C) || ((b.flags & EPI_MASK) && b.ldx != C) || ((b.flags & EPI_LRELU2) && b.ldc2 != C))
     return false;
-  if ((b.flags & EPI_MASKBITS) && (!b.XB || b.ldxb * 8 < C)) return false;
+  // sign-bit masks are loaded as 32-bit words (stage a's slab copy below, the epilogue's row words): rows must start on one
+  if ((b.flags & EPI_MASKBITS) && (!b.XB || b.ldxb * 8 < C || (b.ldxb & 3))) return false;
   if ((b.flags & EPI_BITS2) && (!b.B2 || b.ldb2 * 8 < C)) return false;
   if (a) {
     if (!stage_ok(*a, C, T, EPI_BIAS | EPI_LRELU2 | EPI_NO_C | EPI_MASK | EPI_MASKBITS | EPI_BITS2) || !halo_of(*a).ok) return false;
@@ -588,7 +589,7 @@ bool dmx_conv_pair_eligible(const GemmDesc* a, const GemmDesc& b) {
     if ((a->flags & EPI_LRELU2) && a->C2 && a->ldc2 != C) return false;
     if ((a->flags & EPI_BITS2) && (!(a->flags & EPI_LRELU2) || !a->B2 || a->ldb2 * 8 < C)) return false;
     if ((a->flags & EPI_MASK) && (a->ldx != C || !a->X)) return false;
-    if ((a->flags & EPI_MASKBITS) && (!a->XB || a->ldxb * 8 < C || (a->flags & EPI_MASK))) return false;
+    if ((a->flags & EPI_MASKBITS) && (!a->XB || a->ldxb * 8 < C || (a->ldxb & 3) || (a->flags & EPI_MASK))) return false;
     const Halo hb = halo_of(b);
     if (PAIR_ROWS - hb.lo - hb.hi < 128) return false;
   }

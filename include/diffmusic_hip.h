@@ -378,8 +378,6 @@ int dmx_prof_dominant(double* ms, double* flops, double* bytes);
 
 /* ---- low-level test hook: one implicit-GEMM launch described by the internal descriptor --------*/
 int dmx_gemm_raw(const void* desc, size_t desc_bytes, void* stream);
-/* test hook for the fused convolution pair (HiFi-GAN resblock step, C = 32 / 64): stage `a` (may be NULL: plain slab
- * convolution) feeds stage `b` through LDS.  Returns DMX_ERR_SHAPE when the shape is not handled by the fused kernel. */
 /* test hook for the fused forward attention of the U-Net (diffusers Attention inside UNet2DConditionModel,
  * pipeline_musicldm.py:696-703): q (B,Nq,C), k (B,Nk,C), v (B,Nk,ldv) fp16 channels-last (ldv = 0: C), o (B,Nq,C); colbias optional
  * (B,Nk) fp32 additive key bias. */
@@ -409,10 +407,17 @@ int dmx_geglu_raw(const void* x, void* y, long long rows, int I, void* stream);
 /* test hook: fp32 scratch that lets small-M / deep-K launches run split-K (NULL disables it); the U-Net executor
  * installs its own */
 int dmx_gemm_splitk_workspace(void* ws, size_t bytes);
+/* test hook for the fused convolution pair (HiFi-GAN resblock step, C = 32 / 64 / 128): stage `a` (may be NULL: plain slab
+ * convolution) feeds stage `b` through LDS.  Returns DMX_ERR_SHAPE when the shape is not handled by the fused kernel. */
 int dmx_conv_pair_raw(const void* desc_a, const void* desc_b, size_t desc_bytes, void* stream);
+/* the same launch with dead rows (csrc/conv_pair.h PairDead): dead = {skip0, skip1, zero0, zero1} per clip, NULL = none.  *skipped / *total
+ * (HOST pointers, may be NULL) receive how many output slabs per clip the launch skips and how many there are. */
+int dmx_conv_pair_dead_raw(const void* desc_a, const void* desc_b, size_t desc_bytes, const int* dead, int* skipped, int* total, void* stream);
 /* test hook: n (<= 3) mutually independent fused pairs of one width as ONE grid, longest problem first (the k = 3 / 7 / 11 branches
  * of a HiFi-GAN resblock step, transformers HifiGanResidualBlock.forward); descs_a / descs_b: n consecutive descriptors each. */
 int dmx_conv_pair_group_raw(int n, const void* descs_a, const void* descs_b, size_t desc_bytes, void* stream);
+/* the grouped launch with dead rows per problem: dead = 4 n ints ({skip0, skip1, zero0, zero1} of problem j at dead + 4 j) or NULL */
+int dmx_conv_pair_group_dead_raw(int n, const void* descs_a, const void* descs_b, size_t desc_bytes, const int* dead, void* stream);
 /* test hook: GroupNorm (+ SiLU) forward as the U-Net / VAE executors run it (diffusers ResnetBlock2D norm1 / norm2, Attention
  * group_norm; reached from pipeline_musicldm.py:696-703 and scheduling_dps.py:195-197).  x, y (B, P, C) fp16 channels-last;
  * stats (B, G, 2) = (mean, rstd), scale / shift (B, C) fp32 outputs; partial: fp32 scratch of dmx_groupnorm_scratch_floats(B, C, G). */

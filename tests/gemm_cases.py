@@ -35,6 +35,12 @@ E[x^2] - mean^2.  With ns slots, sa = sum |x|, q = sum x^2:
 Rows keep |mean| <= std (the large-offset rows stay with the norm test in tests/test_gpu_gemm.py): then every term above is of the
 order of K u32 |v| and the bound stays at rounding level.  The fp32 emulation below validates it.
 
+Sign-bit tape (the two flags the vocoder's tape uses).  EPI_MASKBITS is EPI_MASK with the factor taken from a bit of XB (Buf kind 'bits':
+one byte per 8 channels, bit e of byte k <=> channel 8 k + e > 0).  EPI_BITS2 is a third kind of write, compared EXACTLY: when the 16-bit
+tensor is stored next to it (C2, or C without EPI_LRELU2) every byte must equal the sign bits of what the kernel itself stored, element for
+element; when nothing is stored (the fused pair's bits-only tape, tests/pair_cases.py) it must equal (ref > 0) wherever |ref| > A + tiny and
+is free elsewhere.  Untouched bytes keep the sentinel 0xAA.
+
 Emulation share: one rounding to a 16-bit output alone costs up to eps |ref| + tiny / 2, i.e. 2 / 3 of the output term 1.5 eps |ref|, so
 "half the bound" cannot hold for the whole error of a 16-bit output.  The host test therefore asserts half for everything EXCEPT that
 single rounding: err <= (eps |ref| + tiny / 2) + (bound - eps |ref| - tiny / 2) / 2; for fp32 outputs plainly err <= bound / 2."""
@@ -47,13 +53,15 @@ import torch.nn.functional as F
 
 EPI_BIAS, EPI_ROWBIAS, EPI_RESID, EPI_ACCUM, EPI_MASK, EPI_LRELU2, EPI_TANH, EPI_F32OUT, EPI_NO_C, EPI_RESID_INV = \
     1, 2, 4, 8, 16, 32, 64, 128, 256, 512
+EPI_MASKBITS, EPI_BITS2 = 1024, 2048
 EPI_SOFTBWD, EPI_GEGLU, EPI_LNFOLD = 4096, 8192, 16384
 FLAG_NAMES = {"BIAS": EPI_BIAS, "ROWBIAS": EPI_ROWBIAS, "RESID": EPI_RESID, "ACCUM": EPI_ACCUM, "MASK": EPI_MASK, "LRELU2": EPI_LRELU2,
-              "TANH": EPI_TANH, "F32OUT": EPI_F32OUT, "NO_C": EPI_NO_C, "RESID_INV": EPI_RESID_INV, "SOFTBWD": EPI_SOFTBWD,
-              "GEGLU": EPI_GEGLU, "LNFOLD": EPI_LNFOLD}
+              "TANH": EPI_TANH, "F32OUT": EPI_F32OUT, "NO_C": EPI_NO_C, "RESID_INV": EPI_RESID_INV, "MASKBITS": EPI_MASKBITS,
+              "BITS2": EPI_BITS2, "SOFTBWD": EPI_SOFTBWD, "GEGLU": EPI_GEGLU, "LNFOLD": EPI_LNFOLD}
 U32 = 2.0 ** -24
 SENT16 = 0x7B7B                      # untouched 16-bit elements (finite in fp16 and bf16)
 SENT32 = 0x7B7B7B7B                  # untouched fp32 elements
+SENT8 = 0xAA                         # untouched bytes of a sign-bit tensor
 # tile configuration -> (BM, BN); 3 .. 6 are the register-staged kernel, the others LDS-DMA tiles (csrc/gemm_conv.hip launch_by_cfg)
 TILES = {1: (256, 256), 2: (256, 128), 3: (128, 128), 4: (128, 64), 5: (128, 32), 6: (64, 64), 7: (320, 256), 8: (192, 256),
          9: (320, 128), 10: (192, 128), 11: (128, 128), 12: (64, 64), 13: (128, 64), 14: (64, 128), 15: (64, 64), 16: (64, 128),
@@ -61,9 +69,9 @@ TILES = {1: (256, 256), 2: (256, 128), 3: (128, 128), 4: (128, 64), 5: (128, 32)
 DMA_TILES = [t for t in TILES if not 3 <= t <= 6]
 LN_TILES = [1, 2, 10, 11, 18, 12, 13, 14, 3, 4, 6]       # what dmx_gemm_launch_ln maps onto distinct instantiations
 INT_FIELDS = ("M N K ldw Hi Wi Ci lda Hq Wq sy sx ntaps Ho Wo ldc osy ooy osx oox ldr ldx ldc2 Z Zi sAo sAi sWo sWi sCo sCi flags tile_cfg "
-              "ldrb nslots").split()
+              "ldrb nslots ldxb ldb2").split()
 FLOAT_FIELDS = "alpha act_slope mask_slope resid_inv_slope ln_eps".split()
-PTR_FIELDS = "A W C C2 bias rowbias R X colsum rowstats_in".split()
+PTR_FIELDS = "A W C C2 bias rowbias R X colsum rowstats_in XB B2".split()
 
 
 def act_eps(adt):
@@ -79,7 +87,7 @@ def launch(**kw):
     d = {k: 0 for k in INT_FIELDS}
     d.update({k: 0.0 for k in FLOAT_FIELDS})
     d.update({k: None for k in PTR_FIELDS})
-    d.update(Z=1, Zi=1, sy=1, sx=1, osy=1, osx=1, alpha=1.0, tdy=[0], tdx=[0])
+    d.update(Z=1, Zi=1, sy=1, sx=1, osy=1, osx=1, alpha=1.0, tdy=[0], tdx=[0], bias_first=None)     # bias_first: emulate() only (None: its rule)
     unknown = set(kw) - set(d)
     assert not unknown, unknown
     d.update(kw)
@@ -89,20 +97,37 @@ def launch(**kw):
 
 
 class Buf:
-    """A flat buffer.  kind: 'act' (16-bit) or 'f32'.  data: float64 values; NaN marks a sentinel element (outputs only)."""
+    """A flat buffer.  kind: 'act' (16-bit), 'f32' or 'bits' (a sign-bit tensor: one BYTE per 8 channels, bit e of byte k <=> channel
+    8 k + e > 0, csrc/dmx_common.h EPI_MASKBITS; data holds the byte values 0 .. 255).  data: float64 values; NaN marks a sentinel
+    element (outputs only)."""
 
     def __init__(self, kind, data):
         self.kind = kind
         self.data = data.double().reshape(-1).clone()
 
     def rounded(self, adt):
-        if adt is None:
+        if adt is None or self.kind == "bits":
             return Buf(self.kind, self.data)
         return Buf(self.kind, (self.data.to(adt) if self.kind == "act" else self.data.float()).double())
 
 
 def sentinel(kind, n):
     return Buf(kind, torch.full((n,), float("nan"), dtype=torch.float64))
+
+
+_BITW = 2.0 ** torch.arange(8, dtype=torch.float64)
+
+
+def pack_bits(pos):
+    """(rows, N) bool, N % 8 == 0 -> (rows, N / 8) byte values (float64): bit e of byte k <=> column 8 k + e"""
+    return (pos.double().view(pos.shape[0], -1, 8) * _BITW).sum(-1)
+
+
+def unpack_bits(by, reverse=False):
+    """(rows, N / 8) byte values -> (rows, N) bool"""
+    e = torch.arange(8)
+    b = (by.long()[:, :, None] >> (7 - e if reverse else e)) & 1
+    return b.view(by.shape[0], -1) > 0
 
 
 # ------------------------------------------------------------------------------------------------------------------ the model
@@ -180,10 +205,14 @@ def ln_stats(L, bufs, Ag):
     return mean, rstd, d_mean, d_rstd
 
 
-def run_launch(L, state, adt, mut=None):
+def run_launch(L, state, adt, mut=None, in_err=None):
     """Float64 model of one launch.  state: {name: Buf} with the CURRENT contents of every buffer (EPI_ACCUM reads C).
     -> list of writes (buffer name, flat indices (M', N'), exact values, bound): the set of elements the launch may write.
-    adt: output type for the bound (None: bounds are zeros).  mut: name of a mutant of the reference."""
+    adt: output type for the bound (None: bounds are zeros).  mut: name of a mutant of the reference.
+    EPI_BITS2 adds a write to the 'bits' buffer B2: (name, byte indices (M', N / 8), byte of (ref > 0), byte of the bits that are FREE
+    when no 16-bit tensor is stored next to them: |ref| <= A + tiny, the sign of what the kernel holds is open there).
+    in_err: {buffer name: flat element-wise bound of what that buffer's holder may differ from state by} for the input A (the
+    intermediate of a fused pair, tests/pair_cases.py): P = gather(in_err) |W|^T joins the bound like the accumulators themselves."""
     fl = L.flags
     writes = []
     eps, tiny = (act_eps(adt), act_tiny(adt)) if adt is not None else (0.0, 0.0)
@@ -194,14 +223,22 @@ def run_launch(L, state, adt, mut=None):
         if mut == "skip_k_chunk":
             Ag = Ag.clone()
             Ag[:, L.K - 8:] = 0.0
+        if mut == "drop_last_tap":
+            Ag = Ag.clone()
+            Ag[:, L.K - L.Ci:] = 0.0
         acc = Ag @ Wm.t()
         S = Ag.abs() @ Wm.abs().t()
+        P_in = None
+        if in_err is not None and L.A in in_err:
+            Eg, _ = gather(L, {**state, L.A: Buf("act", in_err[L.A])}, z)
+            P_in = Eg @ Wm.abs().t()
+            S = S + P_in
         orow, b = out_rows(L)
         if mut == "oox_off_by_one":
             orow = orow + 1
         n = torch.arange(L.N)
         E = 0
-        pre = torch.zeros_like(acc)                     # error terms that are not of the form (K + E) u32 S
+        pre = torch.zeros_like(acc) if P_in is None else P_in     # error terms that are not of the form (K + E) u32 S
 
         def at(name, ld, rows=orow, off=coff):
             return state[name].data[off + rows[:, None] * ld + n[None, :]]
@@ -226,6 +263,11 @@ def run_launch(L, state, adt, mut=None):
             x = at(L.X, L.ldx)
             pos = (x >= 0) if mut == "mask_zero_positive" else (x > 0)
             f = torch.where(pos, 1.0, L.mask_slope)
+            v, S, pre = v * f, S * f, pre * f
+            E += 1
+        if fl & EPI_MASKBITS:                               # EPI_MASK with the factor taken from the bit
+            by = state[L.XB].data[orow[:, None] * L.ldxb + torch.arange(L.N // 8)[None, :]]
+            f = torch.where(unpack_bits(by, reverse=(mut == "mask_bit_reversed")), 1.0, L.mask_slope)
             v, S, pre = v * f, S * f, pre * f
             E += 1
         if fl & EPI_SOFTBWD:
@@ -302,15 +344,25 @@ def run_launch(L, state, adt, mut=None):
                 return torch.zeros_like(ref)
             return A + (4 * U32 * ref.abs() if kind == "f32" else 1.5 * eps * ref.abs() + tiny / 2)
 
+        def bits_write(ref, A_):
+            free = (ref.abs() <= A_ + tiny) if adt is not None else torch.zeros_like(ref, dtype=torch.bool)
+            bidx = orow[:, None] * L.ldb2 + torch.arange(L.N // 8)[None, :]
+            writes.append((L.B2, bidx[rows], pack_bits(ref > 0)[rows], pack_bits(free)[rows]))
+
         if not (fl & EPI_NO_C):
             idx = coff + orow[:, None] * L.ldc + n[None, :]
             writes.append((L.C, idx[rows, cols], v[rows, cols], bound(v, state[L.C].kind)[rows, cols]))
+            if (fl & EPI_BITS2) and not (fl & EPI_LRELU2):
+                bits_write(v, A)
         if fl & EPI_LRELU2:
             v2 = torch.where(v > 0, v, v * L.act_slope)
             idx = coff + orow[:, None] * L.ldc2 + n[None, :]
             if adt is not None:                             # the slope carries A wherever the sign of v is beyond doubt (|v| > A)
                 A = A * torch.where((v < 0) & (v.abs() > A), L.act_slope, 1.0) + U32 * v2.abs()
-            writes.append((L.C2, idx[rows, cols], v2[rows, cols], bound(v2, "act")[rows, cols]))
+            if L.C2 is not None:
+                writes.append((L.C2, idx[rows, cols], v2[rows, cols], bound(v2, "act")[rows, cols]))
+            if fl & EPI_BITS2:
+                bits_write(v2, A)
     return writes
 
 
@@ -323,28 +375,73 @@ def _unpack_bias(bp):
 def expected(launches, bufs, adt, mut=None):
     """Run every launch of a case.  -> {output buffer name: (values, bound, count)}: flat float64 values (NaN = sentinel kept), the
     element-wise bound and how many launches wrote each element (0 = must keep its sentinel)."""
+    return expected_all(launches, bufs, adt, mut)[0]
+
+
+def expected_all(launches, bufs, adt, mut=None, run=run_launch):
+    """-> (outs as expected() returns them for the 16-bit / fp32 outputs, the same for the sign-bit outputs: {B2 name: (byte of
+    (ref > 0), byte of the free bits, count)}).  An EPI_ACCUM launch onto elements an EARLIER launch of the case wrote inherits that
+    launch's bound (its input is the other's output)."""
     state = {k: Buf(b.kind, b.data) for k, b in bufs.items()}
     outs = {}
     for L in launches:
-        for name in (L.C, L.C2):
+        for name in (L.C, L.C2, L.B2):
             if name is not None and name not in outs:
                 nel = state[name].data.numel()
                 outs[name] = (state[name].data, torch.zeros(nel, dtype=torch.float64), torch.zeros(nel, dtype=torch.int64))
     for L in launches:
-        for name, idx, ref, bnd in run_launch(L, state, adt, mut):
+        for name, idx, ref, bnd in run(L, state, adt, mut):
             val, bd, cnt = outs[name]
             idx = idx.reshape(-1)
             ok = (idx >= 0) & (idx < val.numel())          # (a mutant's row map may leave the buffer)
             val[idx[ok]] = ref.reshape(-1)[ok]
-            bd[idx[ok]] = bnd.reshape(-1)[ok]
+            carry = bd[idx[ok]] if (L.flags & EPI_ACCUM) and name == L.C else 0.0
+            bd[idx[ok]] = bnd.reshape(-1)[ok] + carry
             cnt[idx[ok]] += 1
-    return outs
+    return ({k: v for k, v in outs.items() if state[k].kind != "bits"}, {k: v for k, v in outs.items() if state[k].kind == "bits"})
 
 
-def mutant_ratio(exp, mutd):
+def bits_source(launches):
+    """{B2 name: (name of the 16-bit tensor stored next to it, its row stride, the B2 row stride, N)} -- None where the bits leave alone"""
+    src = {}
+    for L in launches:
+        if L.flags & EPI_BITS2:
+            if L.flags & EPI_LRELU2:
+                src[L.B2] = (L.C2, L.ldc2, L.ldb2, L.N) if L.C2 is not None else None
+            else:
+                src[L.B2] = (L.C, L.ldc, L.ldb2, L.N) if not (L.flags & EPI_NO_C) else None
+    return src
+
+
+def check_bits(name, got_bytes, exp_bits, src, stored):
+    """The third kind of write, compared EXACTLY.  got_bytes: flat byte values of B2 after the launches (float64 / int); exp_bits: its
+    entry of expected_all()[1]; src: its entry of bits_source(); stored: flat float64 values of the stored 16-bit tensor (src not None).
+    -> number of wrong bytes among the written ones (the caller asserts 0 and checks the unwritten ones against the sentinel)."""
+    ref, free, cnt = exp_bits
+    w = cnt > 0
+    got = got_bytes.long()
+    if src is not None:                                     # the sign bits of what the kernel itself stored, element for element
+        _, ld, ldb2, N = src
+        rows = stored.numel() // ld
+        want = torch.full_like(ref, -1.0)
+        nb_rows = min(rows, ref.numel() // ldb2)
+        wb = pack_bits(stored.view(rows, ld)[:nb_rows, :N] > 0)
+        want.view(-1)[:nb_rows * ldb2].view(nb_rows, ldb2)[:, :N // 8] = wb
+        return int((got[w] != want.long()[w]).sum())
+    return int((((got[w] ^ ref.long()[w]) & ~free.long()[w] & 0xFF) != 0).sum())
+
+
+def mutant_ratio(exp, mutd, exp_bits=None, mut_bits=None):
     """largest |mutant - ref| / bound over what the reference writes; inf where a mutant leaves a sentinel in the writable set or
-    writes outside it"""
+    writes outside it, or where a sign byte differs outside the free bits of either side"""
     worst = 0.0
+    for name, (ref, free, cnt) in (exp_bits or {}).items():
+        mref, mfree, mc = mut_bits[name]
+        w = cnt > 0
+        if ((mc > 0) != w).any():
+            return float("inf")
+        if (((ref.long()[w] ^ mref.long()[w]) & ~(free.long()[w] | mfree.long()[w]) & 0xFF) != 0).any():
+            return float("inf")
     for name, (val, bd, cnt) in exp.items():
         mv, _, mc = mutd[name]
         w = cnt > 0
@@ -390,7 +487,9 @@ def emulate(launches, bufs, adt, order):
                 return state[name].data[coff + orow[:, None] * ld + n[None, :]].float()
 
             slices = L.tile_cfg // 100 if L.tile_cfg >= 100 else 1
-            bias_first = bool(fl & EPI_BIAS) and not (fl & (EPI_MASK | EPI_SOFTBWD | EPI_LNFOLD)) and slices == 1
+            bias_first = bool(fl & EPI_BIAS) and not (fl & (EPI_MASK | EPI_MASKBITS | EPI_SOFTBWD | EPI_LNFOLD)) and slices == 1
+            if L.bias_first is not None:
+                bias_first = bool(fl & EPI_BIAS) and L.bias_first
             if slices > 1:
                 nk = -(-L.K // 64)
                 per = -(-nk // slices)
@@ -415,6 +514,9 @@ def emulate(launches, bufs, adt, order):
                 v = (rstd.double()[:, None] * t.double() + bs[None, :]).float()                    # fma: one rounding
             if fl & EPI_MASK:
                 v = v * torch.where(at(L.X, L.ldx) > 0, torch.tensor(1.0), torch.tensor(L.mask_slope, dtype=f32))
+            if fl & EPI_MASKBITS:
+                by = state[L.XB].data[orow[:, None] * L.ldxb + torch.arange(L.N // 8)[None, :]]
+                v = v * torch.where(unpack_bits(by), torch.tensor(1.0), torch.tensor(L.mask_slope, dtype=f32))
             if fl & EPI_SOFTBWD:
                 v = (v - state[L.rowbias].data[z * L.M + torch.arange(L.M)].float()[:, None]) * at(L.X, L.ldx)
             if (fl & EPI_BIAS) and not bias_first and not (fl & EPI_LNFOLD):
@@ -438,13 +540,23 @@ def emulate(launches, bufs, adt, order):
             if fl & EPI_TANH:
                 v = torch.tanh(v)
             assert v.dtype == f32
+
+            def bits_out(o16):                          # the sign bits of the 16-bit value the kernel holds
+                bidx = orow[:, None] * L.ldb2 + torch.arange(L.N // 8)[None, :]
+                state[L.B2].data[bidx.reshape(-1)] = pack_bits(o16.double() > 0).reshape(-1)
+
             if not (fl & EPI_NO_C):
                 o = v if state[L.C].kind == "f32" else v.to(adt)
                 state[L.C].data[(coff + orow[:, None] * L.ldc + n[None, :]).reshape(-1)] = o.double().reshape(-1)
+                if (fl & EPI_BITS2) and not (fl & EPI_LRELU2):
+                    bits_out(o)
             if fl & EPI_LRELU2:
-                v2 = torch.maximum(v, v * torch.tensor(L.act_slope, dtype=f32))
-                state[L.C2].data[(coff + orow[:, None] * L.ldc2 + n[None, :]).reshape(-1)] = v2.to(adt).double().reshape(-1)
-    return {k: state[k].data for L in launches for k in (L.C, L.C2) if k is not None}
+                v2 = torch.maximum(v, v * torch.tensor(L.act_slope, dtype=f32)).to(adt)
+                if L.C2 is not None:
+                    state[L.C2].data[(coff + orow[:, None] * L.ldc2 + n[None, :]).reshape(-1)] = v2.double().reshape(-1)
+                if fl & EPI_BITS2:
+                    bits_out(v2)
+    return {k: state[k].data for L in launches for k in (L.C, L.C2, L.B2) if k is not None}
 
 
 # ------------------------------------------------------------------------------------------------------------------ builders
@@ -483,6 +595,14 @@ def _epi_bufs(g, bufs, L, rows, N, flags, n_img, ld_pad, kind="act", special_mas
     if flags & EPI_LRELU2:
         bufs["C2"] = sentinel("act", nel)
         kw.update(C2="C2", act_slope=0.1)
+    if flags & EPI_MASKBITS:                            # row strides wider than N / 8 (ldxb a multiple of 8: the tiles load words)
+        ldxb = (N // 64 + 1) * 8
+        bufs["XB"] = Buf("bits", torch.randint(0, 256, (rows * ldxb,), generator=g))
+        kw.update(XB="XB", ldxb=ldxb, mask_slope=0.1)
+    if flags & EPI_BITS2:
+        ldb2 = N // 8 + 3
+        bufs["B2"] = sentinel("bits", rows * ldb2)
+        kw.update(B2="B2", ldb2=ldb2)
     bufs["C"] = sentinel(kind, nel)
     kw["C"] = "C"
     return kw
@@ -781,10 +901,17 @@ class Case:
         return self._cache[adt]
 
     def expected(self, adt, mut=None):
+        return self._expected(adt, mut)[0]
+
+    def expected_bits(self, adt, mut=None):
+        """the sign-bit outputs: {B2 name: (byte of (ref > 0), byte of the free bits, count)}"""
+        return self._expected(adt, mut)[1]
+
+    def _expected(self, adt, mut):
         key = ("exp", adt, mut)
         if key not in self._cache:
             launches, bufs, _ = self.data(adt)
-            self._cache[key] = expected(launches, bufs, adt, mut)
+            self._cache[key] = expected_all(launches, bufs, adt, mut)
         return self._cache[key]
 
 
@@ -864,9 +991,22 @@ def _cases():
             nm = f"splitk{tag}-{plan}"
             cs.append(Case(nm, "splitk", lambda adt, nm="splitk" + tag, fl=fl, plan=plan: conv2d_3x3_case(nm, 4, 5, 5, 64, 72, fl, 0.5, plan),
                            plan, fl, M=100, N=72, K=576, HqWq=25, splitk=plan >= 100))
+    # ---- the sign-bit tape of the vocoder on the generic tiles: mask factor from a bit (EPI_MASKBITS), sign bytes of the stored tensor
+    # (EPI_BITS2) with and without the primary output; N = 8 / 16 sit inside one 32-column wave tile (the N-tail path of the mask), N = 88
+    # spans tiles and leaves a tail.  Tile 0 = what the dispatcher picks, 6 = register-staged, 12 = LDS-DMA: every tile has its own
+    # instantiation with the bit paths (csrc/gemm_conv.hip launch_cfg / launch_glds pick it by flag), so no forced tile lacks one.
+    for fname, fl in BIT_FLAG_SETS.items():
+        for N in (8, 16, 88):
+            for tile in BIT_TILES:
+                nm = f"bits-{fname}-n{N}-tile{tile}"
+                cs.append(Case(nm, "bits", lambda adt, nm=nm, fl=fl, N=N, tile=tile: conv1d_case(nm, 2, 50, 24, N, 3, 2, fl, 1.0, tile, 8, 81,
+                                                                                                  special_mask=True), tile, fl, M=81, N=N, K=72, HqWq=50))
     return cs
 
 
+BIT_FLAG_SETS = {"maskbits-resid": EPI_MASKBITS | EPI_RESID, "lrelu2-bits2": EPI_LRELU2 | EPI_BITS2,
+                 "lrelu2-bits2-noc": EPI_LRELU2 | EPI_BITS2 | EPI_NO_C}
+BIT_TILES = (0, 6, 12)
 CASES = _cases()
 BY_NAME = {c.name: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
@@ -905,4 +1045,5 @@ MUTANTS = {
     "geglu_swap": lambda c: bool(c.flags & EPI_GEGLU),
     "geglu_bias_unpacked": lambda c: bool(c.flags & EPI_GEGLU) and bool(c.flags & EPI_BIAS),
     "geglu_erf_fp32": lambda c: bool(c.feat.get("exact_gate")),
+    "mask_bit_reversed": lambda c: bool(c.flags & EPI_MASKBITS),
 }

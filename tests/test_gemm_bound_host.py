@@ -113,6 +113,16 @@ def test_case_table_covers_tiles_flags_and_edges():
     assert any(c.family == "geglu" and c.feat["N"] == 96 for c in cs)
     assert [c.tile for c in cs if c.family == "geglu-ln"] == G.LN_TILES
     assert {c.tile for c in cs if c.family == "splitk"} == {12, 212, 313}
+    bits = [c for c in cs if c.family == "bits"]
+    assert {(c.feat["N"], c.tile) for c in bits} == {(N, t) for N in (8, 16, 88) for t in (0, 6, 12)}
+    for c in bits:
+        L = c.data(torch.float16)[0][0]
+        assert (L.Ci, L.ntaps, L.Hq * L.Wq) == (24, 3, 50)
+        if c.flags & G.EPI_MASKBITS:
+            assert L.ldxb > L.N // 8 and c.flags & G.EPI_RESID
+        if c.flags & G.EPI_BITS2:
+            assert L.ldb2 > L.N // 8 and c.flags & G.EPI_LRELU2
+    assert any(c.flags & G.EPI_BITS2 and c.flags & G.EPI_NO_C for c in bits) and any(c.flags & G.EPI_BITS2 and not c.flags & G.EPI_NO_C for c in bits)
     for c in cs:
         if c.family == "rowmap" and c.feat.get("multi"):
             for val, bd, cnt in c.expected(torch.float16).values():
@@ -148,13 +158,24 @@ def _ratios(case, adt, got):
     return worst, share
 
 
+def _bits_ok(case, adt, got):
+    """the sign bytes of an emulated run: exact against what it stored, or against the reference outside the free bits"""
+    src = G.bits_source(case.data(adt)[0])
+    for name, eb in case.expected_bits(adt).items():
+        bad = G.check_bits(name, got[name], eb, src[name], got[src[name][0]] if src[name] else None)
+        assert bad == 0, (case.name, name, bad)
+        assert torch.isnan(got[name][eb[2] == 0]).all()
+
+
 @pytest.mark.parametrize("adt", ADTS, ids=IDS)
 @pytest.mark.parametrize("name", NAMES)
 def test_emulated_kernel_stays_inside_half_the_bound(name, adt):
     case = G.BY_NAME[name]
     launches, bufs, _ = case.data(adt)
     for order in ("seq", "blk32"):
-        worst, share = _ratios(case, adt, G.emulate(launches, bufs, adt, order))
+        got = G.emulate(launches, bufs, adt, order)
+        _bits_ok(case, adt, got)
+        worst, share = _ratios(case, adt, got)
         print(f"{name} {adt} {order}: emulated err / bound = {worst:.3f}, share beside the output rounding = {share:.3f}")
         assert share <= 0.5, (order, share)
         assert worst <= 1.0
@@ -170,7 +191,8 @@ def test_every_applicable_mutant_leaves_the_bound(name, adt):
     for mut, applies in G.MUTANTS.items():
         if not applies(case):
             continue
-        ratio = G.mutant_ratio(exp, G.expected(launches, bufs, adt, mut))
+        mo, mb = G.expected_all(launches, bufs, adt, mut)
+        ratio = G.mutant_ratio(exp, mo, case.expected_bits(adt), mb)
         print(f"{name} {adt}: mutant {mut} err / bound = {ratio:.3g}")
         applied.append(mut)
         assert ratio > 1.0, (mut, ratio)
