@@ -47,7 +47,8 @@ __global__ __launch_bounds__(256) void f32_gemm_nt_kernel(const float* __restric
       const int b = m / T, f = m - b * T;
       arow = A + (long long)b * lda;                     // lda = waveform row stride
       fbase = f * hop;                                   // padded index of k=0
-      a_fast = (fbase - pad >= 0) && (fbase - pad + K <= L) && ((((long long)b * lda + fbase - pad) & 3) == 0);
+      // 16-byte reads need the ADDRESS aligned, not the element offset: the waveform may be a view that starts mid-vector (wav[:, 1:])
+      a_fast = (fbase - pad >= 0) && (fbase - pad + K <= L) && ((reinterpret_cast<uintptr_t>(arow + (fbase - pad)) & 15) == 0);
     } else {
       arow = A + (long long)m * lda;
     }

@@ -394,7 +394,7 @@ int dmx_stft_mel_bwd(const DmxStftMelTables& t, const float* wav, long long wav_
   P.dwav = dwav; P.dwav_stride = dwav_stride; P.Lfull = Lfull; P.accumulate = accumulate;
   P.add = add; P.add_stride = add_stride; P.addmag = addmag; P.nscale = nscale; P.thr = thr;
   int chunk = (BWD_MAX_CHUNK / hop) * hop;                 // whole hops per workgroup
-  if (chunk < hop) chunk = BWD_MAX_CHUNK;                  // (hop > 2560: any chunking is correct, frames are found from sample ranges)
+  if (chunk < hop) chunk = BWD_MAX_CHUNK;                  // (hop > BWD_MAX_CHUNK = 1280: any chunking is correct, frames are found from sample ranges)
   P.chunk = chunk;
   hipLaunchKernelGGL(stft_mel_bwd_kernel, dim3(cdiv(L, chunk), B), dim3(256), 0, st, P);
   return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
