@@ -286,6 +286,25 @@ def declip_project(wav, measurement, thr, L):
     return out
 
 
+def tf_gain(audio, x, gain_t, L, Lfull, *, out=None):
+    """x (B, >= L) with any row stride, gain_t (frames, 513) shared or (B, frames, 513), frames = ceil(L / 256) + 3 -> (B, Lfull): the
+    time-frequency gain A(x[:, :L]) (csrc/tf_gain.hip), +0 past L.  A is symmetric: the same call is the transpose.
+    out: caller-owned (B, >= Lfull) fp32 with any row stride; only out[:, :Lfull] is written."""
+    _rows("tf_gain", x, L)
+    B, T = x.shape[0], _lib.lib().dmx_audio_tf_frames(L)
+    assert Lfull >= L, (L, Lfull)
+    assert gain_t.is_cuda and gain_t.dtype == torch.float32 and gain_t.is_contiguous() and gain_t.device == x.device and \
+        tuple(gain_t.shape) in ((T, 513), (B, T, 513)), ("tf_gain", tuple(gain_t.shape), (B, T, 513))
+    if out is None:
+        out = torch.empty(B, Lfull, dtype=torch.float32, device=x.device)
+    else:
+        _rows("tf_gain", out, Lfull)
+        assert out.shape[0] == B and out.device == x.device, (out.shape, B)
+    _lib.check(_lib.lib().dmx_audio_tf_gain(audio, _p(x), x.stride(0), _p(gain_t), T * 513 if gain_t.dim() == 3 else 0, _p(out), out.stride(0),
+                                            B, L, Lfull, _stream()), "tf_gain")
+    return out
+
+
 def noise_add(y, noise, sigma):
     """-> y + sigma * noise (new tensor; y and noise contiguous, same number of elements)."""
     assert y.is_contiguous() and noise.is_contiguous() and y.numel() == noise.numel(), (y.shape, noise.shape)

@@ -196,6 +196,21 @@ int dmx_audio_stft_mag_bwd(dmx_audio* a, const float* dmag, float* dwav, long lo
   if (rc) return rc;
   return dmx_overlap_add(s.dframe, dwav, dwav_stride, batch, T, L, a->n_fft, a->hop, accumulate, ST(stream));
 }
+int dmx_audio_tf_frames(int L) { return L < 1 ? 0 : dmx_tf_gain_frames(L); }
+int dmx_audio_tf_gain(dmx_audio* a, const float* x, long long x_stride, const float* gain, long long gain_clip_stride, float* out,
+                      long long out_stride, int batch, int L, int full, void* stream) {
+  if (!a || !x || !gain || !out) { dmx_set_error("tf_gain: null handle or pointer"); return DMX_ERR_SHAPE; }
+  if (a->n_fft != 1024 || !a->hann || !a->fused) { dmx_set_error("tf_gain needs a handle with n_fft = 1024 and the Hann window"); return DMX_ERR_SHAPE; }
+  if (batch < 1 || batch > 65535 || L < 1 || full < L || x_stride < L || out_stride < full ||
+      (gain_clip_stride != 0 && gain_clip_stride < (long long)dmx_tf_gain_frames(L) * a->bins)) {
+    dmx_set_error("tf_gain: x (batch, >= L), out (batch, full) with row strides >= L and >= full, 1 <= L <= full, gain (frames, 513) per clip "
+                  "with clip stride 0 (shared) or >= frames * 513, frames = ceil(L / 256) + 3, 1 <= batch <= 65535");
+    return DMX_ERR_SHAPE;
+  }
+  const int rc = dmx_tf_gain(a->ft, x, x_stride, gain, gain_clip_stride, out, out_stride, batch, L, full, ST(stream));
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("tf_gain: clip too long");
+  return rc;
+}
 int dmx_audio_melscale(dmx_audio* a, const float* mag, float* mel_out, int batch, int T, float lo, float hi, void* stream) {
   return dmx_melscale(mag, a->fb, mel_out, batch, T, a->bins, a->n_mels, lo, hi, ST(stream));
 }

@@ -97,6 +97,11 @@ int dmx_stft_mel_bwd(const DmxStftMelTables& t, const float* wav, long long wav_
 // (B, 513, frames; power2 = 0 only) as |X| + nscale * addmag, in the forward and in the backward's recomputation alike;
 // hard clipping: thr (B) per-clip thresholds c > 0, y = min(max(wav * mask, -c), c) + nscale * add, gradient through -c <= wav * mask <= c only
 
+// ---- tf_gain.hip (time-frequency gain: STFT at hop 256 with zero extension, real gain per bin and frame, inverse STFT; n_fft = 1024, Hann)
+int dmx_tf_gain_frames(int L);                           // ceil(L / 256) + 3
+// out[b, 0:L] = A(x[b, 0:L]), +0 on [L, full); gain (T, 513) rows per clip, clip stride 0 = one grid for every clip; uses t.tw and t.win
+int dmx_tf_gain(const DmxStftMelTables& t, const float* x, long long x_stride, const float* gain, long long gain_clip_stride, float* out,
+                long long out_stride, int B, int L, int full, hipStream_t st);
 
 // ---- sched.hip
 int dmx_pred_x0(const float* x, const float* eps, float* x0, long long n, float sqrt_a, float sqrt_1ma, hipStream_t st);

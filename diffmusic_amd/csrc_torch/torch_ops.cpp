@@ -38,6 +38,8 @@
 #pragma weak dmx_stem_mix_fwd
 #pragma weak dmx_stem_mix_bwd
 #pragma weak dmx_stem_project
+#pragma weak dmx_audio_tf_gain
+#pragma weak dmx_audio_tf_frames
 
 namespace {
 
@@ -354,6 +356,21 @@ at::Tensor declip_project(const at::Tensor& wav, const at::Tensor& measurement, 
                         out.data_ptr<float>(), L, (int)wav.size(0), (int)L, cur_stream()), "declip_project");
   return out;
 }
+// time-frequency gain (include/diffmusic_hip.h dmx_audio_tf_gain): x (B, >= L), gain_t (frames, 513) shared or (B, frames, 513) -> (B, Lfull)
+at::Tensor tf_gain(int64_t audio, const at::Tensor& x, const at::Tensor& gain_t, int64_t L, int64_t Lfull) {
+  rows_ok(x, L, "x");
+  TORCH_CHECK(Lfull >= L, "Lfull must be >= L");
+  DMX_DEVICE_OF(x);
+  f32_cuda(gain_t, "gain_t");
+  const int64_t B = x.size(0), T = dmx_audio_tf_frames((int)L);
+  TORCH_CHECK(gain_t.device() == x.device() && ((gain_t.dim() == 2 && gain_t.size(0) == T && gain_t.size(1) == 513) ||
+              (gain_t.dim() == 3 && gain_t.size(0) == B && gain_t.size(1) == T && gain_t.size(2) == 513)),
+              "gain_t must be (", T, ", 513) or (", B, ", ", T, ", 513) on x's device");
+  at::Tensor out = at::empty({B, Lfull}, x.options());
+  ok(dmx_audio_tf_gain((dmx_audio*)audio, x.data_ptr<float>(), x.stride(0), gain_t.data_ptr<float>(), gain_t.dim() == 3 ? T * 513 : 0,
+                       out.data_ptr<float>(), Lfull, (int)B, (int)L, (int)Lfull, cur_stream()), "tf_gain");
+  return out;
+}
 at::Tensor noise_add(const at::Tensor& y, const at::Tensor& noise, double sigma) {
   f32_cuda(y, "y"); f32_cuda(noise, "noise");
   same_numel(y, noise, "noise_add(y, noise)");
@@ -645,10 +662,12 @@ TORCH_LIBRARY(diffmusic_hip, m) {
                                                          {"dmx_ir_update", (const void*)&dmx_ir_update},
                                                          {"dmx_stem_mix_fwd", (const void*)&dmx_stem_mix_fwd},
                                                          {"dmx_stem_mix_bwd", (const void*)&dmx_stem_mix_bwd},
-                                                         {"dmx_stem_project", (const void*)&dmx_stem_project}};
+                                                         {"dmx_stem_project", (const void*)&dmx_stem_project},
+                                                         {"dmx_audio_tf_gain", (const void*)&dmx_audio_tf_gain},
+                                                         {"dmx_audio_tf_frames", (const void*)&dmx_audio_tf_frames}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
-                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation entry points): rebuild with `python -m diffmusic_amd.build --force`");
+                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking entry points): rebuild with `python -m diffmusic_amd.build --force`");
   }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
@@ -681,6 +700,7 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("clip_bwd(Tensor dy, Tensor wav, Tensor thr, int Lfull) -> Tensor", &clip_bwd);
   m.def("declip_project(Tensor wav, Tensor measurement, Tensor thr, int L) -> Tensor", &declip_project);
   m.def("noise_add(Tensor y, Tensor noise, float sigma) -> Tensor", &noise_add);
+  m.def("tf_gain(int audio, Tensor x, Tensor gain_t, int L, int Lfull) -> Tensor", &tf_gain);
   m.def("track_stitch_fwd(Tensor wav, int[] starts, int L, int R, int T) -> Tensor", &track_stitch_fwd);
   m.def("track_stitch_bwd(Tensor dtrack, int[] starts, int L, int R, int Lfull) -> Tensor", &track_stitch_bwd);
   m.def("stem_mix_fwd(Tensor wav, float[]? gains, int K, int G, int L) -> Tensor", &stem_mix_fwd);

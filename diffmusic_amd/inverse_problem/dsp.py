@@ -67,3 +67,46 @@ def threshold_for_sdr(clean, sdr_db, tol_db=1e-9, max_iter=200):
                 hi = mid
         out[b] = mid
     return out
+
+
+# ---- time-frequency masking (TimeFrequencyMaskOperator; csrc/tf_gain.hip): n_fft 1024, hop 256, frame t starts at sample (t - 3) * 256
+TF_N_FFT, TF_HOP, TF_BINS = 1024, 256, 513
+
+
+def tf_frames(length):
+    """Frames of the time-frequency grid of a clip of `length` samples: T = ceil(length / 256) + 3."""
+    length = int(length)
+    if length < 1:
+        raise ValueError(f"length = {length!r}: at least one sample")
+    return -(-length // TF_HOP) + TF_N_FFT // TF_HOP - 1
+
+
+def tf_gain_grid(length, sample_rate, boxes, base=1.0):
+    """(513, T) fp32 gain grid: `base` everywhere, overwritten in order by boxes (f_lo_hz, f_hi_hz, t0_s, t1_s, gain); a None bound means
+    "to the edge".  Bin k belongs to a box when f_lo <= k * sample_rate / 1024 <= f_hi, frame t when its centre
+    ((t - 3) * 256 + 512) / sample_rate lies in [t0, t1)."""
+    T = tf_frames(length)
+    grid = np.full((TF_BINS, T), base, dtype=np.float32)
+    if not np.isfinite(grid).all():
+        raise ValueError(f"base = {base!r}: a finite number")
+    freq = np.arange(TF_BINS, dtype=np.float64) * float(sample_rate) / TF_N_FFT
+    centre = ((np.arange(T, dtype=np.float64) - (TF_N_FFT // TF_HOP - 1)) * TF_HOP + TF_N_FFT // 2) / float(sample_rate)
+    for box in boxes:
+        if len(box) != 5:
+            raise ValueError(f"box {box!r}: (f_lo_hz, f_hi_hz, t0_s, t1_s, gain)")
+        f_lo, f_hi, t0, t1, gain = box
+        if not math.isfinite(float(gain)):
+            raise ValueError(f"box {box!r}: a finite gain")
+        rows = (freq >= (-math.inf if f_lo is None else float(f_lo))) & (freq <= (math.inf if f_hi is None else float(f_hi)))
+        cols = (centre >= (-math.inf if t0 is None else float(t0))) & (centre < (math.inf if t1 is None else float(t1)))
+        grid[np.ix_(rows, cols)] = np.float32(gain)
+    return grid
+
+
+def hum_boxes(f0_hz, harmonics=1, width_hz=32.0, gain=0.0):
+    """Boxes for `tf_gain_grid` that remove mains hum: bands of `width_hz` centred on f0, 2 f0, ..., harmonics * f0, over the whole clip.
+    The bins are sample_rate / 1024 apart (15.6 Hz at 16 kHz): a band narrower than that may hold no bin."""
+    f0_hz, harmonics, width_hz = float(f0_hz), int(harmonics), float(width_hz)
+    if not (math.isfinite(f0_hz) and f0_hz > 0) or harmonics < 1 or not (math.isfinite(width_hz) and width_hz >= 0):
+        raise ValueError(f"hum_boxes({f0_hz!r}, {harmonics!r}, {width_hz!r}): a positive frequency, at least one harmonic, a width >= 0")
+    return [(m * f0_hz - 0.5 * width_hz, m * f0_hz + 0.5 * width_hz, None, None, float(gain)) for m in range(1, harmonics + 1)]

@@ -721,6 +721,90 @@ class BlindDereverberationOperator(_MelOperator):
         ops.hip.ir_update(part, self._h, self._h_rev, self._m, self._v, self.k, self.lr, self.betas[0], self.betas[1], self.adam_eps)
 
 
+class TimeFrequencyMaskOperator(_MelOperator):
+    """Time-frequency masking (extension; every operator of the reference acts on the time axis): a real gain G[k, t] on the STFT of the
+    clip, resynthesised to a waveform -- spectral holes, hum removal, a band-stop or low-pass at any cut-off, bleed confined to a band.
+
+        A = (1 / c) P^T W F^-1 G F W P      n_fft 1024, hop 256, periodic Hann w, the clip ZERO outside [0, L), c = sum_j w[n + 256 j]^2 = 1.5
+
+    Frame t = 0 .. T - 1, T = ceil(L / 256) + 3 = `dsp.tf_frames(L)`, covers the samples (t - 3) * 256 + n, n = 0 .. 1023, so every sample lies
+    in exactly four frames; G = 1 gives A = I, and A is real and symmetric: `adjoint` is the same kernel (csrc/tf_gain.hip, DESIGN.md section
+    8.7).  forward = noiser(A(x)), transform = clamp(wav2mel, -80, 80) like the IdentityOperator's.  A is materialised (`_on_load` is None):
+    a guided step is the identity's plus two launches.
+
+    gain: (513, T) -- one grid for every clip -- or (B, 513, T), fp32, finite, any sign, in the layout of `stft_mag` (bins, frames);
+    `dsp.tf_gain_grid` builds one from boxes.  The grid belongs to ONE clip length: `apply`, `forward` and `guidance` raise a ValueError
+    naming the expected shape for any other (inside a TrackOperator build it for the track's length).  With per-clip gains the batch must be
+    B, and the pipelines refuse `lanes > 1` and `shard=True` (the gains are indexed by batch position); a shared grid has no such state.
+
+    dead_span: a sample whose four covering frames have gain exactly zero in every bin, for every clip, does not reach y, and its gradient
+    is exactly zero.  Frames t0 .. t1 all zero, t1 - t0 >= 3, give the samples [256 t0, 256 (t1 - 2)); the longest such run is found on the
+    host once.  The front end and the device copy are made on first use, so the operator can be built without a GPU."""
+
+    def __init__(self, sample_rate, gain, noiser=None):
+        g = torch.as_tensor(gain).detach().to(device="cpu", dtype=torch.float32)
+        if g.dim() not in (2, 3) or g.shape[-2] != dsp.TF_BINS or g.shape[-1] < 4 or g.shape[0] < 1:
+            raise ValueError(f"gain has shape {tuple(g.shape)}: ({dsp.TF_BINS}, T) for every clip or (B, {dsp.TF_BINS}, T), T = ceil(L / 256) + 3")
+        if not bool(torch.isfinite(g).all()):
+            raise ValueError("gain: finite values (a real gain per bin and frame, of any sign)")
+        self.sample_rate, self.noiser = sample_rate, noiser
+        self.per_clip = g.dim() == 3
+        self.gain = g.clone()                                 # host copy, public layout (bins, frames)
+        self._gain_t = None                                   # device copy as the kernel reads it: (frames, bins) rows
+        self._dead = self._find_dead(g)
+        self._init_mel(sample_rate, lazy=True)
+
+    @property
+    def frames(self):
+        return self.gain.shape[-1]
+
+    @staticmethod
+    def _find_dead(g):
+        """Frames whose gain is zero in every bin of every clip -> the longest run t0 .. t1 with t1 - t0 >= 3 as samples, or None."""
+        zero = (g == 0).reshape(-1, g.shape[-2], g.shape[-1]).all(dim=1).all(dim=0)
+        run = longest_zero_run(torch.where(zero, 0.0, 1.0).numpy())
+        if run is None or run[1] - run[0] < 4:
+            return None
+        return dsp.TF_HOP * run[0], dsp.TF_HOP * (run[1] - 3)  # t1 = run[1] - 1 inclusive: [256 t0, 256 (t1 - 2))
+
+    def dead_span(self, length):
+        if self._dead is None or dsp.tf_frames(length) != self.frames:
+            return None
+        s0, s1 = self._dead[0], min(self._dead[1], int(length))
+        return (s0, s1) if s1 > s0 else None
+
+    def _check(self, batch, length):
+        T = dsp.tf_frames(length)
+        if self.frames != T:
+            raise ValueError(f"TimeFrequencyMaskOperator holds a gain of shape {tuple(self.gain.shape)}; a clip of {length} samples needs "
+                             f"({dsp.TF_BINS}, {T}) = (513, ceil({length} / 256) + 3)")
+        if self.per_clip and self.gain.shape[0] != batch:
+            raise ValueError(f"TimeFrequencyMaskOperator holds {self.gain.shape[0]} per-clip gain(s) of shape ({dsp.TF_BINS}, {T}), the batch "
+                             f"has {batch} clip(s): expected ({batch}, {dsp.TF_BINS}, {T})")
+
+    def gain_on(self, device):
+        """The gain on `device` as the kernel reads it, (T, 513) or (B, T, 513) contiguous (one tensor, kept)."""
+        if self._gain_t is None or self._gain_t.device != device:
+            self._gain_t = self.gain.transpose(-1, -2).contiguous().to(device)
+        return self._gain_t
+
+    def forward(self, data, **kwargs):
+        self._check(data.shape[0], data.shape[-1])            # before the tensor has to be on the GPU
+        return super().forward(data, **kwargs)
+
+    def guidance(self, wav, length, measurement, supervised_space, **kw):
+        self._check(wav.shape[0], length)
+        return super().guidance(wav, length, measurement, supervised_space, **kw)
+
+    def apply(self, x, length, **kw):
+        self._check(x.shape[0], length)
+        h, g = self.frontend._h.value, self.gain_on(x.device)
+
+        def adjoint(dy, full):                                # A is symmetric: the transpose is A, zero-padded to `full`
+            return ops.hip.tf_gain(h, dy.contiguous(), g, int(length), int(full))
+        return ops.hip.tf_gain(h, x, g, int(length), int(length)), adjoint
+
+
 class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 (unrunnable in the reference: run.py:213-214)
     """Style guidance with BUILD-DEFINED semantics (the reference's `clap_model.get_gram_matrix`
     does not exist anywhere): `forward(x) = noiser(x)` (identity, operator.py:270-271) and

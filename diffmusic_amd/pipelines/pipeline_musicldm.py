@@ -21,7 +21,7 @@ from ..torch_utils import randn_tensor
 from ..profiling import stage
 from ..inverse_problem.noise import step_sigma
 from ..inverse_problem.mixture import MixtureOperator
-from ..inverse_problem.operator import BlindDereverberationOperator
+from ..inverse_problem.operator import BlindDereverberationOperator, TimeFrequencyMaskOperator
 from .. import parallel
 
 
@@ -453,6 +453,13 @@ class MusicLDMPipeline:
         op = self.scheduler.operator
         while hasattr(op, "inner"):                              # the measurement operator inside a track, a mixture, or both
             op = op.inner
+        if isinstance(op, TimeFrequencyMaskOperator) and op.per_clip:     # (one shared grid has no per-position state)
+            if int(self.lanes if lanes is None else lanes) > 1:
+                raise ValueError("TimeFrequencyMaskOperator with per-clip gains cannot run as clip lanes (lanes > 1): its gains are indexed "
+                                 "by batch position, and a lane sees only its own clips")
+            if shard or group is not None:
+                raise ValueError("TimeFrequencyMaskOperator with per-clip gains cannot be sharded over ranks (shard / group): its gains are "
+                                 "indexed by batch position, and a rank sees only its own clips")
         if not isinstance(op, BlindDereverberationOperator):
             return
         if int(self.lanes if lanes is None else lanes) > 1:

@@ -12,10 +12,15 @@ embedding file (`--prompt_embeds x.npy`, (B, 512) CLAP text embeddings for Music
     python examples/run_inverse_problem.py -c dps -t music_blind_dereverberation --wav room.wav        # the response is fitted, not given
     python examples/run_inverse_problem.py -c dps -t music_source_separation --wav drums.wav bass.wav --gains 1 0.5 --project
     python examples/run_inverse_problem.py -c dps -t music_source_separation --mixture song.wav --stems 4 --track_overlap_s 1.28
+    python examples/run_inverse_problem.py -c dps -t music_spectral_inpainting --tf_box 2000,4000,2,2.5 --hum 50,5      # a spectral hole + hum
 
 `--track_overlap_s S` restores a recording longer than the model window whole (track mode, inverse_problem/track.py): the first `--wav`
 (or a synthetic 2.5-window signal) becomes overlapping windows under one loss and one stitched file is written.  Without the flag a
 long `--wav` is cropped to the window as before.
+
+`-t music_spectral_inpainting` measures through a gain on the spectrogram (TimeFrequencyMaskOperator): `--tf_box f_lo,f_hi,t0,t1[,gain]`
+(Hz and seconds, an empty field = to the edge, gain 0 by default; repeatable, later boxes overwrite earlier ones) and `--hum
+f0[,harmonics[,width]]`; without either flag the boxes of configs/inverse_problem/music_spectral_inpainting.yaml are used.
 
 `-t music_source_separation` restores K stems from their mixture under one loss (inverse_problem/mixture.py), one prompt embedding per
 stem: `--wav` names the stems whose gain-weighted sum (`--gains`) is the measurement (SI-SDR per stem is printed), `--mixture mix.wav
@@ -39,14 +44,15 @@ from diffmusic_amd.pipelines import get_pipeline                                
 from diffmusic_amd.schedulers import get_scheduler                                  # noqa: E402
 
 TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation", "music_declipping",
-         "music_blind_dereverberation", "music_source_separation")
+         "music_blind_dereverberation", "music_source_separation", "music_spectral_inpainting")
 SEPARATION = "music_source_separation"
+SPECTRAL = "music_spectral_inpainting"
 
 
-def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None):
+def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None, tf_boxes=None):
     """run.py:157-212: one operator per task, constructor arguments from the data / model config.  `audio_length_in_s`: the length the
     operator acts on when it is not the model window (a track).  `clip_threshold`: music_declipping's threshold(s), a float or one value
-    per clip (`threshold_for_sdr` of the clean clips)."""
+    per clip (`threshold_for_sdr` of the clean clips).  `tf_boxes`: music_spectral_inpainting's boxes (`spectral_boxes`)."""
     noiser = P.get_noiser(**cfg.inverse_problem.noise)
     d, scale = cfg.data, 1
     seconds = cfg.model.pipe.audio_length_in_s if audio_length_in_s is None else audio_length_in_s
@@ -69,6 +75,11 @@ def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=
         if clip_threshold is None:
             raise ValueError("music_declipping needs clip_threshold (e.g. inverse_problem.threshold_for_sdr(clean, sdr_db))")
         op = P.DeclippingOperator(sample_rate=d.sample_rate, threshold=clip_threshold, noiser=noiser)
+    elif task == SPECTRAL:
+        if tf_boxes is None:
+            raise ValueError("music_spectral_inpainting needs tf_boxes (spectral_boxes(args, cfg))")
+        grid = P.tf_gain_grid(int(seconds * d.sample_rate), d.sample_rate, tf_boxes, base=float(cfg.inverse_problem.get("base", 1.0)))
+        op = P.TimeFrequencyMaskOperator(sample_rate=d.sample_rate, gain=grid, noiser=noiser)
     else:
         raise ValueError(f"Unknown task: {task}")
     return op, scale
@@ -141,8 +152,71 @@ def parse_args(argv=None):
     ap.add_argument("--gains", type=float, nargs="*", default=None, help="music_source_separation: one mixing gain per stem (default: all 1)")
     ap.add_argument("--mixture", default=None, help="music_source_separation: a real mixture to separate (then --stems K, no --wav)")
     ap.add_argument("--stems", type=int, default=None, help="music_source_separation: number of stems K (default: the number of --wav, else 2)")
+    ap.add_argument("--tf_box", action="append", default=None, metavar="F_LO,F_HI,T0,T1[,GAIN]",
+                    help="music_spectral_inpainting: a box of the spectrogram (Hz, seconds; empty field = to the edge) set to GAIN (default 0); repeatable")
+    ap.add_argument("--hum", default=None, metavar="F0[,HARMONICS[,WIDTH]]",
+                    help="music_spectral_inpainting: remove bands of WIDTH Hz (default 32) around F0 .. HARMONICS * F0 (default 1)")
     ap.add_argument("--strength", type=float, default=1.0, help="share of num_inference_steps a warm start runs (diffusers' img2img rule)")
     return ap.parse_args(argv)
+
+
+def _field(text, what):
+    text = text.strip()
+    if text == "" or text.lower() == "none":
+        return None
+    try:
+        v = float(text)
+    except ValueError:
+        raise SystemExit(f"{what}: {text!r} is not a number")
+    if not math.isfinite(v):
+        raise SystemExit(f"{what}: {text!r} is not finite")
+    return v
+
+
+def spectral_boxes(args, cfg=None):
+    """The argument rules of -t music_spectral_inpainting -> the boxes of `tf_gain_grid`, in order: --hum first, then every --tf_box; with
+    neither flag, the `hum` and `boxes` of the task's config.  Any other task refuses the two flags."""
+    if args.task != SPECTRAL:
+        for flag in ("tf_box", "hum"):
+            if getattr(args, flag) is not None:
+                raise SystemExit(f"--{flag} belongs to -t {SPECTRAL}")
+        return None
+    boxes = []
+    hum, tf_box = args.hum, args.tf_box
+    if hum is None and tf_box is None and cfg is not None:
+        ip = cfg.inverse_problem
+        hum = ",".join(str(v) for v in ip.get("hum")) if ip.get("hum") else None
+        tf_box = [",".join("" if v is None else str(v) for v in b) for b in (ip.get("boxes") or [])]
+    if hum is not None:
+        parts = hum.split(",")
+        if not 1 <= len(parts) <= 3:
+            raise SystemExit(f"--hum {hum}: F0[,HARMONICS[,WIDTH]]")
+        vals = [_field(p, "--hum") for p in parts]
+        if vals[0] is None or vals[0] <= 0:
+            raise SystemExit(f"--hum {hum}: F0 is a positive frequency in Hz")
+        harmonics = 1 if len(vals) < 2 or vals[1] is None else vals[1]
+        if harmonics != int(harmonics) or harmonics < 1:
+            raise SystemExit(f"--hum {hum}: HARMONICS is a whole number >= 1")
+        width = 32.0 if len(vals) < 3 or vals[2] is None else vals[2]
+        if width < 0:
+            raise SystemExit(f"--hum {hum}: WIDTH is a width in Hz, >= 0")
+        boxes += P.hum_boxes(vals[0], int(harmonics), width)
+    for text in tf_box or []:
+        parts = text.split(",")
+        if len(parts) not in (4, 5):
+            raise SystemExit(f"--tf_box {text}: F_LO,F_HI,T0,T1[,GAIN]")
+        f_lo, f_hi, t0, t1 = (_field(p, "--tf_box") for p in parts[:4])
+        gain = _field(parts[4], "--tf_box") if len(parts) == 5 else 0.0
+        if gain is None:
+            raise SystemExit(f"--tf_box {text}: GAIN is a number")
+        if f_lo is not None and f_hi is not None and f_lo > f_hi:
+            raise SystemExit(f"--tf_box {text}: F_LO > F_HI")
+        if t0 is not None and t1 is not None and t0 >= t1:
+            raise SystemExit(f"--tf_box {text}: T0 >= T1")
+        boxes.append((f_lo, f_hi, t0, t1, gain))
+    if not boxes:
+        raise SystemExit(f"-t {SPECTRAL} needs at least one --tf_box or --hum (or boxes in its config)")
+    return boxes
 
 
 def separation_stems(args):
@@ -233,12 +307,13 @@ def run_separation(args, cfg, K):
 def main(argv=None):
     args = parse_args(argv)
     overrides = [f"data={args.data}", f"model={args.model}"]
-    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION):
+    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL):
         overrides.append(f"inverse_problem={args.task}")
     stems = separation_stems(args)
     if args.project and args.task not in ("music_declipping", SEPARATION):
         raise SystemExit("--project is the output stage of -t music_declipping and -t music_source_separation")
     cfg = compose(args.config_name, overrides=overrides)
+    tf_boxes = spectral_boxes(args, cfg)
     if stems is not None:
         if args.model != "musicldm":
             raise SystemExit("this driver feeds MusicLDM's class-embedding conditioning; AudioLDM2 needs its T5 / GPT-2 states (see bench.py --workload)")
@@ -255,7 +330,7 @@ def main(argv=None):
     if args.track_overlap_s is None:
         gt = load_clips(args.wav, args.batch, sr, length, args.seed).to(device)
         thr = P.threshold_for_sdr(gt, args.clip_sdr_db) if args.task == "music_declipping" else None
-        op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr)
+        op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr, tf_boxes=tf_boxes)
         B = gt.shape[0]
     else:
         if args.task == "music_generation":
@@ -264,7 +339,8 @@ def main(argv=None):
         T = gt.shape[1]
         layout = P.TrackLayout(T, length, int(round(args.track_overlap_s * sr)))
         thr = float(P.threshold_for_sdr(gt, args.clip_sdr_db)[0]) if args.task == "music_declipping" else None
-        inner, scale = build_operator(args.task, cfg, args.mask_type, audio_length_in_s=P.seconds_for_samples(T, sr), clip_threshold=thr)
+        inner, scale = build_operator(args.task, cfg, args.mask_type, audio_length_in_s=P.seconds_for_samples(T, sr), clip_threshold=thr,
+                                      tf_boxes=tf_boxes)
         op = P.TrackOperator(inner, layout)
         B = layout.num_windows
         sched_kw["per_clip_norm"] = False                                          # one loss, norms over all windows

@@ -32,7 +32,8 @@ extern "C" {
  * dmx_track_stitch_fwd / dmx_track_stitch_bwd (track mode: overlapping windows as one sample) and dmx_audio_guidance_{fwd,bwd}_shaped /
  * dmx_clip_fwd / dmx_clip_bwd / dmx_declip_project (declipping: a hard clip inside and beside the guidance pair) and dmx_fir_clip_fwd /
  * dmx_fir_clip_bwd / dmx_fir_wgrad / dmx_fir_wgrad_workspace_floats / dmx_ir_update (blind dereverberation: one fitted response per clip)
- * and dmx_stem_mix_fwd / dmx_stem_mix_bwd / dmx_stem_project (source separation: the stems of a mixture as the batch) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * and dmx_stem_mix_fwd / dmx_stem_mix_bwd / dmx_stem_project (source separation: the stems of a mixture as the batch) and dmx_audio_tf_gain /
+ * dmx_audio_tf_frames (time-frequency masking: a real gain on the STFT) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
  * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
@@ -269,6 +270,16 @@ int dmx_audio_stft_mag(dmx_audio* a, const float* wav, long long wav_stride, flo
  * uses the spectrum the last dmx_audio_stft_mag left in `state` */
 int dmx_audio_stft_mag_bwd(dmx_audio* a, const float* dmag, float* dwav, long long dwav_stride, void* state, int batch, int L,
                            int accumulate, void* stream);
+/* Time-frequency gain (csrc/tf_gain.hip): out[b, 0:L] = A(x[b, 0:L]) and +0 on [L, full), where A multiplies the
+ * STFT of the zero-extended clip (n_fft 1024, hop 256, periodic Hann, frames = ceil(L / 256) + 3, frame t at sample (t - 3) * 256) by the real
+ * gain and resynthesises by windowed overlap-add divided by c = 1.5.  A is symmetric: the same call is its transpose.  gain: (frames, 513)
+ * fp32 rows per clip -- bins contiguous -- with gain_clip_stride floats between clips, 0 = one grid for every clip.  Uses the handle's
+ * twiddle and window tables: the handle must have n_fft = 1024 and the Hann window.  One launch, no workspace, bit-reproducible.
+ * DMX_ERR_SHAPE, with nothing written, for any other handle, L < 1, full < L, x_stride < L, out_stride < full, a non-zero
+ * gain_clip_stride < frames * 513, or a null pointer.  dmx_audio_tf_frames(L) = ceil(L / 256) + 3 (0 for L < 1). */
+int dmx_audio_tf_frames(int L);
+int dmx_audio_tf_gain(dmx_audio* a, const float* x, long long x_stride, const float* gain, long long gain_clip_stride, float* out,
+                      long long out_stride, int batch, int L, int full, void* stream);
 /* PhaseRetrievalOperator.transform on a given magnitude (B, bins, frames) -> (B, frames, n_mels) */
 int dmx_audio_melscale(dmx_audio* a, const float* mag, float* mel_out, int batch, int frames, float lo, float hi, void* stream);
 /* MusicInpaintingOperator.forward (operator.py:132-133): y[b,t] = x[b,t]*mask[t] (t<L), 0 for L<=t<Ly; mask NULL = copy */
