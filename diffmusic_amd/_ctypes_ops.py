@@ -305,6 +305,46 @@ def tf_gain(audio, x, gain_t, L, Lfull, *, out=None):
     return out
 
 
+def tf_curve(audio, x, curve, L, Lfull):
+    """x (B, >= L) with any row stride, curve (513,) shared or (B, 513) -> (B, Lfull): `tf_gain` with a gain constant in time, every frame
+    reading the clip's one row (csrc/tf_gain.hip, frame stride 0), +0 past L.  Symmetric: the same call is the transpose."""
+    _rows("tf_curve", x, L)
+    B = x.shape[0]
+    assert Lfull >= L, (L, Lfull)
+    assert curve.is_cuda and curve.dtype == torch.float32 and curve.is_contiguous() and curve.device == x.device and \
+        tuple(curve.shape) in ((513,), (B, 513)), ("tf_curve", tuple(curve.shape), (B, 513))
+    out = torch.empty(B, Lfull, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_audio_tf_curve(audio, _p(x), x.stride(0), _p(curve), 513 if curve.dim() == 2 else 0, _p(out), Lfull, B, L, Lfull,
+                                             _stream()), "tf_curve")
+    return out
+
+
+def tf_wgrad(audio, dy, x, L):
+    """The gradient of a loss in the curve as partial sums: dy = dLoss/dy and x, both (B, >= L) with any row stride -> (B, segments, 513);
+    row s holds the terms of frames [16 s, 16 s + 16), dg = the sum over s (`eq_update` adds the rows in order)."""
+    _rows("tf_wgrad", x, L)
+    _rows("tf_wgrad", dy, L)
+    B = x.shape[0]
+    assert dy.shape[0] == B and dy.device == x.device, (dy.shape, x.shape)
+    lib = _lib.lib()
+    part = torch.empty(B, lib.dmx_audio_tf_wgrad_segments(L), 513, dtype=torch.float32, device=x.device)
+    _lib.check(lib.dmx_audio_tf_wgrad(audio, _p(x), x.stride(0), _p(dy), dy.stride(0), _p(part), B, L, _stream()), "tf_wgrad")
+    return part
+
+
+def eq_update(partials, g, m, v, k, lr, beta1, beta2, eps, peak):
+    """One Adam step on the curves from the partial rows of `tf_wgrad`, the clamp at zero, then g <- g / max g per clip when `peak`; g, m,
+    v (B, 513) are updated IN PLACE, k is the 1-based count of updates since the last reset.  A clip whose gradient or step is not finite,
+    or whose peak would be zero, keeps its state."""
+    assert partials.is_cuda and partials.dtype == torch.float32 and partials.dim() == 3 and partials.is_contiguous() and \
+        partials.shape[2] == 513, partials.shape
+    B, segments, n = partials.shape
+    for t in (g, m, v):
+        assert _taps("eq_update", t, B) == n and t.device == partials.device, (t.shape, partials.shape)
+    _lib.check(_lib.lib().dmx_audio_eq_update(_p(partials), segments, _p(g), _p(m), _p(v), B, int(k), float(lr), float(beta1), float(beta2),
+                                              float(eps), 1 if peak else 0, _stream()), "eq_update")
+
+
 def noise_add(y, noise, sigma):
     """-> y + sigma * noise (new tensor; y and noise contiguous, same number of elements)."""
     assert y.is_contiguous() and noise.is_contiguous() and y.numel() == noise.numel(), (y.shape, noise.shape)

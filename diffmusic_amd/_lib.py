@@ -173,6 +173,11 @@ _SIGS = {
     "dmx_audio_tf_frames": (C.c_int, [C.c_int]),
     "dmx_audio_tf_gain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p]),
+    "dmx_audio_tf_curve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p]),
+    "dmx_audio_tf_wgrad_segments": (C.c_int, [C.c_int]),
+    "dmx_audio_tf_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dmx_audio_eq_update": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_void_p]),
     "dmx_audio_melscale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
     "dmx_mask_apply": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dmx_l2_loss": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_void_p]),
@@ -203,7 +208,8 @@ ADDED_IN_V4 = ("dmx_vae_encoder_create", "dmx_vae_encoder_workspace_bytes", "dmx
                "dmx_track_stitch_fwd", "dmx_track_stitch_bwd", "dmx_audio_guidance_fwd_shaped", "dmx_audio_guidance_bwd_shaped",
                "dmx_clip_fwd", "dmx_clip_bwd", "dmx_declip_project", "dmx_hifigan_fwd_dead", "dmx_hifigan_dead_plan", "dmx_conv_dead_rows",
                "dmx_fir_clip_fwd", "dmx_fir_clip_bwd", "dmx_fir_wgrad", "dmx_fir_wgrad_workspace_floats", "dmx_ir_update",
-               "dmx_stem_mix_fwd", "dmx_stem_mix_bwd", "dmx_stem_project", "dmx_audio_tf_gain", "dmx_audio_tf_frames")
+               "dmx_stem_mix_fwd", "dmx_stem_mix_bwd", "dmx_stem_project", "dmx_audio_tf_gain", "dmx_audio_tf_frames",
+               "dmx_audio_tf_curve", "dmx_audio_tf_wgrad_segments", "dmx_audio_tf_wgrad", "dmx_audio_eq_update")
 
 _lib = None
 
@@ -213,7 +219,7 @@ def check_symbols(h, path=LIB_PATH):
     for name in ADDED_IN_V4:
         if not hasattr(h, name):
             raise RuntimeError(f"{path} reports ABI version {ABI_VERSION} but does not export `{name}` (a build from before the VAE "
-                               "encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking entry points): rebuild it (python -m diffmusic_amd.build --force)")
+                               "encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation entry points): rebuild it (python -m diffmusic_amd.build --force)")
 
 
 def lib():

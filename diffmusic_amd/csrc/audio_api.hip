@@ -207,8 +207,34 @@ int dmx_audio_tf_gain(dmx_audio* a, const float* x, long long x_stride, const fl
                   "with clip stride 0 (shared) or >= frames * 513, frames = ceil(L / 256) + 3, 1 <= batch <= 65535");
     return DMX_ERR_SHAPE;
   }
-  const int rc = dmx_tf_gain(a->ft, x, x_stride, gain, gain_clip_stride, out, out_stride, batch, L, full, ST(stream));
+  const int rc = dmx_tf_gain(a->ft, x, x_stride, gain, gain_clip_stride, a->bins, out, out_stride, batch, L, full, ST(stream));
   if (rc == DMX_ERR_SHAPE) dmx_set_error("tf_gain: clip too long");
+  return rc;
+}
+int dmx_audio_tf_curve(dmx_audio* a, const float* x, long long x_stride, const float* curve, long long curve_clip_stride, float* out,
+                       long long out_stride, int batch, int L, int full, void* stream) {
+  if (!a || !x || !curve || !out) { dmx_set_error("tf_curve: null handle or pointer"); return DMX_ERR_SHAPE; }
+  if (a->n_fft != 1024 || !a->hann || !a->fused) { dmx_set_error("tf_curve needs a handle with n_fft = 1024 and the Hann window"); return DMX_ERR_SHAPE; }
+  if (batch < 1 || batch > 65535 || L < 1 || full < L || x_stride < L || out_stride < full || (curve_clip_stride != 0 && curve_clip_stride < a->bins)) {
+    dmx_set_error("tf_curve: x (batch, >= L), out (batch, full) with row strides >= L and >= full, 1 <= L <= full, curve (513) per clip with clip "
+                  "stride 0 (shared) or >= 513, 1 <= batch <= 65535");
+    return DMX_ERR_SHAPE;
+  }
+  const int rc = dmx_tf_gain(a->ft, x, x_stride, curve, curve_clip_stride, 0, out, out_stride, batch, L, full, ST(stream));
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("tf_curve: clip too long");
+  return rc;
+}
+int dmx_audio_tf_wgrad_segments(int L) { return L < 1 ? 0 : dmx_tf_wgrad_segments(L); }
+int dmx_audio_tf_wgrad(dmx_audio* a, const float* x, long long x_stride, const float* dy, long long dy_stride, float* partials, int batch, int L,
+                       void* stream) {
+  if (!a || !x || !dy || !partials) { dmx_set_error("tf_wgrad: null handle or pointer"); return DMX_ERR_SHAPE; }
+  if (a->n_fft != 1024 || !a->hann || !a->fused) { dmx_set_error("tf_wgrad needs a handle with n_fft = 1024 and the Hann window"); return DMX_ERR_SHAPE; }
+  if (batch < 1 || batch > 65535 || L < 1 || x_stride < L || dy_stride < L) {
+    dmx_set_error("tf_wgrad: x and dy (batch, >= L) with row strides >= L, L >= 1, 1 <= batch <= 65535; partials (batch, segments, 513)");
+    return DMX_ERR_SHAPE;
+  }
+  const int rc = dmx_tf_wgrad(a->ft, x, x_stride, dy, dy_stride, partials, batch, L, ST(stream));
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("tf_wgrad: clip too long");
   return rc;
 }
 int dmx_audio_melscale(dmx_audio* a, const float* mag, float* mel_out, int batch, int T, float lo, float hi, void* stream) {

@@ -14,6 +14,7 @@
 #include <cmath>
 #include "dmx_common.h"
 #include "kernels.h"
+#include "adam_step.h"
 #include "../../include/diffmusic_hip.h"
 void dmx_set_error(const char* fmt, ...);
 
@@ -59,17 +60,6 @@ __global__ __launch_bounds__(WT) void fir_wgrad_kernel(const float* __restrict__
     const int t = t0 + WR * threadIdx.x + r;
     if (t < taps) row[t] = acc[r];
   }
-}
-
-// One Adam step of one tap, every operation rounded on its own (no contraction: the two passes of the update must agree bit for bit)
-struct AdamStep {                                            // host scalars of one step, each rounded to fp32 from its float64 value
-  float lr, b1, b2, omb1, omb2, eps, bc1, bc2;               // omb = 1 - beta, bc = 1 - beta^k (1 - 0.999f would be off by 1e-5 of itself)
-};
-__device__ __forceinline__ void adam_tap(float g, float m, float v, float h, const AdamStep& a, float& mn, float& vn, float& hn) {
-#pragma clang fp contract(off)
-  mn = a.b1 * m + a.omb1 * g;
-  vn = a.b2 * v + (a.omb2 * g) * g;
-  hn = h - a.lr * (mn / a.bc1) / (sqrtf(vn / a.bc2) + a.eps);
 }
 
 // One workgroup per clip: g = the partial rows summed in segment order, Adam, max|h'| over the clip, h = h' / max|h'| and its reverse.
@@ -159,12 +149,11 @@ extern "C" int dmx_ir_update(const float* partials, int segments, float* h, floa
     dmx_set_error("ir_update: %d taps, one workgroup per clip covers at most %d", taps, UMAX);
     return DMX_ERR_SHAPE;
   }
-  if (!(lr > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || k < 1) {
+  if (!adam_args_ok(lr, beta1, beta2, eps, k)) {
     dmx_set_error("ir_update: lr > 0, betas in [0, 1), eps >= 0 and k >= 1 (the 1-based count of updates) are required");
     return DMX_ERR_SHAPE;
   }
-  const AdamStep a = {(float)lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
-                      (float)(1.0 - std::pow(beta1, (double)k)), (float)(1.0 - std::pow(beta2, (double)k))};
+  const AdamStep a = adam_step_of(lr, beta1, beta2, eps, k);
   hipLaunchKernelGGL(ir_update_kernel, dim3((unsigned)batch), dim3(UT), 0, (hipStream_t)stream, partials, segments, h, h_rev, m, v, taps, a);
   return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
 }

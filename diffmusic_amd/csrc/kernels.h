@@ -100,8 +100,15 @@ int dmx_stft_mel_bwd(const DmxStftMelTables& t, const float* wav, long long wav_
 // ---- tf_gain.hip (time-frequency gain: STFT at hop 256 with zero extension, real gain per bin and frame, inverse STFT; n_fft = 1024, Hann)
 int dmx_tf_gain_frames(int L);                           // ceil(L / 256) + 3
 // out[b, 0:L] = A(x[b, 0:L]), +0 on [L, full); gain (T, 513) rows per clip, clip stride 0 = one grid for every clip; uses t.tw and t.win
-int dmx_tf_gain(const DmxStftMelTables& t, const float* x, long long x_stride, const float* gain, long long gain_clip_stride, float* out,
-                long long out_stride, int B, int L, int full, hipStream_t st);
+// gain_frame_stride: 513 = a grid, 0 = one 513-row per clip that every frame reads (clip stride then 0 or >= 513)
+int dmx_tf_gain(const DmxStftMelTables& t, const float* x, long long x_stride, const float* gain, long long gain_clip_stride,
+                long long gain_frame_stride, float* out, long long out_stride, int B, int L, int full, hipStream_t st);
+
+// ---- tf_eq.hip (blind equalisation: the gradient of a loss in a time-invariant gain curve g[513], and its Adam + projection update)
+int dmx_tf_wgrad_segments(int L);                        // ceil(frames / 16)
+// part[b, seg, 0:513] = the terms of frames [16 seg, 16 seg + 16) of dg[b, k] = (h_k / 1536) sum_t Re(X[k, t] conj(U[k, t])); uses t.tw, t.win
+int dmx_tf_wgrad(const DmxStftMelTables& t, const float* x, long long x_stride, const float* dy, long long dy_stride, float* part, int B, int L,
+                 hipStream_t st);
 
 // ---- sched.hip
 int dmx_pred_x0(const float* x, const float* eps, float* x0, long long n, float sqrt_a, float sqrt_1ma, hipStream_t st);

@@ -17,7 +17,9 @@
 // Only the slab's own samples below L are written; the last slab of a clip writes +0.0f to out[b, L : full).
 //
 // gain is read as (T, 513) rows (lane = bin: 256-byte reads); clip stride 0 = one grid for every clip.  The public layout of the operator
-// stays (513, T); it keeps the transposed device copy (inverse_problem/operator.py, TimeFrequencyMaskOperator).
+// stays (513, T); it keeps the transposed device copy (inverse_problem/operator.py, TimeFrequencyMaskOperator).  The distance between the
+// gain rows of consecutive frames is a parameter: 513 for a grid, 0 for ONE 513-row that every frame reads (a gain constant in time, the
+// equalisation curve of BlindEqualizationOperator).  Only the address changes, no arithmetic.
 #include "dmx_common.h"
 #include "kernels.h"
 #include "fft1024.h"
@@ -36,6 +38,7 @@ constexpr float INV_C = 2.f / 3.f;       // 1 / c, c = 1.5 (rounded once)
 struct TfParams {
   const float* x; long long x_stride;
   const float* gain; long long gain_stride;   // (T, 513) rows; clip stride 0 = shared
+  long long gain_frame_stride;                // floats between the rows of consecutive frames: 513, or 0 = one row for every frame
   float* out; long long out_stride;
   int L, full, T, H;                    // H = ceil(L / 256) output hops
   const float2* tw;
@@ -85,7 +88,7 @@ __global__ __launch_bounds__(256) void tf_gain_kernel(const TfParams P) {
     if (t + 4 < t1) tf_fetch(xr, L, t + 4, xs, lane);      // in flight under this frame's two FFTs
     fft1024<false>(buf, s_tw, lane);
     // Y[k] = G[k, t] X[k] on the one-sided bins (read from the lower half only), conjugates into the upper half
-    const float* g = gr + (long long)t * NB;
+    const float* g = gr + (long long)t * P.gain_frame_stride;
 #pragma unroll
     for (int j = 0; j < 9; ++j) {
       const int k = lane + 64 * j;
@@ -121,14 +124,15 @@ __global__ __launch_bounds__(256) void tf_gain_kernel(const TfParams P) {
 
 int dmx_tf_gain_frames(int L) { return cdiv(L, HOP) + HALO; }
 
-int dmx_tf_gain(const DmxStftMelTables& t, const float* x, long long x_stride, const float* gain, long long gain_clip_stride, float* out,
-                long long out_stride, int B, int L, int full, hipStream_t st) {
+int dmx_tf_gain(const DmxStftMelTables& t, const float* x, long long x_stride, const float* gain, long long gain_clip_stride,
+                long long gain_frame_stride, float* out, long long out_stride, int B, int L, int full, hipStream_t st) {
   if (!x || !gain || !out || B < 1 || B > 65535 || L < 1 || full < L || L > 0x7fffffff - 2 * NF || x_stride < L || out_stride < full) return DMX_ERR_SHAPE;
   const int T = dmx_tf_gain_frames(L);
-  if (gain_clip_stride != 0 && gain_clip_stride < (long long)T * NB) return DMX_ERR_SHAPE;
+  if (gain_frame_stride != 0 && gain_frame_stride != NB) return DMX_ERR_SHAPE;
+  if (gain_clip_stride != 0 && gain_clip_stride < (gain_frame_stride ? (long long)T * NB : (long long)NB)) return DMX_ERR_SHAPE;
   TfParams P;
   memset(&P, 0, sizeof(P));
-  P.x = x; P.x_stride = x_stride; P.gain = gain; P.gain_stride = gain_clip_stride; P.out = out; P.out_stride = out_stride;
+  P.x = x; P.x_stride = x_stride; P.gain = gain; P.gain_stride = gain_clip_stride; P.gain_frame_stride = gain_frame_stride; P.out = out; P.out_stride = out_stride;
   P.L = L; P.full = full; P.T = T; P.H = T - HALO; P.tw = t.tw; P.win = t.win;
   hipLaunchKernelGGL(tf_gain_kernel, dim3(cdiv(P.H, SLAB_HOPS), B), dim3(256), 0, st, P);
   return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;

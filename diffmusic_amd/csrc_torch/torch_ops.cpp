@@ -40,6 +40,10 @@
 #pragma weak dmx_stem_project
 #pragma weak dmx_audio_tf_gain
 #pragma weak dmx_audio_tf_frames
+#pragma weak dmx_audio_tf_curve
+#pragma weak dmx_audio_tf_wgrad_segments
+#pragma weak dmx_audio_tf_wgrad
+#pragma weak dmx_audio_eq_update
 
 namespace {
 
@@ -371,6 +375,42 @@ at::Tensor tf_gain(int64_t audio, const at::Tensor& x, const at::Tensor& gain_t,
                        out.data_ptr<float>(), Lfull, (int)B, (int)L, (int)Lfull, cur_stream()), "tf_gain");
   return out;
 }
+// blind equalisation (include/diffmusic_hip.h dmx_audio_tf_curve / dmx_audio_tf_wgrad / dmx_audio_eq_update): one gain curve per clip
+at::Tensor tf_curve(int64_t audio, const at::Tensor& x, const at::Tensor& curve, int64_t L, int64_t Lfull) {
+  rows_ok(x, L, "x");
+  TORCH_CHECK(Lfull >= L, "Lfull must be >= L");
+  DMX_DEVICE_OF(x);
+  f32_cuda(curve, "curve");
+  const int64_t B = x.size(0);
+  TORCH_CHECK(curve.device() == x.device() && ((curve.dim() == 1 && curve.size(0) == 513) ||
+              (curve.dim() == 2 && curve.size(0) == B && curve.size(1) == 513)), "curve must be (513) or (", B, ", 513) on x's device");
+  at::Tensor out = at::empty({B, Lfull}, x.options());
+  ok(dmx_audio_tf_curve((dmx_audio*)audio, x.data_ptr<float>(), x.stride(0), curve.data_ptr<float>(), curve.dim() == 2 ? 513 : 0,
+                        out.data_ptr<float>(), Lfull, (int)B, (int)L, (int)Lfull, cur_stream()), "tf_curve");
+  return out;
+}
+at::Tensor tf_wgrad(int64_t audio, const at::Tensor& dy, const at::Tensor& x, int64_t L) {
+  rows_ok(x, L, "x");
+  rows_ok(dy, L, "dy");
+  TORCH_CHECK(dy.size(0) == x.size(0) && dy.device() == x.device(), "tf_wgrad: dy and x must be (B, >= L) on one device");
+  DMX_DEVICE_OF(x);
+  const int64_t B = x.size(0);
+  at::Tensor part = at::empty({B, (int64_t)dmx_audio_tf_wgrad_segments((int)L), 513}, x.options());
+  ok(dmx_audio_tf_wgrad((dmx_audio*)audio, x.data_ptr<float>(), x.stride(0), dy.data_ptr<float>(), dy.stride(0), part.data_ptr<float>(), (int)B,
+                        (int)L, cur_stream()), "tf_wgrad");
+  return part;
+}
+void eq_update(const at::Tensor& partials, at::Tensor g, at::Tensor m, at::Tensor v, int64_t k, double lr, double beta1, double beta2, double eps,
+               bool peak) {
+  f32_cuda(partials, "partials");
+  TORCH_CHECK(partials.dim() == 3 && partials.size(2) == 513, "partials must be (B, segments, 513)");
+  DMX_DEVICE_OF(partials);
+  const int64_t B = partials.size(0);
+  TORCH_CHECK(taps_of(g, partials, B, "g") == 513 && taps_of(m, partials, B, "m") == 513 && taps_of(v, partials, B, "v") == 513,
+              "eq_update: g, m and v must be (B, 513) like the partial rows");
+  ok(dmx_audio_eq_update(partials.data_ptr<float>(), (int)partials.size(1), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), (int)B,
+                         (int)k, lr, beta1, beta2, eps, peak ? 1 : 0, cur_stream()), "eq_update");
+}
 at::Tensor noise_add(const at::Tensor& y, const at::Tensor& noise, double sigma) {
   f32_cuda(y, "y"); f32_cuda(noise, "noise");
   same_numel(y, noise, "noise_add(y, noise)");
@@ -664,10 +704,14 @@ TORCH_LIBRARY(diffmusic_hip, m) {
                                                          {"dmx_stem_mix_bwd", (const void*)&dmx_stem_mix_bwd},
                                                          {"dmx_stem_project", (const void*)&dmx_stem_project},
                                                          {"dmx_audio_tf_gain", (const void*)&dmx_audio_tf_gain},
-                                                         {"dmx_audio_tf_frames", (const void*)&dmx_audio_tf_frames}};
+                                                         {"dmx_audio_tf_frames", (const void*)&dmx_audio_tf_frames},
+                                                         {"dmx_audio_tf_curve", (const void*)&dmx_audio_tf_curve},
+                                                         {"dmx_audio_tf_wgrad_segments", (const void*)&dmx_audio_tf_wgrad_segments},
+                                                         {"dmx_audio_tf_wgrad", (const void*)&dmx_audio_tf_wgrad},
+                                                         {"dmx_audio_eq_update", (const void*)&dmx_audio_eq_update}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
-                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking entry points): rebuild with `python -m diffmusic_amd.build --force`");
+                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation entry points): rebuild with `python -m diffmusic_amd.build --force`");
   }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
@@ -701,6 +745,10 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("declip_project(Tensor wav, Tensor measurement, Tensor thr, int L) -> Tensor", &declip_project);
   m.def("noise_add(Tensor y, Tensor noise, float sigma) -> Tensor", &noise_add);
   m.def("tf_gain(int audio, Tensor x, Tensor gain_t, int L, int Lfull) -> Tensor", &tf_gain);
+  m.def("tf_curve(int audio, Tensor x, Tensor curve, int L, int Lfull) -> Tensor", &tf_curve);
+  m.def("tf_wgrad(int audio, Tensor dy, Tensor x, int L) -> Tensor", &tf_wgrad);
+  m.def("eq_update(Tensor partials, Tensor(a!) g, Tensor(b!) m, Tensor(c!) v, int k, float lr, float beta1, float beta2, float eps, bool peak) "
+        "-> ()", &eq_update);
   m.def("track_stitch_fwd(Tensor wav, int[] starts, int L, int R, int T) -> Tensor", &track_stitch_fwd);
   m.def("track_stitch_bwd(Tensor dtrack, int[] starts, int L, int R, int Lfull) -> Tensor", &track_stitch_bwd);
   m.def("stem_mix_fwd(Tensor wav, float[]? gains, int K, int G, int L) -> Tensor", &stem_mix_fwd);

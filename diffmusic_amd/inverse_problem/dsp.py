@@ -110,3 +110,26 @@ def hum_boxes(f0_hz, harmonics=1, width_hz=32.0, gain=0.0):
     if not (math.isfinite(f0_hz) and f0_hz > 0) or harmonics < 1 or not (math.isfinite(width_hz) and width_hz >= 0):
         raise ValueError(f"hum_boxes({f0_hz!r}, {harmonics!r}, {width_hz!r}): a positive frequency, at least one harmonic, a width >= 0")
     return [(m * f0_hz - 0.5 * width_hz, m * f0_hz + 0.5 * width_hz, None, None, float(gain)) for m in range(1, harmonics + 1)]
+
+
+# ---- blind equalisation (BlindEqualizationOperator; csrc/tf_eq.hip): a gain per bin, constant in time; bin k sits at k * sample_rate / 1024
+def eq_curve(sample_rate, points):
+    """(513,) fp32 gain curve through (frequency_hz, gain_db) breakpoints: linear in dB over log-frequency between them, flat beyond the
+    first and the last (DC included).  Frequencies positive and strictly increasing."""
+    pts = [(float(f), float(db)) for f, db in points]
+    if not pts or not all(math.isfinite(f) and f > 0 and math.isfinite(db) for f, db in pts) or \
+            any(b[0] <= a[0] for a, b in zip(pts, pts[1:])):
+        raise ValueError(f"eq_curve points {points!r}: at least one (hz, dB) pair, finite, frequencies positive and strictly increasing")
+    freq = np.arange(TF_BINS, dtype=np.float64) * float(sample_rate) / TF_N_FFT
+    logf = np.log(np.maximum(freq, pts[0][0]))               # below the first breakpoint (and at DC): its value
+    db = np.interp(logf, np.log([f for f, _ in pts]), [d for _, d in pts])
+    return (10.0 ** (db / 20.0)).astype(np.float32)
+
+
+def lowpass_curve(sample_rate, cutoff_hz, order=4):
+    """(513,) fp32 magnitude of a Butterworth low-pass: 1 / sqrt(1 + (f / cutoff_hz)^(2 * order)), f = k * sample_rate / 1024."""
+    cutoff_hz, order = float(cutoff_hz), int(order)
+    if not (math.isfinite(cutoff_hz) and cutoff_hz > 0) or order < 1:
+        raise ValueError(f"lowpass_curve({cutoff_hz!r}, order={order!r}): a positive cut-off and an order >= 1")
+    freq = np.arange(TF_BINS, dtype=np.float64) * float(sample_rate) / TF_N_FFT
+    return (1.0 / np.sqrt(1.0 + (freq / cutoff_hz) ** (2 * order))).astype(np.float32)

@@ -805,6 +805,135 @@ class TimeFrequencyMaskOperator(_MelOperator):
         return ops.hip.tf_gain(h, x, g, int(length), int(length)), adjoint
 
 
+class BlindEqualizationOperator(_MelOperator):
+    """Equalisation with an UNKNOWN curve (extension): the time-frequency gain of `TimeFrequencyMaskOperator` constant in time, G[k, t] =
+    g[k] -- a tape or microphone colouration, a low-pass at an unknown cut-off, a tone control -- with one estimate g[b] per clip
+    (`eq_estimate`, (B, 513) fp32 on the GPU) fitted inside the guided loop, the way `BlindDereverberationOperator` fits its response.
+
+        A_g = (1 / c) P^T W F^-1 diag(g) F W P      n_fft 1024, hop 256, periodic Hann, the clip ZERO outside [0, L), c = 1.5; A_1 = I
+
+    One `guidance` call computes the loss and the gradient w.r.t. the audio with the current estimate g_k, then takes one Adam step on
+    the curve from the same cotangent dy: dg[b, k] = (h_k / 1536) sum_t Re(X[k, t] conj(U[k, t])) with X, U the STFTs of x and dy, the
+    clamp at zero (a magnitude response is not negative) and, with normalize="peak", g <- g / max g, which pins the scale ambiguity between
+    g and x.  All of it is HIP: `tf_curve` (csrc/tf_gain.hip with frame stride 0; A is symmetric, the adjoint is the same op), `tf_wgrad`
+    and `eq_update` (csrc/tf_eq.hip).  A clip whose gradient or step is not finite keeps its estimate and moments.
+
+    forward(data, curve=None) makes the measurement with the TRUE curve ((513,) or (B, 513)) and keeps it as `true_curve` (B, 513); with
+    neither an argument nor a kept curve it raises a ValueError (`dsp.eq_curve` and `dsp.lowpass_curve` build one).
+    init: "flat" (g = 1: A = identity) or a (513,) / (B, 513) tensor, finite and non-negative; with normalize="peak" it needs a positive
+    peak and is peak-normalised per row.  reset_cache() (every `set_timesteps`) and restart() (NaN-retry) put the estimate back to `init`,
+    zero the moments and set k = 0, so two identical pipeline calls give the same bits.  `guidance(..., update_eq=False)` (through the
+    scheduler: `op_kwargs=dict(update_eq=False)`) freezes the estimate; `curve=` pins the curve of one call and never updates.
+
+    The model is a real, non-negative, time-invariant curve, hence zero-phase: the mel loss cannot tell it from a minimum-phase filter of the
+    same magnitude.  The state is indexed by batch position, so the pipelines refuse `lanes > 1` and `shard=True`; inside a TrackOperator
+    the batch is the one track.  dead_span stays None: the estimate moves.  k, the count of updates since the last reset, is kept on the
+    host and shared by the clips."""
+
+    def __init__(self, sample_rate=16000, noiser=None, lr=0.05, betas=(0.9, 0.999), adam_eps=1e-8, init="flat", normalize="peak"):
+        if not (isinstance(lr, (int, float)) and math.isfinite(lr) and lr > 0):
+            raise ValueError(f"lr = {lr!r}: a positive number")
+        if len(betas) != 2 or not all(isinstance(b, (int, float)) and 0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"betas = {betas!r}: two numbers in [0, 1)")
+        if not (isinstance(adam_eps, (int, float)) and math.isfinite(adam_eps) and adam_eps >= 0):
+            raise ValueError(f"adam_eps = {adam_eps!r}: a non-negative number")
+        if normalize not in ("peak", "none"):
+            raise ValueError(f"normalize = {normalize!r}: 'peak' or 'none'")
+        n = dsp.TF_BINS
+        self.sample_rate, self.noiser, self.normalize = sample_rate, noiser, normalize
+        self.lr, self.betas, self.adam_eps = float(lr), (float(betas[0]), float(betas[1])), float(adam_eps)
+        if isinstance(init, str):
+            if init != "flat":
+                raise ValueError(f"init = {init!r}: 'flat' or a ({n},) / (B, {n}) tensor")
+            start = torch.ones(1, n)
+        else:
+            start = torch.as_tensor(init, dtype=torch.float32).detach().cpu()
+            if start.dim() not in (1, 2) or start.shape[-1] != n or start.numel() == 0:
+                raise ValueError(f"init has shape {tuple(start.shape)}: ({n},) or (B, {n})")
+            start = start.reshape(-1, n).clone()
+            if not bool(torch.isfinite(start).all()) or not bool((start >= 0).all()):
+                raise ValueError("init: finite, non-negative curves")
+            if normalize == "peak":
+                peak = start.amax(dim=1, keepdim=True)
+                if not bool((peak > 0).all()):
+                    raise ValueError("init: curves with a positive peak (normalize = 'peak')")
+                start = start / peak
+        self._start = start                                   # host, (1, 513) for every clip or (B, 513)
+        self.true_curve = None
+        self._g = self._m = self._v = None
+        self.k = 0
+        self._init_mel(sample_rate, lazy=True)
+
+    # ---- the estimate and its optimiser state
+    def _rows(self, curve, batch, what):
+        """(513,) / (1, 513) / (batch, 513) -> host (batch, 513) fp32."""
+        curve = torch.as_tensor(curve).detach().to(device="cpu", dtype=torch.float32)
+        if curve.dim() not in (1, 2) or curve.shape[-1] != dsp.TF_BINS or curve.numel() == 0:
+            raise ValueError(f"{what} has shape {tuple(curve.shape)}: ({dsp.TF_BINS},) or (B, {dsp.TF_BINS})")
+        curve = curve.reshape(-1, dsp.TF_BINS)
+        if curve.shape[0] not in (1, batch):
+            raise ValueError(f"{what} holds {curve.shape[0]} curve(s), the batch has {batch} clip(s)")
+        return curve.expand(batch, dsp.TF_BINS)
+
+    def _state(self, batch, device):
+        """The (batch, 513) estimate with its Adam moments on `device`; made from `init` on first use and when the batch changes."""
+        if self._g is None or self._g.shape[0] != batch or self._g.device != device:
+            self._g = self._rows(self._start, batch, "init").to(device).contiguous()
+            self._m, self._v = torch.zeros_like(self._g), torch.zeros_like(self._g)
+            self.k = 0
+        return self._g
+
+    @property
+    def eq_estimate(self):
+        """(B, 513) fp32 on the GPU, updated in place by every guided step; None before the first call has fixed the batch."""
+        return self._g
+
+    def _to_start(self):
+        if self._g is not None:
+            self._g.copy_(self._rows(self._start, self._g.shape[0], "init"))
+            self._m.zero_()
+            self._v.zero_()
+        self.k = 0
+
+    def reset_cache(self):
+        super().reset_cache()
+        self._to_start()
+
+    def restart(self):
+        self._to_start()
+
+    # ---- A
+    def forward(self, data, curve=None, **kwargs):
+        B = data.shape[0]
+        if curve is None:
+            if self.true_curve is None:
+                raise ValueError("BlindEqualizationOperator.forward needs the true curve of the measurement: curve=(513,) or (B, 513) "
+                                 "(dsp.eq_curve / dsp.lowpass_curve build one); none was given and none is kept")
+            curve = self._rows(self.true_curve, B, "true_curve")
+        else:
+            curve = self.true_curve = self._rows(curve, B, "curve").clone()
+        return super().forward(data, curve=curve, **kwargs)
+
+    def apply(self, x, length, curve=None, update_eq=True, **kw):
+        """curve: the curve(s) of this call instead of the estimate ((513,) or (B, 513)); the estimate is then neither used nor updated."""
+        B = x.shape[0]
+        g = self._state(B, x.device) if curve is None else self._rows(curve, B, "curve").to(x.device).contiguous()
+        h = self.frontend._h.value
+
+        def adjoint(dy, full):                                # A_g is symmetric: the transpose is A_g, zero-padded to `full`
+            return ops.hip.tf_curve(h, dy.contiguous(), g, int(length), int(full))
+        return ops.hip.tf_curve(h, x, g, int(length), int(length)), adjoint
+
+    def after_cotangent(self, x, length, dy, curve=None, update_eq=True, **kw):
+        """g_k -> g_{k+1}: the curve gradient of this step's cotangent and one Adam + projection step, two launches, no host sync."""
+        if curve is not None or not update_eq:
+            return
+        part = ops.hip.tf_wgrad(self.frontend._h.value, dy.contiguous(), x, int(length))
+        self.k += 1
+        ops.hip.eq_update(part, self._g, self._m, self._v, self.k, self.lr, self.betas[0], self.betas[1], self.adam_eps,
+                          self.normalize == "peak")
+
+
 class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 (unrunnable in the reference: run.py:213-214)
     """Style guidance with BUILD-DEFINED semantics (the reference's `clap_model.get_gram_matrix`
     does not exist anywhere): `forward(x) = noiser(x)` (identity, operator.py:270-271) and

@@ -21,7 +21,7 @@ from ..torch_utils import randn_tensor
 from ..profiling import stage
 from ..inverse_problem.noise import step_sigma
 from ..inverse_problem.mixture import MixtureOperator
-from ..inverse_problem.operator import BlindDereverberationOperator, TimeFrequencyMaskOperator
+from ..inverse_problem.operator import BlindDereverberationOperator, BlindEqualizationOperator, TimeFrequencyMaskOperator
 from .. import parallel
 
 
@@ -448,7 +448,7 @@ class MusicLDMPipeline:
             restart()
 
     def _check_positional_state(self, shard, group, lanes):
-        """An operator that keeps per-clip state by batch position (the blind dereverberation's response estimates) sees every clip of the
+        """An operator that keeps per-clip state by batch position (the blind dereverberation's response estimates, the blind equalisation's curves) sees every clip of the
         call in one batch, in call order: no clip lanes, no clip sharding."""
         op = self.scheduler.operator
         while hasattr(op, "inner"):                              # the measurement operator inside a track, a mixture, or both
@@ -460,6 +460,13 @@ class MusicLDMPipeline:
             if shard or group is not None:
                 raise ValueError("TimeFrequencyMaskOperator with per-clip gains cannot be sharded over ranks (shard / group): its gains are "
                                  "indexed by batch position, and a rank sees only its own clips")
+        if isinstance(op, BlindEqualizationOperator):
+            if int(self.lanes if lanes is None else lanes) > 1:
+                raise ValueError("BlindEqualizationOperator cannot run as clip lanes (lanes > 1): its curve estimates are indexed by batch "
+                                 "position, and a lane sees only its own clips")
+            if shard or group is not None:
+                raise ValueError("BlindEqualizationOperator cannot be sharded over ranks (shard / group): its curve estimates are indexed "
+                                 "by batch position, and a rank sees only its own clips")
         if not isinstance(op, BlindDereverberationOperator):
             return
         if int(self.lanes if lanes is None else lanes) > 1:

@@ -13,6 +13,7 @@ embedding file (`--prompt_embeds x.npy`, (B, 512) CLAP text embeddings for Music
     python examples/run_inverse_problem.py -c dps -t music_source_separation --wav drums.wav bass.wav --gains 1 0.5 --project
     python examples/run_inverse_problem.py -c dps -t music_source_separation --mixture song.wav --stems 4 --track_overlap_s 1.28
     python examples/run_inverse_problem.py -c dps -t music_spectral_inpainting --tf_box 2000,4000,2,2.5 --hum 50,5      # a spectral hole + hum
+    python examples/run_inverse_problem.py -c dps -t music_blind_equalization --eq_lowpass 3000,4      # the EQ curve is fitted, not given
 
 `--track_overlap_s S` restores a recording longer than the model window whole (track mode, inverse_problem/track.py): the first `--wav`
 (or a synthetic 2.5-window signal) becomes overlapping windows under one loss and one stitched file is written.  Without the flag a
@@ -21,6 +22,11 @@ long `--wav` is cropped to the window as before.
 `-t music_spectral_inpainting` measures through a gain on the spectrogram (TimeFrequencyMaskOperator): `--tf_box f_lo,f_hi,t0,t1[,gain]`
 (Hz and seconds, an empty field = to the edge, gain 0 by default; repeatable, later boxes overwrite earlier ones) and `--hum
 f0[,harmonics[,width]]`; without either flag the boxes of configs/inverse_problem/music_spectral_inpainting.yaml are used.
+
+`-t music_blind_equalization` measures through an equalisation curve that the restoration does not know (BlindEqualizationOperator fits
+it inside the guided loop): `--eq_lowpass HZ[,ORDER]` (a Butterworth magnitude, order 4 by default) or `--eq_points "f,dB;f,dB;..."`
+(breakpoints, linear in dB over log-frequency) is the TRUE curve of the synthetic measurement; the two exclude each other, and without
+either the `points` of configs/inverse_problem/music_blind_equalization.yaml are used.
 
 `-t music_source_separation` restores K stems from their mixture under one loss (inverse_problem/mixture.py), one prompt embedding per
 stem: `--wav` names the stems whose gain-weighted sum (`--gains`) is the measurement (SI-SDR per stem is printed), `--mixture mix.wav
@@ -44,15 +50,17 @@ from diffmusic_amd.pipelines import get_pipeline                                
 from diffmusic_amd.schedulers import get_scheduler                                  # noqa: E402
 
 TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation", "music_declipping",
-         "music_blind_dereverberation", "music_source_separation", "music_spectral_inpainting")
+         "music_blind_dereverberation", "music_source_separation", "music_spectral_inpainting", "music_blind_equalization")
 SEPARATION = "music_source_separation"
 SPECTRAL = "music_spectral_inpainting"
+BLIND_EQ = "music_blind_equalization"
 
 
-def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None, tf_boxes=None):
+def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None, tf_boxes=None, eq_true=None):
     """run.py:157-212: one operator per task, constructor arguments from the data / model config.  `audio_length_in_s`: the length the
     operator acts on when it is not the model window (a track).  `clip_threshold`: music_declipping's threshold(s), a float or one value
-    per clip (`threshold_for_sdr` of the clean clips).  `tf_boxes`: music_spectral_inpainting's boxes (`spectral_boxes`)."""
+    per clip (`threshold_for_sdr` of the clean clips).  `tf_boxes`: music_spectral_inpainting's boxes (`spectral_boxes`).  `eq_true`:
+    music_blind_equalization's true curve (`equalization_curve`), kept on the operator for `forward`."""
     noiser = P.get_noiser(**cfg.inverse_problem.noise)
     d, scale = cfg.data, 1
     seconds = cfg.model.pipe.audio_length_in_s if audio_length_in_s is None else audio_length_in_s
@@ -80,6 +88,14 @@ def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=
             raise ValueError("music_spectral_inpainting needs tf_boxes (spectral_boxes(args, cfg))")
         grid = P.tf_gain_grid(int(seconds * d.sample_rate), d.sample_rate, tf_boxes, base=float(cfg.inverse_problem.get("base", 1.0)))
         op = P.TimeFrequencyMaskOperator(sample_rate=d.sample_rate, gain=grid, noiser=noiser)
+    elif task == BLIND_EQ:
+        if eq_true is None:
+            raise ValueError("music_blind_equalization needs eq_true (equalization_curve(args, cfg))")
+        ip = cfg.inverse_problem
+        op = P.BlindEqualizationOperator(sample_rate=d.sample_rate, noiser=noiser, lr=ip.get("lr") or 0.05,
+                                         betas=tuple(ip.get("betas") or (0.9, 0.999)), adam_eps=float(ip.get("adam_eps") or 1e-8),
+                                         init=ip.get("init") or "flat", normalize=ip.get("normalize") or "peak")
+        op.true_curve = torch.as_tensor(np.asarray(eq_true, dtype=np.float32)).reshape(1, -1)
     else:
         raise ValueError(f"Unknown task: {task}")
     return op, scale
@@ -156,6 +172,10 @@ def parse_args(argv=None):
                     help="music_spectral_inpainting: a box of the spectrogram (Hz, seconds; empty field = to the edge) set to GAIN (default 0); repeatable")
     ap.add_argument("--hum", default=None, metavar="F0[,HARMONICS[,WIDTH]]",
                     help="music_spectral_inpainting: remove bands of WIDTH Hz (default 32) around F0 .. HARMONICS * F0 (default 1)")
+    ap.add_argument("--eq_lowpass", default=None, metavar="HZ[,ORDER]",
+                    help="music_blind_equalization: the true curve is a Butterworth low-pass magnitude at HZ (ORDER 4 by default)")
+    ap.add_argument("--eq_points", default=None, metavar="F,DB;F,DB;...",
+                    help="music_blind_equalization: the true curve through (Hz, dB) breakpoints, linear in dB over log-frequency")
     ap.add_argument("--strength", type=float, default=1.0, help="share of num_inference_steps a warm start runs (diffusers' img2img rule)")
     return ap.parse_args(argv)
 
@@ -217,6 +237,47 @@ def spectral_boxes(args, cfg=None):
     if not boxes:
         raise SystemExit(f"-t {SPECTRAL} needs at least one --tf_box or --hum (or boxes in its config)")
     return boxes
+
+
+def equalization_curve(args, cfg=None):
+    """The argument rules of -t music_blind_equalization -> the true (513,) curve of the synthetic measurement: --eq_lowpass or
+    --eq_points (not both); with neither, the `points` of the task's config.  Any other task refuses the two flags."""
+    if args.task != BLIND_EQ:
+        for flag in ("eq_lowpass", "eq_points"):
+            if getattr(args, flag) is not None:
+                raise SystemExit(f"--{flag} belongs to -t {BLIND_EQ}")
+        return None
+    if args.eq_lowpass is not None and args.eq_points is not None:
+        raise SystemExit("--eq_lowpass and --eq_points both name the true curve: pass one of them")
+    sr = 16000 if cfg is None else cfg.data.sample_rate
+    if args.eq_lowpass is not None:
+        parts = args.eq_lowpass.split(",")
+        if not 1 <= len(parts) <= 2:
+            raise SystemExit(f"--eq_lowpass {args.eq_lowpass}: HZ[,ORDER]")
+        vals = [_field(p, "--eq_lowpass") for p in parts]
+        if vals[0] is None or vals[0] <= 0:
+            raise SystemExit(f"--eq_lowpass {args.eq_lowpass}: HZ is a positive frequency")
+        order = 4 if len(vals) < 2 or vals[1] is None else vals[1]
+        if order != int(order) or order < 1:
+            raise SystemExit(f"--eq_lowpass {args.eq_lowpass}: ORDER is a whole number >= 1")
+        return P.lowpass_curve(sr, vals[0], int(order))
+    if args.eq_points is not None:
+        points = []
+        for text in args.eq_points.split(";"):
+            parts = text.split(",")
+            if len(parts) != 2:
+                raise SystemExit(f"--eq_points {args.eq_points}: F,DB;F,DB;...")
+            f, db = (_field(p, "--eq_points") for p in parts)
+            if f is None or db is None or f <= 0:
+                raise SystemExit(f"--eq_points {args.eq_points}: every point is a positive frequency in Hz and a gain in dB")
+            points.append((f, db))
+    else:
+        points = [tuple(p) for p in ((cfg.inverse_problem.get("points") if cfg is not None else None) or [])]
+        if not points:
+            raise SystemExit(f"-t {BLIND_EQ} needs --eq_lowpass or --eq_points (or points in its config)")
+    if any(b[0] <= a[0] for a, b in zip(points, points[1:])):
+        raise SystemExit("--eq_points: the frequencies increase strictly")
+    return P.eq_curve(sr, points)
 
 
 def separation_stems(args):
@@ -307,13 +368,14 @@ def run_separation(args, cfg, K):
 def main(argv=None):
     args = parse_args(argv)
     overrides = [f"data={args.data}", f"model={args.model}"]
-    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL):
+    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL, BLIND_EQ):
         overrides.append(f"inverse_problem={args.task}")
     stems = separation_stems(args)
     if args.project and args.task not in ("music_declipping", SEPARATION):
         raise SystemExit("--project is the output stage of -t music_declipping and -t music_source_separation")
     cfg = compose(args.config_name, overrides=overrides)
     tf_boxes = spectral_boxes(args, cfg)
+    eq_true = equalization_curve(args, cfg)
     if stems is not None:
         if args.model != "musicldm":
             raise SystemExit("this driver feeds MusicLDM's class-embedding conditioning; AudioLDM2 needs its T5 / GPT-2 states (see bench.py --workload)")
@@ -330,7 +392,7 @@ def main(argv=None):
     if args.track_overlap_s is None:
         gt = load_clips(args.wav, args.batch, sr, length, args.seed).to(device)
         thr = P.threshold_for_sdr(gt, args.clip_sdr_db) if args.task == "music_declipping" else None
-        op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr, tf_boxes=tf_boxes)
+        op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr, tf_boxes=tf_boxes, eq_true=eq_true)
         B = gt.shape[0]
     else:
         if args.task == "music_generation":
@@ -340,7 +402,7 @@ def main(argv=None):
         layout = P.TrackLayout(T, length, int(round(args.track_overlap_s * sr)))
         thr = float(P.threshold_for_sdr(gt, args.clip_sdr_db)[0]) if args.task == "music_declipping" else None
         inner, scale = build_operator(args.task, cfg, args.mask_type, audio_length_in_s=P.seconds_for_samples(T, sr), clip_threshold=thr,
-                                      tf_boxes=tf_boxes)
+                                      tf_boxes=tf_boxes, eq_true=eq_true)
         op = P.TrackOperator(inner, layout)
         B = layout.num_windows
         sched_kw["per_clip_norm"] = False                                          # one loss, norms over all windows
@@ -382,6 +444,10 @@ def main(argv=None):
         est, true = blind.ir_estimate.cpu(), blind.true_ir                         # the synthetic measurement knows its response
         err = torch.linalg.vector_norm(est - true, dim=1) / torch.linalg.vector_norm(true, dim=1)
         print("impulse response estimate, relative error per clip: " + " ".join(f"{e:.3f}" for e in err.tolist()))
+    if isinstance(blind, P.BlindEqualizationOperator) and blind.true_curve is not None and blind.eq_estimate is not None:
+        est, true = blind.eq_estimate.cpu(), blind.true_curve                      # the synthetic measurement knows its curve
+        err = torch.linalg.vector_norm(est - true, dim=1) / torch.linalg.vector_norm(true, dim=1)
+        print("equalisation curve estimate, relative error per clip: " + " ".join(f"{e:.3f}" for e in err.tolist()))
     ref = gt.cpu().numpy()
     print(f"wrote {B} clip(s) to {out}; LSD {LogSpectralDistance().score(ref, audio[:, :length]):.4f}  MSE {MeanSquaredError().score(ref, audio[:, :length]):.6f}")
 

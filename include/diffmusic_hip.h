@@ -33,7 +33,8 @@ extern "C" {
  * dmx_clip_fwd / dmx_clip_bwd / dmx_declip_project (declipping: a hard clip inside and beside the guidance pair) and dmx_fir_clip_fwd /
  * dmx_fir_clip_bwd / dmx_fir_wgrad / dmx_fir_wgrad_workspace_floats / dmx_ir_update (blind dereverberation: one fitted response per clip)
  * and dmx_stem_mix_fwd / dmx_stem_mix_bwd / dmx_stem_project (source separation: the stems of a mixture as the batch) and dmx_audio_tf_gain /
- * dmx_audio_tf_frames (time-frequency masking: a real gain on the STFT) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * dmx_audio_tf_frames (time-frequency masking: a real gain on the STFT) and dmx_audio_tf_curve / dmx_audio_tf_wgrad /
+ * dmx_audio_tf_wgrad_segments / dmx_audio_eq_update (blind equalisation: a fitted gain curve per clip) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
  * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
@@ -280,6 +281,31 @@ int dmx_audio_stft_mag_bwd(dmx_audio* a, const float* dmag, float* dwav, long lo
 int dmx_audio_tf_frames(int L);
 int dmx_audio_tf_gain(dmx_audio* a, const float* x, long long x_stride, const float* gain, long long gain_clip_stride, float* out,
                       long long out_stride, int batch, int L, int full, void* stream);
+/* Blind equalisation (csrc/tf_gain.hip, csrc/tf_eq.hip): the gain of dmx_audio_tf_gain constant in time, G[k, t] =
+ * g[k], one curve per clip, fitted inside the guided loop.  Same handle requirement (n_fft 1024, Hann) and frame conventions.
+ *   tf_curve   dmx_audio_tf_gain with the gain row of EVERY frame at curve + b * curve_clip_stride: curve (513) fp32 per clip,
+ *              curve_clip_stride 0 = one curve for every clip.  Bit for bit dmx_audio_tf_gain of the curve broadcast over the frames; the
+ *              same refusals, with a non-zero curve_clip_stride < 513 in place of the grid's.
+ *   tf_wgrad   the gradient of a loss in g from x and the cotangent dy = dLoss/dy at y = A_g(x), both (batch, >= L), zero outside [0, L):
+ *              dg[b, k] = (h_k / 1536) sum_t Re(X[k, t] conj(U[k, t])), h_0 = h_512 = 1, else 2, X and U the analysis STFTs of x and dy,
+ *              as `segments` partial rows, partials (batch, segments, 513): row s holds the frames [16 s, 16 s + 16) added in increasing t.
+ *              segments = dmx_audio_tf_wgrad_segments(L) = ceil((ceil(L / 256) + 3) / 16) (0 for L < 1).  No atomics: the same bits on
+ *              every call, and a clip's rows depend neither on the batch nor on its place in it; dy = 0 gives +0 everywhere.
+ *              DMX_ERR_SHAPE, with nothing written, for another handle, a null pointer, L < 1, a row stride < L, batch > 65535.
+ *   eq_update  dg = sum_s partials[b, s, :] in increasing s, then per clip, k the 1-based count of updates since the last reset:
+ *                m <- b1 m + (1 - b1) dg;  v <- b2 v + (1 - b2) dg dg;  g~ = max(g - lr (m / (1 - b1^k)) / (sqrt(v / (1 - b2^k)) + eps), 0)
+ *                g <- g~ / max_k g~ (normalize = 1, "peak") or g~ (normalize = 0, "none")
+ *              the arithmetic of dmx_ir_update (csrc/adam_step.h), scalars taken in double on the host and rounded once.  A clip with a
+ *              non-finite element in dg or g~, or with max g~ = 0 under "peak", keeps its g, m and v untouched (decided on the device).
+ *              DMX_ERR_SHAPE for a null pointer, batch < 1, segments < 1, k < 1, lr <= 0, a beta outside [0, 1), eps < 0.
+ * One launch each. */
+int dmx_audio_tf_curve(dmx_audio* a, const float* x, long long x_stride, const float* curve, long long curve_clip_stride, float* out,
+                       long long out_stride, int batch, int L, int full, void* stream);
+int dmx_audio_tf_wgrad_segments(int L);
+int dmx_audio_tf_wgrad(dmx_audio* a, const float* x, long long x_stride, const float* dy, long long dy_stride, float* partials, int batch, int L,
+                       void* stream);
+int dmx_audio_eq_update(const float* partials, int segments, float* g, float* m, float* v, int batch, int k, double lr, double beta1,
+                        double beta2, double eps, int normalize, void* stream);
 /* PhaseRetrievalOperator.transform on a given magnitude (B, bins, frames) -> (B, frames, n_mels) */
 int dmx_audio_melscale(dmx_audio* a, const float* mag, float* mel_out, int batch, int frames, float lo, float hi, void* stream);
 /* MusicInpaintingOperator.forward (operator.py:132-133): y[b,t] = x[b,t]*mask[t] (t<L), 0 for L<=t<Ly; mask NULL = copy */
