@@ -286,6 +286,42 @@ def declip_project(wav, measurement, thr, L):
     return out
 
 
+def drc_fwd(x, L, threshold_db, slope, knee_db, a_att, a_rel, makeup_db):
+    """x (B, >= L) with any row stride -> (y (B, L), state (B, 3, H) fp32 with the rows p, G, s, tape (B, H) uint8: bits 0-1 the region of
+    the static curve, bit 2 the attack gate), H = ceil(L / 64): the block-rate compressor of csrc/drc.hip.  slope = 1 - 1 / ratio."""
+    if not x.is_cuda:
+        raise RuntimeError("drc_fwd: tensors must be on the GPU (no CPU fallback)")
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] >= L >= 1, ("drc_fwd", x.shape, L)
+    B, H = x.shape[0], -(-L // 64)
+    y = torch.empty(B, L, dtype=torch.float32, device=x.device)
+    state = torch.empty(B, 3, H, dtype=torch.float32, device=x.device)
+    tape = torch.empty(B, H, dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.lib().dmx_drc_fwd(_p(x), x.stride(0), _p(y), L, _p(state), _p(tape), min(B, 65536), L, threshold_db, slope, knee_db, a_att,
+                                      a_rel, makeup_db, _stream()), "drc_fwd")
+    return y, state, tape
+
+
+def drc_bwd(dy, x, state, tape, Lfull, threshold_db, slope, knee_db, a_att, a_rel, makeup_db):
+    """dy (B, L) and x (B, >= L) with any row strides, state and tape as `drc_fwd` returned them for x -> (B, Lfull): the transpose of the
+    Jacobian of drc_fwd at x applied to dy, zeros past L.  The gates come from the tape."""
+    if not dy.is_cuda:
+        raise RuntimeError("drc_bwd: tensors must be on the GPU (no CPU fallback)")
+    assert dy.dtype == torch.float32 and dy.dim() == 2 and dy.stride(1) == 1 and Lfull >= dy.shape[1] >= 1, ("drc_bwd", dy.shape, Lfull)
+    B, L = dy.shape
+    H = -(-L // 64)
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == B and x.shape[1] >= L and \
+        x.device == dy.device, ("drc_bwd", x.shape, dy.shape)
+    assert state.device == dy.device and state.dtype == torch.float32 and state.is_contiguous() and tuple(state.shape) == (B, 3, H), \
+        ("drc_bwd", tuple(state.shape), (B, 3, H))
+    assert tape.device == dy.device and tape.dtype == torch.uint8 and tape.is_contiguous() and tuple(tape.shape) == (B, H), \
+        ("drc_bwd", tuple(tape.shape), (B, H))
+    work = torch.empty(B, H, dtype=torch.float32, device=dy.device)
+    d = torch.empty(B, Lfull, dtype=torch.float32, device=dy.device)
+    _lib.check(_lib.lib().dmx_drc_bwd(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(state), _p(tape), _p(work), _p(d), Lfull, min(B, 65536), L, Lfull,
+                                      threshold_db, slope, knee_db, a_att, a_rel, makeup_db, _stream()), "drc_bwd")
+    return d
+
+
 def tf_gain(audio, x, gain_t, L, Lfull, *, out=None):
     """x (B, >= L) with any row stride, gain_t (frames, 513) shared or (B, frames, 513), frames = ceil(L / 256) + 3 -> (B, Lfull): the
     time-frequency gain A(x[:, :L]) (csrc/tf_gain.hip), +0 past L.  A is symmetric: the same call is the transpose.

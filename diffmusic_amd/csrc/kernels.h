@@ -110,6 +110,10 @@ int dmx_tf_wgrad_segments(int L);                        // ceil(frames / 16)
 int dmx_tf_wgrad(const DmxStftMelTables& t, const float* x, long long x_stride, const float* dy, long long dy_stride, float* part, int B, int L,
                  hipStream_t st);
 
+// ---- drc.hip (dynamic-range compression at block rate and the transpose of its Jacobian; three launches per direction).  Like
+// waveshape.hip it needs no handle: its launchers are the C ABI's own dmx_drc_fwd / dmx_drc_bwd (include/diffmusic_hip.h)
+constexpr int DMX_DRC_BLOCK = 64;                        // samples per sidechain block; state (B, 3, H) and tape (B, H), H = ceil(L / 64)
+
 // ---- sched.hip
 int dmx_pred_x0(const float* x, const float* eps, float* x0, long long n, float sqrt_a, float sqrt_1ma, hipStream_t st);
 int dmx_pred_x0_ex(const float* x, const float* m, float* x0, long long n, float sqrt_a, float sqrt_1ma, int ptype, float clip_r, hipStream_t st);

@@ -44,6 +44,8 @@
 #pragma weak dmx_audio_tf_wgrad_segments
 #pragma weak dmx_audio_tf_wgrad
 #pragma weak dmx_audio_eq_update
+#pragma weak dmx_drc_fwd
+#pragma weak dmx_drc_bwd
 
 namespace {
 
@@ -359,6 +361,42 @@ at::Tensor declip_project(const at::Tensor& wav, const at::Tensor& measurement, 
   ok(dmx_declip_project(wav.data_ptr<float>(), wav.stride(0), measurement.data_ptr<float>(), measurement.stride(0), thr.data_ptr<float>(),
                         out.data_ptr<float>(), L, (int)wav.size(0), (int)L, cur_stream()), "declip_project");
   return out;
+}
+// dynamic-range compression (include/diffmusic_hip.h dmx_drc_fwd / dmx_drc_bwd): x (B, >= L) -> y (B, L), state (B, 3, H) fp32 (rows p, G, s),
+// tape (B, H) uint8 (bits 0-1 region, bit 2 attack), H = ceil(L / 64); the backward takes them back and returns (B, Lfull)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> drc_fwd(const at::Tensor& x, int64_t L, double threshold_db, double slope, double knee_db, double a_att,
+                                                       double a_rel, double makeup_db) {
+  rows_ok(x, L, "x");
+  TORCH_CHECK(L <= (int64_t(1) << 30), "L must be <= 2^30");
+  DMX_DEVICE_OF(x);
+  const int64_t B = x.size(0), H = (L + 63) / 64;
+  at::Tensor y = at::empty({B, L}, x.options());
+  at::Tensor state = at::empty({B, 3, H}, x.options());
+  at::Tensor tape = at::empty({B, H}, x.options().dtype(at::kByte));
+  ok(dmx_drc_fwd(x.data_ptr<float>(), x.stride(0), y.data_ptr<float>(), L, state.data_ptr<float>(), tape.data_ptr<uint8_t>(), (int)std::min<int64_t>(B, 65536),
+                 (int)L, (float)threshold_db, (float)slope, (float)knee_db, (float)a_att, (float)a_rel, (float)makeup_db, cur_stream()), "drc_fwd");
+  return {y, state, tape};
+}
+at::Tensor drc_bwd(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& state, const at::Tensor& tape, int64_t Lfull, double threshold_db,
+                   double slope, double knee_db, double a_att, double a_rel, double makeup_db) {
+  TORCH_CHECK(dy.is_cuda(), "dy must be a GPU tensor (the diffmusic_hip ops have no CPU fallback)");
+  TORCH_CHECK(dy.scalar_type() == at::kFloat && dy.dim() == 2 && dy.stride(1) == 1 && dy.size(1) >= 1 && Lfull >= dy.size(1) &&
+              Lfull <= (int64_t(1) << 30), "dy must be (B, L) fp32 with 1 <= L <= Lfull <= 2^30");
+  const int64_t B = dy.size(0), L = dy.size(1), H = (L + 63) / 64;
+  rows_ok(x, L, "x");
+  TORCH_CHECK(x.size(0) == B && x.device() == dy.device(), "x must hold dy's clips");
+  DMX_DEVICE_OF(dy);
+  f32_cuda(state, "state");
+  TORCH_CHECK(state.device() == dy.device() && state.dim() == 3 && state.size(0) == B && state.size(1) == 3 && state.size(2) == H,
+              "state must be (", B, ", 3, ", H, ") on dy's device");
+  TORCH_CHECK(tape.is_cuda() && tape.device() == dy.device() && tape.scalar_type() == at::kByte && tape.is_contiguous() && tape.dim() == 2 &&
+              tape.size(0) == B && tape.size(1) == H, "tape must be contiguous uint8 (", B, ", ", H, ") on dy's device");
+  at::Tensor work = at::empty({B, H}, dy.options());
+  at::Tensor d = at::empty({B, Lfull}, dy.options());
+  ok(dmx_drc_bwd(dy.data_ptr<float>(), dy.stride(0), x.data_ptr<float>(), x.stride(0), state.data_ptr<float>(), tape.data_ptr<uint8_t>(),
+                 work.data_ptr<float>(), d.data_ptr<float>(), Lfull, (int)std::min<int64_t>(B, 65536), (int)L, (int)Lfull, (float)threshold_db, (float)slope,
+                 (float)knee_db, (float)a_att, (float)a_rel, (float)makeup_db, cur_stream()), "drc_bwd");
+  return d;
 }
 // time-frequency gain (include/diffmusic_hip.h dmx_audio_tf_gain): x (B, >= L), gain_t (frames, 513) shared or (B, frames, 513) -> (B, Lfull)
 at::Tensor tf_gain(int64_t audio, const at::Tensor& x, const at::Tensor& gain_t, int64_t L, int64_t Lfull) {
@@ -708,10 +746,12 @@ TORCH_LIBRARY(diffmusic_hip, m) {
                                                          {"dmx_audio_tf_curve", (const void*)&dmx_audio_tf_curve},
                                                          {"dmx_audio_tf_wgrad_segments", (const void*)&dmx_audio_tf_wgrad_segments},
                                                          {"dmx_audio_tf_wgrad", (const void*)&dmx_audio_tf_wgrad},
-                                                         {"dmx_audio_eq_update", (const void*)&dmx_audio_eq_update}};
+                                                         {"dmx_audio_eq_update", (const void*)&dmx_audio_eq_update},
+                                                         {"dmx_drc_fwd", (const void*)&dmx_drc_fwd},
+                                                         {"dmx_drc_bwd", (const void*)&dmx_drc_bwd}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
-                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation entry points): rebuild with `python -m diffmusic_amd.build --force`");
+                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression entry points): rebuild with `python -m diffmusic_amd.build --force`");
   }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
@@ -743,6 +783,10 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("clip_fwd(Tensor x, Tensor thr, int L) -> Tensor", &clip_fwd);
   m.def("clip_bwd(Tensor dy, Tensor wav, Tensor thr, int Lfull) -> Tensor", &clip_bwd);
   m.def("declip_project(Tensor wav, Tensor measurement, Tensor thr, int L) -> Tensor", &declip_project);
+  m.def("drc_fwd(Tensor x, int L, float threshold_db, float slope, float knee_db, float a_att, float a_rel, float makeup_db) -> (Tensor, Tensor, Tensor)",
+        &drc_fwd);
+  m.def("drc_bwd(Tensor dy, Tensor x, Tensor state, Tensor tape, int Lfull, float threshold_db, float slope, float knee_db, float a_att, float a_rel, "
+        "float makeup_db) -> Tensor", &drc_bwd);
   m.def("noise_add(Tensor y, Tensor noise, float sigma) -> Tensor", &noise_add);
   m.def("tf_gain(int audio, Tensor x, Tensor gain_t, int L, int Lfull) -> Tensor", &tf_gain);
   m.def("tf_curve(int audio, Tensor x, Tensor curve, int L, int Lfull) -> Tensor", &tf_curve);

@@ -133,3 +133,41 @@ def lowpass_curve(sample_rate, cutoff_hz, order=4):
         raise ValueError(f"lowpass_curve({cutoff_hz!r}, order={order!r}): a positive cut-off and an order >= 1")
     freq = np.arange(TF_BINS, dtype=np.float64) * float(sample_rate) / TF_N_FFT
     return (1.0 / np.sqrt(1.0 + (freq / cutoff_hz) ** (2 * order))).astype(np.float32)
+
+
+# ---- de-compression (DynamicRangeOperator; csrc/drc.hip): a compressor whose sidechain runs on blocks of 64 samples
+DRC_BLOCK = 64
+
+
+def drc_coeffs(sample_rate, attack_ms, release_ms):
+    """(aA, aR) as np.float32: the per-block coefficients 1 - exp(-64 / (sample_rate * t)) of the attack / release follower, computed in
+    float64 and rounded once -- the constants the kernels and the tests' model share."""
+    sample_rate, attack_ms, release_ms = float(sample_rate), float(attack_ms), float(release_ms)
+    if not (math.isfinite(sample_rate) and sample_rate > 0):
+        raise ValueError(f"sample_rate = {sample_rate!r}: a positive finite rate")
+    out = []
+    for name, ms in (("attack_ms", attack_ms), ("release_ms", release_ms)):
+        if not (math.isfinite(ms) and ms > 0):
+            raise ValueError(f"{name} = {ms!r}: a positive finite time in milliseconds")
+        a = np.float32(-math.expm1(-DRC_BLOCK / (sample_rate * ms * 1e-3)))
+        if not 0.0 < float(a) <= 1.0:
+            raise ValueError(f"{name} = {ms!r}: its per-block coefficient {float(a)!r} rounds outside (0, 1] -- too long for blocks of "
+                             f"{DRC_BLOCK} samples at {sample_rate} Hz")
+        out.append(a)
+    return out[0], out[1]
+
+
+def drc_static_curve(level_db, threshold_db, ratio, knee_db):
+    """Gain reduction c >= 0 in dB of a compressor's static curve at `level_db` (float64 array): with d = level - threshold, k = 1 - 1 / ratio
+    and knee width W, c = 0 where 2 d < -W, k (d + W / 2)^2 / (2 W) where 2 d <= W, and k d above (ratio = inf: a limiter)."""
+    threshold_db, ratio, knee_db = float(threshold_db), float(ratio), float(knee_db)
+    if math.isnan(ratio) or ratio < 1:
+        raise ValueError(f"ratio = {ratio!r}: at least 1 (inf = a limiter)")
+    if not (math.isfinite(knee_db) and knee_db >= 0):
+        raise ValueError(f"knee_db = {knee_db!r}: a finite width >= 0")
+    if not math.isfinite(threshold_db):
+        raise ValueError(f"threshold_db = {threshold_db!r}: a finite level")
+    k = 1.0 - 1.0 / ratio
+    d = np.asarray(level_db, dtype=np.float64) - threshold_db
+    knee = k * (d + 0.5 * knee_db) ** 2 / (2.0 * knee_db) if knee_db > 0 else np.zeros_like(d)
+    return np.where(2.0 * d < -knee_db, 0.0, np.where(2.0 * d <= knee_db, knee, k * d))

@@ -934,6 +934,58 @@ class BlindEqualizationOperator(_MelOperator):
                           self.normalize == "peak")
 
 
+class DynamicRangeOperator(_MelOperator):
+    """De-compression (extension; the first operator that is nonlinear WITH MEMORY): a feed-forward, mono dynamic-range compressor or
+    limiter -- over-mastered releases, broadcast AGC, bus compressors -- whose sidechain runs on blocks of 64 samples (4 ms at 16 kHz).
+    Per clip, x zero outside [0, L) (csrc/drc.hip):
+
+        p[j] = mean of x^2 over block j     d = 10 log10(p + 1e-10) - threshold_db     k = 1 - 1 / ratio, W = knee_db
+        c[j] = 0 (2 d < -W) | k (d + W/2)^2 / (2 W) (2 d <= W) | k d                   the static curve: gain reduction in dB
+        s[j] = s[j-1] + (c[j] > s[j-1] ? aA : aR) (c[j] - s[j-1]), s[-1] = 0           aA, aR = dsp.drc_coeffs(sample_rate, attack_ms, release_ms)
+        G[j] = 10^((makeup_db - s[j]) / 20)                                            y = g x, g linear from G[j-1] to G[j] over block j
+
+    forward = noiser(A(x)), transform = clamp(wav2mel, -80, 80) like the IdentityOperator's.  A is materialised (`_on_load` is None): a
+    guided step is the identity's plus `drc_fwd` and `drc_bwd`, three launches each.  The Jacobian is not diagonal: `adjoint` runs the
+    follower's recurrence backwards in time, at the x `apply` was given, with the gates `apply` decided (one tape byte per block).
+
+    The parameters are GIVEN, shared by all clips and rounded to fp32 once here; nothing is fitted and nothing is kept per clip, so clip lanes
+    and sharding work.  ratio = inf is a limiter.  Bad parameters are refused by name at construction; the front end is made on first use, so
+    the operator can be built without a GPU.  `dead_span` is None: every sample reaches y."""
+
+    def __init__(self, sample_rate=16000, threshold_db=-24.0, ratio=4.0, knee_db=6.0, attack_ms=5.0, release_ms=100.0, makeup_db=0.0, noiser=None):
+        def finite(name, v, lo=None, hi=200.0):
+            v = float(v)
+            if not math.isfinite(v) or abs(v) > hi or (lo is not None and v < lo):
+                raise ValueError(f"{name} = {v!r}: a finite number" + (f" >= {lo}" if lo is not None else "") + f", at most {hi} in magnitude")
+            return float(np.float32(v))
+        if not (math.isfinite(float(sample_rate)) and float(sample_rate) > 0):
+            raise ValueError(f"sample_rate = {sample_rate!r}: a positive finite rate")
+        ratio = float(ratio)
+        if math.isnan(ratio) or ratio < 1:
+            raise ValueError(f"ratio = {ratio!r}: at least 1 (inf = a limiter)")
+        self.sample_rate, self.noiser = sample_rate, noiser
+        self.threshold_db, self.makeup_db = finite("threshold_db", threshold_db), finite("makeup_db", makeup_db)
+        self.knee_db = finite("knee_db", knee_db, lo=0.0)
+        self.ratio, self.attack_ms, self.release_ms = ratio, float(attack_ms), float(release_ms)
+        self.slope = float(np.float32(1.0 - 1.0 / ratio))         # k
+        a_att, a_rel = dsp.drc_coeffs(sample_rate, attack_ms, release_ms)      # refuses bad times by name
+        self.a_att, self.a_rel = float(a_att), float(a_rel)
+        self._init_mel(sample_rate, lazy=True)
+
+    @property
+    def params(self):
+        """The six fp32 parameters in the order `drc_fwd` / `drc_bwd` take them."""
+        return self.threshold_db, self.slope, self.knee_db, self.a_att, self.a_rel, self.makeup_db
+
+    def apply(self, x, length, **kw):
+        params = self.params
+        y, state, tape = ops.hip.drc_fwd(x, int(length), *params)
+
+        def adjoint(dy, full):                                # the Jacobian of a nonlinear A is taken at x, with the gates of this apply
+            return ops.hip.drc_bwd(dy, x, state, tape, int(full), *params)
+        return y, adjoint
+
+
 class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 (unrunnable in the reference: run.py:213-214)
     """Style guidance with BUILD-DEFINED semantics (the reference's `clap_model.get_gram_matrix`
     does not exist anywhere): `forward(x) = noiser(x)` (identity, operator.py:270-271) and

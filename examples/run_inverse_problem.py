@@ -14,6 +14,7 @@ embedding file (`--prompt_embeds x.npy`, (B, 512) CLAP text embeddings for Music
     python examples/run_inverse_problem.py -c dps -t music_source_separation --mixture song.wav --stems 4 --track_overlap_s 1.28
     python examples/run_inverse_problem.py -c dps -t music_spectral_inpainting --tf_box 2000,4000,2,2.5 --hum 50,5      # a spectral hole + hum
     python examples/run_inverse_problem.py -c dps -t music_blind_equalization --eq_lowpass 3000,4      # the EQ curve is fitted, not given
+    python examples/run_inverse_problem.py -c dps -t music_decompression --drc_threshold_db -30 --drc_ratio inf      # undo a limiter
 
 `--track_overlap_s S` restores a recording longer than the model window whole (track mode, inverse_problem/track.py): the first `--wav`
 (or a synthetic 2.5-window signal) becomes overlapping windows under one loss and one stitched file is written.  Without the flag a
@@ -27,6 +28,10 @@ f0[,harmonics[,width]]`; without either flag the boxes of configs/inverse_proble
 it inside the guided loop): `--eq_lowpass HZ[,ORDER]` (a Butterworth magnitude, order 4 by default) or `--eq_points "f,dB;f,dB;..."`
 (breakpoints, linear in dB over log-frequency) is the TRUE curve of the synthetic measurement; the two exclude each other, and without
 either the `points` of configs/inverse_problem/music_blind_equalization.yaml are used.
+
+`-t music_decompression` measures through a dynamic-range compressor with given parameters (DynamicRangeOperator): `--drc_threshold_db`,
+`--drc_ratio` (>= 1, `inf` = a limiter), `--drc_knee_db`, `--drc_attack_ms`, `--drc_release_ms`, `--drc_makeup_db`; a flag that is not
+given takes its value from configs/inverse_problem/music_decompression.yaml.
 
 `-t music_source_separation` restores K stems from their mixture under one loss (inverse_problem/mixture.py), one prompt embedding per
 stem: `--wav` names the stems whose gain-weighted sum (`--gains`) is the measurement (SI-SDR per stem is printed), `--mixture mix.wav
@@ -50,17 +55,20 @@ from diffmusic_amd.pipelines import get_pipeline                                
 from diffmusic_amd.schedulers import get_scheduler                                  # noqa: E402
 
 TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation", "music_declipping",
-         "music_blind_dereverberation", "music_source_separation", "music_spectral_inpainting", "music_blind_equalization")
+         "music_blind_dereverberation", "music_source_separation", "music_spectral_inpainting", "music_blind_equalization", "music_decompression")
 SEPARATION = "music_source_separation"
 SPECTRAL = "music_spectral_inpainting"
 BLIND_EQ = "music_blind_equalization"
+DECOMPRESSION = "music_decompression"
+DRC_FLAGS = ("threshold_db", "ratio", "knee_db", "attack_ms", "release_ms", "makeup_db")
 
 
-def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None, tf_boxes=None, eq_true=None):
+def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None, tf_boxes=None, eq_true=None, drc=None):
     """run.py:157-212: one operator per task, constructor arguments from the data / model config.  `audio_length_in_s`: the length the
     operator acts on when it is not the model window (a track).  `clip_threshold`: music_declipping's threshold(s), a float or one value
     per clip (`threshold_for_sdr` of the clean clips).  `tf_boxes`: music_spectral_inpainting's boxes (`spectral_boxes`).  `eq_true`:
-    music_blind_equalization's true curve (`equalization_curve`), kept on the operator for `forward`."""
+    music_blind_equalization's true curve (`equalization_curve`), kept on the operator for `forward`.  `drc`: music_decompression's
+    parameters (`compressor_params`)."""
     noiser = P.get_noiser(**cfg.inverse_problem.noise)
     d, scale = cfg.data, 1
     seconds = cfg.model.pipe.audio_length_in_s if audio_length_in_s is None else audio_length_in_s
@@ -96,6 +104,10 @@ def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=
                                          betas=tuple(ip.get("betas") or (0.9, 0.999)), adam_eps=float(ip.get("adam_eps") or 1e-8),
                                          init=ip.get("init") or "flat", normalize=ip.get("normalize") or "peak")
         op.true_curve = torch.as_tensor(np.asarray(eq_true, dtype=np.float32)).reshape(1, -1)
+    elif task == DECOMPRESSION:
+        if drc is None:
+            raise ValueError("music_decompression needs drc (compressor_params(args, cfg))")
+        op = P.DynamicRangeOperator(sample_rate=d.sample_rate, noiser=noiser, **drc)
     else:
         raise ValueError(f"Unknown task: {task}")
     return op, scale
@@ -176,6 +188,9 @@ def parse_args(argv=None):
                     help="music_blind_equalization: the true curve is a Butterworth low-pass magnitude at HZ (ORDER 4 by default)")
     ap.add_argument("--eq_points", default=None, metavar="F,DB;F,DB;...",
                     help="music_blind_equalization: the true curve through (Hz, dB) breakpoints, linear in dB over log-frequency")
+    for flag, what in zip(DRC_FLAGS, ("threshold in dB", "ratio >= 1, inf = a limiter", "knee width in dB, 0 = hard knee", "attack time in ms",
+                                      "release time in ms", "make-up gain in dB")):
+        ap.add_argument(f"--drc_{flag}", type=float, default=None, help=f"music_decompression: the compressor's {what} (default: the task's config)")
     ap.add_argument("--strength", type=float, default=1.0, help="share of num_inference_steps a warm start runs (diffusers' img2img rule)")
     return ap.parse_args(argv)
 
@@ -280,6 +295,26 @@ def equalization_curve(args, cfg=None):
     return P.eq_curve(sr, points)
 
 
+def compressor_params(args, cfg=None):
+    """The argument rules of -t music_decompression -> the keyword arguments of the DynamicRangeOperator: every --drc_* flag that is given,
+    the task's config for the others (the operator's defaults without a config).  argparse's float reads `inf`; the operator refuses a bad
+    value by name.  Any other task refuses the flags."""
+    given = {flag: getattr(args, f"drc_{flag}") for flag in DRC_FLAGS if getattr(args, f"drc_{flag}") is not None}
+    if args.task != DECOMPRESSION:
+        if given:
+            raise SystemExit(f"--drc_{next(iter(given))} belongs to -t {DECOMPRESSION}")
+        return None
+    out = {}
+    if cfg is not None:
+        out = {flag: float(cfg.inverse_problem.get(flag)) for flag in DRC_FLAGS if cfg.inverse_problem.get(flag) is not None}
+    out.update(given)
+    try:
+        P.DynamicRangeOperator(**out)                                              # the operator's own refusals, before any GPU work
+    except ValueError as e:
+        raise SystemExit(f"-t {DECOMPRESSION}: {e}")
+    return out
+
+
 def separation_stems(args):
     """The argument rules of -t music_source_separation -> K, the number of stems; any other task refuses the separation flags."""
     if args.task != SEPARATION:
@@ -368,7 +403,7 @@ def run_separation(args, cfg, K):
 def main(argv=None):
     args = parse_args(argv)
     overrides = [f"data={args.data}", f"model={args.model}"]
-    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL, BLIND_EQ):
+    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL, BLIND_EQ, DECOMPRESSION):
         overrides.append(f"inverse_problem={args.task}")
     stems = separation_stems(args)
     if args.project and args.task not in ("music_declipping", SEPARATION):
@@ -376,6 +411,7 @@ def main(argv=None):
     cfg = compose(args.config_name, overrides=overrides)
     tf_boxes = spectral_boxes(args, cfg)
     eq_true = equalization_curve(args, cfg)
+    drc = compressor_params(args, cfg)
     if stems is not None:
         if args.model != "musicldm":
             raise SystemExit("this driver feeds MusicLDM's class-embedding conditioning; AudioLDM2 needs its T5 / GPT-2 states (see bench.py --workload)")
@@ -392,7 +428,7 @@ def main(argv=None):
     if args.track_overlap_s is None:
         gt = load_clips(args.wav, args.batch, sr, length, args.seed).to(device)
         thr = P.threshold_for_sdr(gt, args.clip_sdr_db) if args.task == "music_declipping" else None
-        op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr, tf_boxes=tf_boxes, eq_true=eq_true)
+        op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr, tf_boxes=tf_boxes, eq_true=eq_true, drc=drc)
         B = gt.shape[0]
     else:
         if args.task == "music_generation":
@@ -402,7 +438,7 @@ def main(argv=None):
         layout = P.TrackLayout(T, length, int(round(args.track_overlap_s * sr)))
         thr = float(P.threshold_for_sdr(gt, args.clip_sdr_db)[0]) if args.task == "music_declipping" else None
         inner, scale = build_operator(args.task, cfg, args.mask_type, audio_length_in_s=P.seconds_for_samples(T, sr), clip_threshold=thr,
-                                      tf_boxes=tf_boxes, eq_true=eq_true)
+                                      tf_boxes=tf_boxes, eq_true=eq_true, drc=drc)
         op = P.TrackOperator(inner, layout)
         B = layout.num_windows
         sched_kw["per_clip_norm"] = False                                          # one loss, norms over all windows

@@ -34,7 +34,8 @@ extern "C" {
  * dmx_fir_clip_bwd / dmx_fir_wgrad / dmx_fir_wgrad_workspace_floats / dmx_ir_update (blind dereverberation: one fitted response per clip)
  * and dmx_stem_mix_fwd / dmx_stem_mix_bwd / dmx_stem_project (source separation: the stems of a mixture as the batch) and dmx_audio_tf_gain /
  * dmx_audio_tf_frames (time-frequency masking: a real gain on the STFT) and dmx_audio_tf_curve / dmx_audio_tf_wgrad /
- * dmx_audio_tf_wgrad_segments / dmx_audio_eq_update (blind equalisation: a fitted gain curve per clip) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * dmx_audio_tf_wgrad_segments / dmx_audio_eq_update (blind equalisation: a fitted gain curve per clip) and dmx_drc_fwd / dmx_drc_bwd
+ * (de-compression: a dynamic-range compressor and the transpose of its Jacobian) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
  * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
@@ -262,6 +263,23 @@ int dmx_clip_bwd(const float* dy, long long dy_stride, const float* wav, long lo
                  long long dwav_stride, int batch, int L, int Lfull, void* stream);
 int dmx_declip_project(const float* xhat, long long xhat_stride, const float* meas, long long meas_stride, const float* thr, float* out,
                        long long out_stride, int batch, int L, void* stream);
+/* Dynamic-range compression on materialised waveforms (csrc/drc.hip): a feed-forward compressor whose sidechain
+ * runs on blocks of 64 samples, H = ceil(L / 64) blocks per clip, the clip taken as zero outside [0, L).  Parameters, shared by all clips:
+ * threshold_db and makeup_db (finite, within +-200), slope = 1 - 1 / ratio in [0, 1] (1 = limiter), knee_db in [0, 200], a_att and a_rel in
+ * (0, 1], the follower's per-block coefficients 1 - exp(-64 / (fs t)).
+ *   drc_fwd   y[b, 0:L] = g x; state (batch, 3, H) receives the rows p (block power), G (block gain) and s (gain reduction in dB) of each
+ *             clip, tape (batch, H) one byte per block: bits 0-1 the region of the static curve, bit 2 the attack gate
+ *   drc_bwd   dx[b, 0:L] = the transpose of the Jacobian of drc_fwd at x applied to dy, +0 on [L, Lfull); takes the state and the tape that
+ *             drc_fwd wrote for the same x and parameters and never decides a gate again; work: batch * H floats of scratch
+ * Three launches each, no atomics, bit-reproducible and independent of the batch position.  A NaN sample of x: drc_fwd gives NaN from the
+ * first sample of its block to the end of its clip (y; G and s from that block on) and leaves everything before it bit-equal; drc_bwd gives
+ * NaN for the WHOLE dx of that clip (the backward recurrence carries it to block 0).  Other clips are untouched by both.  DMX_ERR_SHAPE, with nothing written, for a null
+ * pointer, batch outside 1 .. 65535, L < 1, Lfull < L, a length above 2^30, a row stride below its row, or a parameter outside its range. */
+int dmx_drc_fwd(const float* x, long long x_stride, float* y, long long y_stride, float* state, unsigned char* tape, int batch, int L,
+                float threshold_db, float slope, float knee_db, float a_att, float a_rel, float makeup_db, void* stream);
+int dmx_drc_bwd(const float* dy, long long dy_stride, const float* x, long long x_stride, const float* state, const unsigned char* tape,
+                float* work, float* dx, long long dx_stride, int batch, int L, int Lfull, float threshold_db, float slope, float knee_db,
+                float a_att, float a_rel, float makeup_db, void* stream);
 /* out[i] = y[i] + scale * z[i], i < n (the noiser on a materialised measurement A(x): super-resolution, dereverberation, wav_form) */
 int dmx_noise_add(const float* y, const float* z, float* out, long long n, float scale, void* stream);
 /* PhaseRetrievalOperator.forward: |torch.stft(wav)| as (B, n_fft/2+1, frames) fp32 */
