@@ -1,11 +1,13 @@
-"""The ctypes spelling of the op surface: one function per op registered in csrc_torch/torch_ops.cpp, with the op's name, positional
-parameters, return values, dtypes and shapes, over the same `extern "C"` launchers of libdiffmusic_hip.so (`_lib.py`).  Outputs come
-from torch's caching allocator, launches go to torch's current HIP stream, model / audio handles arrive as Python ints.
+"""The ctypes spelling of the op surface: one function per op registered in csrc_torch/torch_ops.cpp, with the op's name, parameters
+(names, order, positional / keyword-only split, defaults), return values, dtypes and shapes, over the same `extern "C"` launchers of
+libdiffmusic_hip.so (`_lib.py`).  Outputs come from torch's caching allocator, launches go to torch's current HIP stream, model /
+audio handles arrive as Python ints.
 
-`ops.hip.<name>` resolves here when the op library is switched off or unavailable (ops.py); `ops.ctypes_hip` is this module.  Where
-a C entry point takes more than the op schema expresses (caller-owned outputs, row strides, prediction type and clip range, a mel
-width other than 64, a U-Net whose output channels differ from its input's) the function takes it as trailing keyword-only
-parameters; tests/test_abi.py holds the positional signatures equal to the schemas."""
+`ops.hip.<name>` resolves here when the op library is switched off or unavailable (ops.py); `ops.ctypes_hip` is this module.  There
+is one function per operation: what it can do beyond its plain form (caller-owned outputs with their row strides, prediction type and
+clip range, measurement noise and clip thresholds of the guidance pair, a dead span, context tensors, a U-Net whose output channels
+differ from its input's) is a defaulted parameter, and the function calls the longest rung of the C ABI's additive ladder
+(_ex / _shaped / _ctx / _dead), which stays for C callers.  tests/test_abi.py holds every signature equal to its schema."""
 import ctypes as C
 
 import torch
@@ -60,7 +62,7 @@ def sched_update(mode, x, eps, x0, g0, inv_scale, noise, alpha_t, alpha_prev, si
 
 
 def randn_philox(shape, seeds, offset, device):
-    """Seeds are taken modulo 2^64 (the op's int[] holds signed 64-bit values only)."""
+    """Seeds and offset are taken modulo 2^64 (the op's ints are signed 64-bit: `torch_utils.randn_philox` folds larger values)."""
     B = int(shape[0])
     n = 1
     for d in shape[1:]:
@@ -74,6 +76,8 @@ def randn_philox(shape, seeds, offset, device):
 # ---- measurement operators and the loss
 def mask_mul(x, mask, L, Ly):
     """y[:, :L] = x[:, :L] * mask (None: copy), zeros up to Ly; x (B, >= L) with any row stride."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1, ("mask_mul", x.shape)
+    assert mask is None or (mask.dtype == torch.float32 and mask.is_contiguous()), "mask_mul: mask must be contiguous fp32"
     B = x.shape[0]
     y = torch.empty(B, Ly, dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().dmx_mask_apply(_p(x), x.stride(0), _p(mask), _p(y), Ly, B, L, Ly, _stream()), "mask_mul")
@@ -81,7 +85,8 @@ def mask_mul(x, mask, L, Ly):
 
 
 def l2norm(ref, pred, gscale, *, want_grad=True):
-    """-> (loss (B), dpred like pred, or None when want_grad is False)."""
+    """-> (loss (B), dpred like pred, or None when want_grad is False); ref and pred contiguous."""
+    assert ref.is_contiguous() and pred.is_contiguous(), ("l2norm", ref.shape, pred.shape)
     B = pred.shape[0]
     n = pred[0].numel()
     loss = torch.empty(B, dtype=torch.float32, device=pred.device)
@@ -168,11 +173,12 @@ def ir_update(partials, h, h_rev, m, v, k, lr, beta1, beta2, eps):
                                         float(eps), int(k), _stream()), "ir_update")
 
 
-def logmel_fwd(audio, wav, state, L, power2, to_db, lo, hi, *, out=None, n_mels=64):
-    """out: caller-owned (B, frames, n_mels) result; n_mels: the handle's mel width (the op allocates 64 columns)."""
+def logmel_fwd(audio, wav, state, L, power2, to_db, lo, hi, *, out=None):
+    """out: caller-owned contiguous (B, frames, 64) result."""
     lib = _lib.lib()
-    B = wav.shape[0]
-    mel = out if out is not None else torch.empty(B, lib.dmx_audio_num_frames(audio, L), n_mels, dtype=torch.float32, device=wav.device)
+    B, T = wav.shape[0], lib.dmx_audio_num_frames(audio, L)
+    assert out is None or (out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * T * 64), ("logmel_fwd", out.shape)
+    mel = out if out is not None else torch.empty(B, T, 64, dtype=torch.float32, device=wav.device)
     _lib.check(lib.dmx_audio_transform_fwd(audio, _p(wav), wav.stride(0), _p(mel), _p(state), B, L, int(power2), int(to_db), lo, hi,
                                            _stream()), "audio_transform_fwd")
     return mel
@@ -183,50 +189,18 @@ def logmel_bwd(audio, dmel, state, L, power2, to_db, lo, hi, *, dwav=None):
     B = dmel.shape[0]
     if dwav is None:
         dwav = torch.empty(B, L, dtype=torch.float32, device=dmel.device)
+    else:
+        _rows("logmel_bwd", dwav, L)
     _lib.check(_lib.lib().dmx_audio_transform_bwd(audio, _p(dmel), _p(dwav), dwav.stride(0), _p(state), B, L, int(power2), int(to_db),
                                                   lo, hi, 0, _stream()), "audio_transform_bwd")
     return dwav
 
 
-def mel_guidance(audio, wav, mask, ref, state, L, Lfull, power2, to_db, lo, hi, gscale):
-    lib = _lib.lib()
-    B = wav.shape[0]
-    T = lib.dmx_audio_num_frames(audio, L)
-    assert ref.numel() in (T * 64, B * T * 64), (ref.shape, B, T)
-    rs = 0 if (ref.numel() == T * 64 and B > 1) else T * 64
-    loss = torch.empty(B, dtype=torch.float32, device=wav.device)
-    dwav = torch.empty(B, Lfull, dtype=torch.float32, device=wav.device)
-    _lib.check(lib.dmx_audio_guidance_fwd(audio, _p(wav), wav.stride(0), _p(mask), _p(ref), rs, None, _p(state), B, L, int(power2),
-                                          int(to_db), lo, hi, _stream()), "audio_guidance_fwd")
-    _lib.check(lib.dmx_audio_guidance_bwd(audio, _p(wav), wav.stride(0), _p(mask), _p(ref), rs, gscale, _p(loss), _p(dwav), Lfull, Lfull,
-                                          _p(state), B, L, int(power2), int(to_db), lo, hi, _stream()), "audio_guidance_bwd")
-    return loss, dwav
-
-
-def mel_guidance_noisy(audio, wav, mask, ref, state, L, Lfull, power2, to_db, lo, hi, gscale, noise, noise_mag, sigma):
-    """mel_guidance with the step's measurement noise: noise (B, >= L) in the sample domain (y = wav * mask + sigma * noise) and / or
-    noise_mag (B, bins, frames) on the magnitudes (power2 False only); standard-normal draws, either may be None."""
-    lib = _lib.lib()
-    B = wav.shape[0]
-    T = lib.dmx_audio_num_frames(audio, L)
-    assert ref.numel() in (T * 64, B * T * 64), (ref.shape, B, T)
-    assert noise is None or (noise.shape[0] == B and noise.shape[1] >= L and noise.stride(1) == 1), noise.shape
-    assert noise_mag is None or (noise_mag.is_contiguous() and noise_mag.numel() == B * lib.dmx_audio_num_bins(audio) * T), noise_mag.shape
-    rs = 0 if (ref.numel() == T * 64 and B > 1) else T * 64
-    ns = noise.stride(0) if noise is not None else 0
-    loss = torch.empty(B, dtype=torch.float32, device=wav.device)
-    dwav = torch.empty(B, Lfull, dtype=torch.float32, device=wav.device)
-    _lib.check(lib.dmx_audio_guidance_fwd_ex(audio, _p(wav), wav.stride(0), _p(mask), _p(ref), rs, None, _p(state), B, L, int(power2),
-                                             int(to_db), lo, hi, _p(noise), ns, _p(noise_mag), sigma, _stream()), "audio_guidance_fwd_ex")
-    _lib.check(lib.dmx_audio_guidance_bwd_ex(audio, _p(wav), wav.stride(0), _p(mask), _p(ref), rs, gscale, _p(loss), _p(dwav), Lfull, Lfull,
-                                             _p(state), B, L, int(power2), int(to_db), lo, hi, _p(noise), ns, _p(noise_mag), sigma, _stream()),
-               "audio_guidance_bwd_ex")
-    return loss, dwav
-
-
-def mel_guidance_shaped(audio, wav, mask, ref, state, L, Lfull, power2, to_db, lo, hi, gscale, noise, noise_mag, sigma, thr):
-    """mel_guidance_noisy with a hard clip between the mask and the noise: thr (B) fp32 per-clip thresholds c > 0, y = clip(wav * mask, c) +
-    sigma * noise, gradient through -c <= wav * mask <= c only.  thr None: mel_guidance_noisy, bit for bit."""
+def mel_guidance(audio, wav, mask, ref, state, L, Lfull, power2, to_db, lo, hi, gscale, noise=None, noise_mag=None, sigma=0.0, thr=None):
+    """The fused guidance pair -> (loss (B), dwav (B, Lfull)).  The step's measurement noise: noise (B, >= L) in the sample domain and / or
+    noise_mag (B, bins, frames) on the magnitudes (power2 False only), standard-normal draws used as sigma * noise.  thr (B) fp32: per-clip
+    hard-clip thresholds c > 0 between the mask and the noise, y = clip(wav * mask, c) + sigma * noise, gradient through
+    -c <= wav * mask <= c only."""
     lib = _lib.lib()
     B = wav.shape[0]
     T = lib.dmx_audio_num_frames(audio, L)
@@ -474,35 +448,34 @@ def stft_mag_fwd(audio, wav, state, L):
 
 
 def stft_mag_bwd(audio, dmag, state, L, Lfull, *, dwav=None):
-    """dwav: caller-owned (B, >= L) result with any row stride (overwritten up to L; the op returns zeros past L)."""
+    """dwav: caller-owned (B, >= L) result with any row stride, overwritten up to L; without it -> (B, Lfull) with zeros past L."""
     B = dmag.shape[0]
     if dwav is None:
         dwav = torch.zeros(B, Lfull, dtype=torch.float32, device=dmag.device)
+    else:
+        _rows("stft_mag_bwd", dwav, L)
     _lib.check(_lib.lib().dmx_audio_stft_mag_bwd(audio, _p(dmag), _p(dwav), dwav.stride(0), _p(state), B, L, 0, _stream()), "stft_mag_bwd")
     return dwav
 
 
-def melscale_fwd(audio, mag, lo, hi, *, n_mels=64):
+def melscale_fwd(audio, mag, lo, hi):
     B, _, T = mag.shape
-    mel = torch.empty(B, T, n_mels, dtype=torch.float32, device=mag.device)
+    mel = torch.empty(B, T, 64, dtype=torch.float32, device=mag.device)
     _lib.check(_lib.lib().dmx_audio_melscale(audio, _p(mag), _p(mel), B, T, lo, hi, _stream()), "melscale")
     return mel
 
 
 # ---- networks (workspaces are caller-owned byte tensors sized by *_workspace_bytes)
-def unet_fwd(model, x, t, class_labels, ws, *, out_channels=None):
-    """out_channels: of the U-Net when they differ from x's (the op returns eps shaped like x)."""
+def unet_fwd(model, x, t, class_labels, ws, c0=None, c1=None, bias1=None, *, out_channels=None):
+    """c0 (B, n0, d0), c1 (B, n1, d1), bias1 (B, n1): the two context streams of the AudioLDM2 U-Net and the additive key bias of the
+    second, all three or none.  out_channels: of the U-Net when they differ from x's -> eps (B, out_channels or C, h, w)."""
+    if not ((c0 is None) == (c1 is None) == (bias1 is None)):
+        raise RuntimeError("unet_fwd: c0, c1 and bias1 go together, all three or none")
     B, Cin, h, w = x.shape
-    eps = torch.empty(B, out_channels or Cin, h, w, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().dmx_unet_fwd(model, _p(x), _p(t), _p(class_labels), _p(eps), B, h, w, _p(ws), ws.numel(), _stream()), "unet_fwd")
-    return eps
-
-
-def unet_fwd_ctx(model, x, t, class_labels, c0, c1, bias1, ws, *, out_channels=None):
-    B, Cin, h, w = x.shape
-    eps = torch.empty(B, out_channels or Cin, h, w, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().dmx_unet_fwd_ctx(model, _p(x), _p(t), _p(class_labels), _p(c0), c0.shape[1], _p(c1), c1.shape[1], _p(bias1),
-                                           _p(eps), B, h, w, _p(ws), ws.numel(), _stream()), "unet_fwd_ctx")
+    n0, n1 = (c0.shape[1], c1.shape[1]) if c0 is not None else (0, 0)
+    eps = torch.empty(B, Cin if out_channels is None else out_channels, h, w, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_unet_fwd_ctx(model, _p(x), _p(t), _p(class_labels), _p(c0), n0, _p(c1), n1, _p(bias1), _p(eps), B, h, w,
+                                           _p(ws), ws.numel(), _stream()), "unet_fwd")
     return eps
 
 
@@ -554,20 +527,13 @@ def grad_normalize_(dwav, target):
     return inv_scale
 
 
-def hifigan_fwd(model, mel, ws):
-    lib = _lib.lib()
-    B, T, _ = mel.shape
-    wav = torch.empty(B, lib.dmx_hifigan_out_len(model, T), dtype=torch.float32, device=mel.device)
-    _lib.check(lib.dmx_hifigan_fwd(model, _p(mel), _p(wav), B, T, _p(ws), ws.numel(), _stream()), "hifigan_fwd")
-    return wav
-
-
-def hifigan_fwd_dead(model, mel, s0, s1, ws):
-    """hifigan_fwd for a loss that never looks at the samples [s0, s1) of any clip: zeros there, the same bits elsewhere."""
+def hifigan_fwd(model, mel, ws, s0=0, s1=0):
+    """[s0, s1): samples of every clip that the caller's loss never looks at: zeros there, the same bits elsewhere (an empty span: the
+    plain forward)."""
     B, T, _ = mel.shape
     lib = _lib.lib()
     wav = torch.empty(B, lib.dmx_hifigan_out_len(model, T), dtype=torch.float32, device=mel.device)
-    _lib.check(lib.dmx_hifigan_fwd_dead(model, _p(mel), _p(wav), B, T, int(s0), int(s1), _p(ws), ws.numel(), _stream()), "hifigan_fwd_dead")
+    _lib.check(lib.dmx_hifigan_fwd_dead(model, _p(mel), _p(wav), B, T, int(s0), int(s1), _p(ws), ws.numel(), _stream()), "hifigan_fwd")
     return wav
 
 

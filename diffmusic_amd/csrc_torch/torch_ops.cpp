@@ -71,12 +71,17 @@ inline void act_cuda(const at::Tensor& t, const char* name) {
 inline const float* fp(const std::optional<at::Tensor>& t) { return t.has_value() ? t->data_ptr<float>() : nullptr; }
 
 // ---- scheduler arithmetic (scheduling_{ddim,dps,mpgd,dsg,diffmusic}.py step bodies; pipeline_musicldm.py:706-708)
-at::Tensor sched_pred_x0(const at::Tensor& x, const at::Tensor& eps, double alpha_t) {
+// ptype / clip_r: the DDIM parent's other branches (sample / v_prediction, clip_sample); the defaults keep the epsilon kernel
+at::Tensor sched_pred_x0(const at::Tensor& x, const at::Tensor& eps, double alpha_t, int64_t ptype, double clip_r) {
   f32_cuda(x, "x"); f32_cuda(eps, "eps");
   same_numel(x, eps, "sched_pred_x0(x, eps)");
   DMX_DEVICE_OF(x);
   at::Tensor x0 = at::empty_like(x);
-  ok(dmx_sched_pred_x0(x.data_ptr<float>(), eps.data_ptr<float>(), x0.data_ptr<float>(), x.numel(), (float)alpha_t, cur_stream()), "sched_pred_x0");
+  if (ptype == 0 && clip_r == 0.0)
+    ok(dmx_sched_pred_x0(x.data_ptr<float>(), eps.data_ptr<float>(), x0.data_ptr<float>(), x.numel(), (float)alpha_t, cur_stream()), "sched_pred_x0");
+  else
+    ok(dmx_sched_pred_x0_ex(x.data_ptr<float>(), eps.data_ptr<float>(), x0.data_ptr<float>(), x.numel(), (float)alpha_t, (int)ptype, (float)clip_r,
+                            cur_stream()), "sched_pred_x0");
   return x0;
 }
 at::Tensor cfg_combine(const at::Tensor& eps2, double scale) {
@@ -89,12 +94,13 @@ at::Tensor cfg_combine(const at::Tensor& eps2, double scale) {
   ok(dmx_sched_cfg_combine(eps2.data_ptr<float>(), out.data_ptr<float>(), out.numel(), (float)scale, cur_stream()), "cfg_combine");
   return out;
 }
-// returns (prev_sample, x0_updated): the second is MPGD's guided x0 (scheduling_mpgd.py:202) and None for every other mode (no output
-// aliases an input: the schema is a plain functional op)
+// returns (prev_sample, x0_updated): the second is MPGD's guided x0 (scheduling_mpgd.py:202) and None for every other mode.
+// grad_out: caller-owned tensor like x that receives the applied gradient; ptype / clip_r as in sched_pred_x0
 std::tuple<at::Tensor, std::optional<at::Tensor>> sched_update(int64_t mode, const at::Tensor& x, const at::Tensor& eps, const at::Tensor& x0,
                                                 const std::optional<at::Tensor>& g0, const std::optional<at::Tensor>& inv_scale,
                                                 const std::optional<at::Tensor>& noise, double alpha_t, double alpha_prev, double sigma,
-                                                double rate, double eps_small, bool global_norm) {
+                                                double rate, double eps_small, bool global_norm, int64_t ptype, double clip_r,
+                                                const std::optional<at::Tensor>& grad_out) {
   f32_cuda(x, "x"); f32_cuda(eps, "eps"); f32_cuda(x0, "x0");
   TORCH_CHECK(x.dim() >= 1 && x.size(0) >= 1, "x must have a batch dimension");
   same_numel(x, eps, "sched_update(x, eps)"); same_numel(x, x0, "sched_update(x, x0)");
@@ -103,14 +109,22 @@ std::tuple<at::Tensor, std::optional<at::Tensor>> sched_update(int64_t mode, con
   if (g0) { f32_cuda(*g0, "g0"); same_numel(x, *g0, "sched_update(x, g0)"); }
   if (inv_scale) { f32_cuda(*inv_scale, "inv_scale"); TORCH_CHECK(inv_scale->numel() == B && inv_scale->device() == x.device(), "inv_scale must hold one value per clip"); }
   if (noise) { f32_cuda(*noise, "noise"); same_numel(x, *noise, "sched_update(x, noise)"); }
+  if (grad_out) { f32_cuda(*grad_out, "grad_out"); same_numel(x, *grad_out, "sched_update(x, grad_out)"); }
   TORCH_CHECK(mode == DMX_SCHED_DDIM || (g0 && inv_scale), "guided modes need g0 and inv_scale");
   DMX_DEVICE_OF(x);
   at::Tensor prev = at::empty_like(x);
   std::optional<at::Tensor> x0_out;
   if (mode == DMX_SCHED_MPGD) x0_out = at::empty_like(x);
-  ok(dmx_sched_step((int)mode, x.data_ptr<float>(), eps.data_ptr<float>(), x0.data_ptr<float>(), fp(g0), fp(inv_scale), fp(noise),
-                    prev.data_ptr<float>(), x0_out ? x0_out->data_ptr<float>() : nullptr, nullptr, B, n, (float)alpha_t,
-                    (float)alpha_prev, (float)sigma, (float)rate, (float)eps_small, global_norm ? 1 : 0, cur_stream()), "sched_update");
+  float* const x0o = x0_out ? x0_out->data_ptr<float>() : nullptr;
+  float* const go = grad_out ? grad_out->data_ptr<float>() : nullptr;
+  if (ptype == 0 && clip_r == 0.0)
+    ok(dmx_sched_step((int)mode, x.data_ptr<float>(), eps.data_ptr<float>(), x0.data_ptr<float>(), fp(g0), fp(inv_scale), fp(noise),
+                      prev.data_ptr<float>(), x0o, go, B, n, (float)alpha_t, (float)alpha_prev, (float)sigma, (float)rate, (float)eps_small,
+                      global_norm ? 1 : 0, cur_stream()), "sched_update");
+  else
+    ok(dmx_sched_step_ex((int)mode, x.data_ptr<float>(), eps.data_ptr<float>(), x0.data_ptr<float>(), fp(g0), fp(inv_scale), fp(noise),
+                         prev.data_ptr<float>(), x0o, go, B, n, (float)alpha_t, (float)alpha_prev, (float)sigma, (float)rate, (float)eps_small,
+                         global_norm ? 1 : 0, (int)ptype, (float)clip_r, cur_stream()), "sched_update");
   return {prev, x0_out};
 }
 at::Tensor randn_philox(at::IntArrayRef shape, at::IntArrayRef seeds, int64_t offset, at::Device device) {
@@ -132,15 +146,18 @@ at::Tensor mask_mul(const at::Tensor& x, const std::optional<at::Tensor>& mask, 
   ok(dmx_mask_apply(x.data_ptr<float>(), x.stride(0), fp(mask), y.data_ptr<float>(), Ly, (int)x.size(0), (int)L, (int)Ly, cur_stream()), "mask_mul");
   return y;
 }
-std::tuple<at::Tensor, at::Tensor> l2norm(const at::Tensor& ref, const at::Tensor& pred, double gscale) {
+// (loss (B), dpred like pred, or None when want_grad is false)
+std::tuple<at::Tensor, std::optional<at::Tensor>> l2norm(const at::Tensor& ref, const at::Tensor& pred, double gscale, bool want_grad) {
   f32_cuda(ref, "ref"); f32_cuda(pred, "pred");
   DMX_DEVICE_OF(pred);
   const int B = (int)pred.size(0);
   const long long n = pred.numel() / B;
   TORCH_CHECK((ref.numel() == n || ref.numel() == n * B) && ref.device() == pred.device(), "ref must match pred or broadcast over the batch");
-  at::Tensor loss = at::empty({B}, pred.options()), dpred = at::empty_like(pred);
-  ok(dmx_l2_loss(ref.data_ptr<float>(), ref.numel() == n && B > 1 ? 0 : n, pred.data_ptr<float>(), loss.data_ptr<float>(), dpred.data_ptr<float>(),
-                 B, n, (float)gscale, cur_stream()), "l2norm");
+  at::Tensor loss = at::empty({B}, pred.options());
+  std::optional<at::Tensor> dpred;
+  if (want_grad) dpred = at::empty_like(pred);
+  ok(dmx_l2_loss(ref.data_ptr<float>(), ref.numel() == n && B > 1 ? 0 : n, pred.data_ptr<float>(), loss.data_ptr<float>(),
+                 dpred ? dpred->data_ptr<float>() : nullptr, B, n, (float)gscale, cur_stream()), "l2norm");
   return {loss, dpred};
 }
 at::Tensor resample_fwd(const at::Tensor& x, const at::Tensor& h, int64_t Lin, int64_t Lout, int64_t orig, int64_t new_, int64_t off) {
@@ -216,88 +233,51 @@ void ir_update(const at::Tensor& partials, at::Tensor h, at::Tensor h_rev, at::T
   ok(dmx_ir_update(partials.data_ptr<float>(), (int)partials.size(1), h.data_ptr<float>(), h_rev.data_ptr<float>(), m.data_ptr<float>(),
                    v.data_ptr<float>(), (int)B, (int)n, lr, beta1, beta2, eps, (int)k, cur_stream()), "ir_update");
 }
-at::Tensor logmel_fwd(int64_t audio, const at::Tensor& wav, const at::Tensor& state, int64_t L, bool power2, bool to_db, double lo, double hi) {
+// a caller-owned waveform-shaped result (`dwav=` / `out=`): (B, >= L) fp32 rows of any stride on `like`'s device, else a fresh (B, cols)
+inline at::Tensor rows_out(const std::optional<at::Tensor>& given, const at::Tensor& like, int64_t L, int64_t cols, bool zeroed, const char* name) {
+  if (!given) return zeroed ? at::zeros({like.size(0), cols}, like.options()) : at::empty({like.size(0), cols}, like.options());
+  TORCH_CHECK(given->is_cuda() && given->device() == like.device() && given->scalar_type() == at::kFloat && given->dim() == 2 &&
+              given->stride(1) == 1 && given->size(0) == like.size(0) && given->size(1) >= L, name, " must be (B, >= L) fp32 on the input's device");
+  return *given;
+}
+// out: caller-owned contiguous (B, frames, 64) result
+at::Tensor logmel_fwd(int64_t audio, const at::Tensor& wav, const at::Tensor& state, int64_t L, bool power2, bool to_db, double lo, double hi,
+                      const std::optional<at::Tensor>& out) {
   dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
   TORCH_CHECK(wav.is_cuda() && wav.scalar_type() == at::kFloat && wav.dim() == 2 && wav.stride(1) == 1, "wav must be (B, >= L) fp32 on the GPU");
   DMX_DEVICE_OF(wav);
   TORCH_CHECK(state.is_cuda() && (size_t)state.nbytes() >= dmx_audio_state_bytes(a, (int)wav.size(0), (int)L), "state buffer too small");
-  at::Tensor mel = at::empty({wav.size(0), dmx_audio_num_frames(a, (int)L), 64}, wav.options());
+  const int64_t T = dmx_audio_num_frames(a, (int)L);
+  if (out) { f32_cuda(*out, "out"); TORCH_CHECK(out->numel() == wav.size(0) * T * 64 && out->device() == wav.device(), "out must be (B, frames, 64)"); }
+  at::Tensor mel = out ? *out : at::empty({wav.size(0), T, 64}, wav.options());
   ok(dmx_audio_transform_fwd(a, wav.data_ptr<float>(), wav.stride(0), mel.data_ptr<float>(), state.data_ptr(), (int)wav.size(0), (int)L,
                              power2, to_db, (float)lo, (float)hi, cur_stream()), "logmel_fwd");
   return mel;
 }
-at::Tensor logmel_bwd(int64_t audio, const at::Tensor& dmel, const at::Tensor& state, int64_t L, bool power2, bool to_db, double lo, double hi) {
+// dwav: caller-owned (B, >= L) result with any row stride, overwritten up to L
+at::Tensor logmel_bwd(int64_t audio, const at::Tensor& dmel, const at::Tensor& state, int64_t L, bool power2, bool to_db, double lo, double hi,
+                      const std::optional<at::Tensor>& dwav) {
   dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
   f32_cuda(dmel, "dmel");
   DMX_DEVICE_OF(dmel);
-  at::Tensor dwav = at::empty({dmel.size(0), L}, dmel.options());
-  ok(dmx_audio_transform_bwd(a, dmel.data_ptr<float>(), dwav.data_ptr<float>(), L, state.data_ptr(), (int)dmel.size(0), (int)L, power2, to_db,
+  at::Tensor d = rows_out(dwav, dmel, L, L, false, "dwav");
+  ok(dmx_audio_transform_bwd(a, dmel.data_ptr<float>(), d.data_ptr<float>(), d.stride(0), state.data_ptr(), (int)dmel.size(0), (int)L, power2, to_db,
                              (float)lo, (float)hi, 0, cur_stream()), "logmel_bwd");
-  return dwav;
+  return d;
 }
-// fused guidance of the mel-space operators (include/diffmusic_hip.h dmx_audio_guidance_{fwd,bwd}): (loss (B), dwav (B, Lfull))
-std::tuple<at::Tensor, at::Tensor> mel_guidance(int64_t audio, const at::Tensor& wav, const std::optional<at::Tensor>& mask, const at::Tensor& ref,
-                                                at::Tensor state, int64_t L, int64_t Lfull, bool power2, bool to_db, double lo, double hi, double gscale) {
-  dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
-  TORCH_CHECK(wav.is_cuda() && wav.scalar_type() == at::kFloat && wav.dim() == 2 && wav.stride(1) == 1 && wav.size(1) >= L, "wav must be (B, >= L) fp32 on the GPU");
-  DMX_DEVICE_OF(wav);
-  f32_cuda(ref, "ref");
-  if (mask) { f32_cuda(*mask, "mask"); TORCH_CHECK(mask->numel() >= L && mask->device() == wav.device(), "mask must hold L samples"); }
-  const int B = (int)wav.size(0), T = dmx_audio_num_frames(a, (int)L);
-  TORCH_CHECK(ref.device() == wav.device() && (ref.numel() == (int64_t)T * 64 || ref.numel() == (int64_t)B * T * 64), "ref must be (B or 1, frames, 64)");
-  TORCH_CHECK(state.is_cuda() && (size_t)state.nbytes() >= dmx_audio_state_bytes(a, B, (int)L), "state buffer too small");
-  TORCH_CHECK(Lfull >= L, "Lfull < L");
-  const long long rs = ref.numel() == (int64_t)T * 64 && B > 1 ? 0 : (long long)T * 64;
-  at::Tensor loss = at::empty({B}, wav.options()), dwav = at::empty({B, Lfull}, wav.options());
-  ok(dmx_audio_guidance_fwd(a, wav.data_ptr<float>(), wav.stride(0), fp(mask), ref.data_ptr<float>(), rs, nullptr, state.data_ptr(), B, (int)L,
-                            power2, to_db, (float)lo, (float)hi, cur_stream()), "mel_guidance (forward)");
-  ok(dmx_audio_guidance_bwd(a, wav.data_ptr<float>(), wav.stride(0), fp(mask), ref.data_ptr<float>(), rs, (float)gscale, loss.data_ptr<float>(),
-                            dwav.data_ptr<float>(), Lfull, (int)Lfull, state.data_ptr(), B, (int)L, power2, to_db, (float)lo, (float)hi, cur_stream()),
-     "mel_guidance (backward)");
-  return {loss, dwav};
-}
-// the same pair with the step's measurement noise (dmx_audio_guidance_{fwd,bwd}_ex): standard-normal `noise` (B, >= L) in the sample domain
-// and / or `noise_mag` (B, bins, frames) on the magnitudes, used as sigma * noise
-std::tuple<at::Tensor, at::Tensor> mel_guidance_noisy(int64_t audio, const at::Tensor& wav, const std::optional<at::Tensor>& mask, const at::Tensor& ref,
-                                                      at::Tensor state, int64_t L, int64_t Lfull, bool power2, bool to_db, double lo, double hi, double gscale,
-                                                      const std::optional<at::Tensor>& noise, const std::optional<at::Tensor>& noise_mag, double sigma) {
-  dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
-  TORCH_CHECK(wav.is_cuda() && wav.scalar_type() == at::kFloat && wav.dim() == 2 && wav.stride(1) == 1 && wav.size(1) >= L, "wav must be (B, >= L) fp32 on the GPU");
-  DMX_DEVICE_OF(wav);
-  f32_cuda(ref, "ref");
-  if (mask) { f32_cuda(*mask, "mask"); TORCH_CHECK(mask->numel() >= L && mask->device() == wav.device(), "mask must hold L samples"); }
-  const int B = (int)wav.size(0), T = dmx_audio_num_frames(a, (int)L);
-  if (noise) TORCH_CHECK(noise->is_cuda() && noise->device() == wav.device() && noise->scalar_type() == at::kFloat && noise->dim() == 2 && noise->stride(1) == 1 &&
-                         noise->size(0) == B && noise->size(1) >= L, "noise must be (B, >= L) fp32 on wav's device");
-  if (noise_mag) {
-    f32_cuda(*noise_mag, "noise_mag");
-    TORCH_CHECK(!power2 && noise_mag->device() == wav.device() && noise_mag->numel() == (int64_t)B * dmx_audio_num_bins(a) * T,
-                "noise_mag must be (B, bins, frames) and goes with power2 = False");
-  }
-  TORCH_CHECK(ref.device() == wav.device() && (ref.numel() == (int64_t)T * 64 || ref.numel() == (int64_t)B * T * 64), "ref must be (B or 1, frames, 64)");
-  TORCH_CHECK(state.is_cuda() && (size_t)state.nbytes() >= dmx_audio_state_bytes(a, B, (int)L), "state buffer too small");
-  TORCH_CHECK(Lfull >= L, "Lfull < L");
-  const long long rs = ref.numel() == (int64_t)T * 64 && B > 1 ? 0 : (long long)T * 64;
-  const long long ns = noise ? noise->stride(0) : 0;
-  at::Tensor loss = at::empty({B}, wav.options()), dwav = at::empty({B, Lfull}, wav.options());
-  ok(dmx_audio_guidance_fwd_ex(a, wav.data_ptr<float>(), wav.stride(0), fp(mask), ref.data_ptr<float>(), rs, nullptr, state.data_ptr(), B, (int)L,
-                               power2, to_db, (float)lo, (float)hi, fp(noise), ns, fp(noise_mag), (float)sigma, cur_stream()), "mel_guidance_noisy (forward)");
-  ok(dmx_audio_guidance_bwd_ex(a, wav.data_ptr<float>(), wav.stride(0), fp(mask), ref.data_ptr<float>(), rs, (float)gscale, loss.data_ptr<float>(),
-                               dwav.data_ptr<float>(), Lfull, (int)Lfull, state.data_ptr(), B, (int)L, power2, to_db, (float)lo, (float)hi, fp(noise), ns,
-                               fp(noise_mag), (float)sigma, cur_stream()), "mel_guidance_noisy (backward)");
-  return {loss, dwav};
-}
-// the same pair with a hard clip between the mask and the noise (dmx_audio_guidance_{fwd,bwd}_shaped): thr (B) per-clip thresholds; thr None
-// is mel_guidance_noisy
 inline void thr_ok(const std::optional<at::Tensor>& thr, const at::Tensor& like, int64_t B) {
   if (!thr) return;
   f32_cuda(*thr, "thr");
   TORCH_CHECK(thr->numel() == B && thr->device() == like.device(), "thr must hold one threshold per clip on the waveform's device");
 }
-std::tuple<at::Tensor, at::Tensor> mel_guidance_shaped(int64_t audio, const at::Tensor& wav, const std::optional<at::Tensor>& mask, const at::Tensor& ref,
-                                                       at::Tensor state, int64_t L, int64_t Lfull, bool power2, bool to_db, double lo, double hi, double gscale,
-                                                       const std::optional<at::Tensor>& noise, const std::optional<at::Tensor>& noise_mag, double sigma,
-                                                       const std::optional<at::Tensor>& thr) {
+// fused guidance of the mel-space operators (include/diffmusic_hip.h dmx_audio_guidance_{fwd,bwd}_shaped, which the shorter C entry points
+// forward to with null pointers): (loss (B), dwav (B, Lfull)).  The step's measurement noise, used as sigma * noise: standard-normal `noise`
+// (B, >= L) in the sample domain and / or `noise_mag` (B, bins, frames) on the magnitudes; thr (B): per-clip hard-clip thresholds between
+// the mask and the noise
+std::tuple<at::Tensor, at::Tensor> mel_guidance(int64_t audio, const at::Tensor& wav, const std::optional<at::Tensor>& mask, const at::Tensor& ref,
+                                                at::Tensor state, int64_t L, int64_t Lfull, bool power2, bool to_db, double lo, double hi, double gscale,
+                                                const std::optional<at::Tensor>& noise, const std::optional<at::Tensor>& noise_mag, double sigma,
+                                                const std::optional<at::Tensor>& thr) {
   dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
   TORCH_CHECK(wav.is_cuda() && wav.scalar_type() == at::kFloat && wav.dim() == 2 && wav.stride(1) == 1 && wav.size(1) >= L, "wav must be (B, >= L) fp32 on the GPU");
   DMX_DEVICE_OF(wav);
@@ -320,10 +300,10 @@ std::tuple<at::Tensor, at::Tensor> mel_guidance_shaped(int64_t audio, const at::
   at::Tensor loss = at::empty({B}, wav.options()), dwav = at::empty({B, Lfull}, wav.options());
   ok(dmx_audio_guidance_fwd_shaped(a, wav.data_ptr<float>(), wav.stride(0), fp(mask), ref.data_ptr<float>(), rs, nullptr, state.data_ptr(), B, (int)L,
                                    power2, to_db, (float)lo, (float)hi, fp(noise), ns, fp(noise_mag), (float)sigma, fp(thr), cur_stream()),
-     "mel_guidance_shaped (forward)");
+     "mel_guidance (forward)");
   ok(dmx_audio_guidance_bwd_shaped(a, wav.data_ptr<float>(), wav.stride(0), fp(mask), ref.data_ptr<float>(), rs, (float)gscale, loss.data_ptr<float>(),
                                    dwav.data_ptr<float>(), Lfull, (int)Lfull, state.data_ptr(), B, (int)L, power2, to_db, (float)lo, (float)hi, fp(noise), ns,
-                                   fp(noise_mag), (float)sigma, fp(thr), cur_stream()), "mel_guidance_shaped (backward)");
+                                   fp(noise_mag), (float)sigma, fp(thr), cur_stream()), "mel_guidance (backward)");
   return {loss, dwav};
 }
 // hard clipping on materialised waveforms (include/diffmusic_hip.h dmx_clip_fwd / dmx_clip_bwd / dmx_declip_project)
@@ -399,7 +379,8 @@ at::Tensor drc_bwd(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& 
   return d;
 }
 // time-frequency gain (include/diffmusic_hip.h dmx_audio_tf_gain): x (B, >= L), gain_t (frames, 513) shared or (B, frames, 513) -> (B, Lfull)
-at::Tensor tf_gain(int64_t audio, const at::Tensor& x, const at::Tensor& gain_t, int64_t L, int64_t Lfull) {
+// out: caller-owned (B, >= Lfull) fp32 with any row stride; only out[:, :Lfull] is written
+at::Tensor tf_gain(int64_t audio, const at::Tensor& x, const at::Tensor& gain_t, int64_t L, int64_t Lfull, const std::optional<at::Tensor>& out) {
   rows_ok(x, L, "x");
   TORCH_CHECK(Lfull >= L, "Lfull must be >= L");
   DMX_DEVICE_OF(x);
@@ -408,10 +389,10 @@ at::Tensor tf_gain(int64_t audio, const at::Tensor& x, const at::Tensor& gain_t,
   TORCH_CHECK(gain_t.device() == x.device() && ((gain_t.dim() == 2 && gain_t.size(0) == T && gain_t.size(1) == 513) ||
               (gain_t.dim() == 3 && gain_t.size(0) == B && gain_t.size(1) == T && gain_t.size(2) == 513)),
               "gain_t must be (", T, ", 513) or (", B, ", ", T, ", 513) on x's device");
-  at::Tensor out = at::empty({B, Lfull}, x.options());
+  at::Tensor y = rows_out(out, x, Lfull, Lfull, false, "out");
   ok(dmx_audio_tf_gain((dmx_audio*)audio, x.data_ptr<float>(), x.stride(0), gain_t.data_ptr<float>(), gain_t.dim() == 3 ? T * 513 : 0,
-                       out.data_ptr<float>(), Lfull, (int)B, (int)L, (int)Lfull, cur_stream()), "tf_gain");
-  return out;
+                       y.data_ptr<float>(), y.stride(0), (int)B, (int)L, (int)Lfull, cur_stream()), "tf_gain");
+  return y;
 }
 // blind equalisation (include/diffmusic_hip.h dmx_audio_tf_curve / dmx_audio_tf_wgrad / dmx_audio_eq_update): one gain curve per clip
 at::Tensor tf_curve(int64_t audio, const at::Tensor& x, const at::Tensor& curve, int64_t L, int64_t Lfull) {
@@ -535,13 +516,14 @@ at::Tensor stft_mag_fwd(int64_t audio, const at::Tensor& wav, const at::Tensor& 
   ok(dmx_audio_stft_mag(a, wav.data_ptr<float>(), wav.stride(0), mag.data_ptr<float>(), state.data_ptr(), (int)wav.size(0), (int)L, cur_stream()), "stft_mag_fwd");
   return mag;
 }
-at::Tensor stft_mag_bwd(int64_t audio, const at::Tensor& dmag, const at::Tensor& state, int64_t L, int64_t Lfull) {
+// dwav: caller-owned (B, >= L) result with any row stride, overwritten up to L; without it the op returns (B, Lfull) with zeros past L
+at::Tensor stft_mag_bwd(int64_t audio, const at::Tensor& dmag, const at::Tensor& state, int64_t L, int64_t Lfull, const std::optional<at::Tensor>& dwav) {
   dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
   f32_cuda(dmag, "dmag");
   DMX_DEVICE_OF(dmag);
-  at::Tensor dwav = at::zeros({dmag.size(0), Lfull}, dmag.options());
-  ok(dmx_audio_stft_mag_bwd(a, dmag.data_ptr<float>(), dwav.data_ptr<float>(), Lfull, state.data_ptr(), (int)dmag.size(0), (int)L, 0, cur_stream()), "stft_mag_bwd");
-  return dwav;
+  at::Tensor d = rows_out(dwav, dmag, L, Lfull, true, "dwav");
+  ok(dmx_audio_stft_mag_bwd(a, dmag.data_ptr<float>(), d.data_ptr<float>(), d.stride(0), state.data_ptr(), (int)dmag.size(0), (int)L, 0, cur_stream()), "stft_mag_bwd");
+  return d;
 }
 at::Tensor melscale_fwd(int64_t audio, const at::Tensor& mag, double lo, double hi) {
   dmx_audio* a = reinterpret_cast<dmx_audio*>(audio);
@@ -553,27 +535,25 @@ at::Tensor melscale_fwd(int64_t audio, const at::Tensor& mag, double lo, double 
 }
 
 // ---- networks (handles from dmx_*_create; workspaces are caller-owned byte tensors sized by *_workspace_bytes)
-at::Tensor unet_fwd(int64_t model, const at::Tensor& x, const at::Tensor& t, const std::optional<at::Tensor>& class_labels, at::Tensor ws) {
+// c0, c1, bias1 (all three or none): the AudioLDM2UNet2DConditionModel call (plpeline_audioldm2.py:1147-1154) with GPT-2 states c0 (B, n0, d0),
+// T5 states c1 (B, n1, d1) + additive key bias.  out_channels: of the U-Net when they differ from x's; eps is (B, out_channels or C, h, w)
+at::Tensor unet_fwd(int64_t model, const at::Tensor& x, const at::Tensor& t, const std::optional<at::Tensor>& class_labels, at::Tensor ws,
+                    const std::optional<at::Tensor>& c0, const std::optional<at::Tensor>& c1, const std::optional<at::Tensor>& bias1,
+                    std::optional<int64_t> out_channels) {
   f32_cuda(x, "x"); f32_cuda(t, "t");
-  DMX_DEVICE_OF(x);
+  TORCH_CHECK(x.dim() == 4, "x must be (B, C, h, w)");
   if (class_labels) f32_cuda(*class_labels, "class_labels");
-  at::Tensor eps = at::empty_like(x);
-  ok(dmx_unet_fwd(reinterpret_cast<dmx_model*>(model), x.data_ptr<float>(), t.data_ptr<float>(), fp(class_labels), eps.data_ptr<float>(),
-                  (int)x.size(0), (int)x.size(2), (int)x.size(3), ws.data_ptr(), ws.nbytes(), cur_stream()), "unet_fwd");
-  return eps;
-}
-// AudioLDM2UNet2DConditionModel call (plpeline_audioldm2.py:1147-1154): GPT-2 states c0 (B, n0, d0), T5 states c1 (B, n1, d1) + additive key bias
-at::Tensor unet_fwd_ctx(int64_t model, const at::Tensor& x, const at::Tensor& t, const std::optional<at::Tensor>& class_labels,
-                        const at::Tensor& c0, const at::Tensor& c1, const at::Tensor& bias1, at::Tensor ws) {
-  f32_cuda(x, "x"); f32_cuda(t, "t"); f32_cuda(c0, "encoder_hidden_states"); f32_cuda(c1, "encoder_hidden_states_1"); f32_cuda(bias1, "bias1");
-  if (class_labels) f32_cuda(*class_labels, "class_labels");
-  TORCH_CHECK(c0.dim() == 3 && c1.dim() == 3 && c0.size(0) == x.size(0) && c1.size(0) == x.size(0) && bias1.numel() == c1.size(0) * c1.size(1),
-              "context tensors must be (B, tokens, dim) with one additive bias per T5 token");
+  TORCH_CHECK(c0.has_value() == c1.has_value() && c1.has_value() == bias1.has_value(), "unet_fwd: c0, c1 and bias1 go together, all three or none");
+  if (c0) {
+    f32_cuda(*c0, "encoder_hidden_states"); f32_cuda(*c1, "encoder_hidden_states_1"); f32_cuda(*bias1, "bias1");
+    TORCH_CHECK(c0->dim() == 3 && c1->dim() == 3 && c0->size(0) == x.size(0) && c1->size(0) == x.size(0) && bias1->numel() == c1->size(0) * c1->size(1),
+                "context tensors must be (B, tokens, dim) with one additive bias per T5 token");
+  }
   DMX_DEVICE_OF(x);
-  at::Tensor eps = at::empty_like(x);
-  ok(dmx_unet_fwd_ctx(reinterpret_cast<dmx_model*>(model), x.data_ptr<float>(), t.data_ptr<float>(), fp(class_labels), c0.data_ptr<float>(),
-                      (int)c0.size(1), c1.data_ptr<float>(), (int)c1.size(1), bias1.data_ptr<float>(), eps.data_ptr<float>(), (int)x.size(0),
-                      (int)x.size(2), (int)x.size(3), ws.data_ptr(), ws.nbytes(), cur_stream()), "unet_fwd_ctx");
+  at::Tensor eps = at::empty({x.size(0), out_channels.value_or(x.size(1)), x.size(2), x.size(3)}, x.options());
+  ok(dmx_unet_fwd_ctx(reinterpret_cast<dmx_model*>(model), x.data_ptr<float>(), t.data_ptr<float>(), fp(class_labels), fp(c0), c0 ? (int)c0->size(1) : 0,
+                      fp(c1), c1 ? (int)c1->size(1) : 0, fp(bias1), eps.data_ptr<float>(), (int)x.size(0), (int)x.size(2), (int)x.size(3), ws.data_ptr(),
+                      ws.nbytes(), cur_stream()), "unet_fwd");
   return eps;
 }
 // returns (mel 16-bit, mel fp32 or None): `vae.decode(z).sample` (scheduling_dps.py:195-197)
@@ -633,23 +613,15 @@ at::Tensor vae_dec_bwd(int64_t model, const at::Tensor& dmel, double z_scale, in
   ok(dmx_vae_decode_bwd(reinterpret_cast<dmx_model*>(model), (const uint16_t*)dmel.data_ptr(), (float)z_scale, dz.data_ptr<float>(), cur_stream()), "vae_dec_bwd");
   return dz;
 }
-at::Tensor hifigan_fwd(int64_t model, const at::Tensor& mel, at::Tensor ws) {
-  act_cuda(mel, "mel");
-  DMX_DEVICE_OF(mel);
-  dmx_model* m = reinterpret_cast<dmx_model*>(model);
-  const int B = (int)mel.size(0), T = (int)mel.size(1);
-  at::Tensor wav = at::empty({B, dmx_hifigan_out_len(m, T)}, mel.options().dtype(at::kFloat));
-  ok(dmx_hifigan_fwd(m, (const uint16_t*)mel.data_ptr(), wav.data_ptr<float>(), B, T, ws.data_ptr(), ws.nbytes(), cur_stream()), "hifigan_fwd");
-  return wav;
-}
-at::Tensor hifigan_fwd_dead(int64_t model, const at::Tensor& mel, int64_t s0, int64_t s1, at::Tensor ws) {
+// [s0, s1): samples of every clip that the caller's loss never looks at: zeros there, the same bits elsewhere (an empty span: the plain forward)
+at::Tensor hifigan_fwd(int64_t model, const at::Tensor& mel, at::Tensor ws, int64_t s0, int64_t s1) {
   act_cuda(mel, "mel");
   DMX_DEVICE_OF(mel);
   dmx_model* m = reinterpret_cast<dmx_model*>(model);
   const int B = (int)mel.size(0), T = (int)mel.size(1);
   at::Tensor wav = at::empty({B, dmx_hifigan_out_len(m, T)}, mel.options().dtype(at::kFloat));
   ok(dmx_hifigan_fwd_dead(m, (const uint16_t*)mel.data_ptr(), wav.data_ptr<float>(), B, T, (int)s0, (int)s1, ws.data_ptr(), ws.nbytes(), cur_stream()),
-     "hifigan_fwd_dead");
+     "hifigan_fwd");
   return wav;
 }
 std::vector<int64_t> hifigan_dead_plan(int64_t model, int64_t stages) {
@@ -756,15 +728,18 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
   // (written by *_fwd / mel_guidance, read by the matching *_bwd) and the network workspaces `ws` (written by *_fwd; the model handle's
-  // tape points into it and *_bwd reads it).  Handles travel as ints: effects behind a handle are invisible to the schema, so under
+  // tape points into it and *_bwd reads it), and the optional caller-owned results (`out`, `dwav`, `grad_out`), which an op that is given
+  // one writes and returns.  One op per operation: what an operation can do beyond its plain form is a defaulted argument, keyword-only
+  // where the ctypes function of the same name has it keyword-only (tests/test_abi.py holds the two signatures equal).  The C ABI keeps
+  // its additive ladder (_ex / _shaped / _ctx / _dead) for C callers; an op calls the longest rung.  Handles travel as ints: effects behind a handle are invisible to the schema, so under
   // torch.compile / functionalization a forward and its backward must still be kept in program order by the caller (eager use today).
-  m.def("sched_pred_x0(Tensor x, Tensor eps, float alpha_t) -> Tensor", &sched_pred_x0);
+  m.def("sched_pred_x0(Tensor x, Tensor eps, float alpha_t, *, int ptype=0, float clip_r=0.0) -> Tensor", &sched_pred_x0);
   m.def("cfg_combine(Tensor eps2, float scale) -> Tensor", &cfg_combine);
   m.def("sched_update(int mode, Tensor x, Tensor eps, Tensor x0, Tensor? g0, Tensor? inv_scale, Tensor? noise, float alpha_t, float alpha_prev, "
-        "float sigma, float rate, float eps_small, bool global_norm) -> (Tensor, Tensor?)", &sched_update);
+        "float sigma, float rate, float eps_small, bool global_norm, *, int ptype=0, float clip_r=0.0, Tensor(a!)? grad_out=None) -> (Tensor, Tensor?)", &sched_update);
   m.def("randn_philox(int[] shape, int[] seeds, int offset, Device device) -> Tensor", &randn_philox);
   m.def("mask_mul(Tensor x, Tensor? mask, int L, int Ly) -> Tensor", &mask_mul);
-  m.def("l2norm(Tensor ref, Tensor pred, float gscale) -> (Tensor, Tensor)", &l2norm);
+  m.def("l2norm(Tensor ref, Tensor pred, float gscale, *, bool want_grad=True) -> (Tensor, Tensor?)", &l2norm);
   m.def("resample_fwd(Tensor x, Tensor h, int Lin, int Lout, int orig, int new_, int off) -> Tensor", &resample_fwd);
   m.def("resample_bwd(Tensor dy, Tensor h, Tensor? h_rev, int Lin, int Lfull, int orig, int new_, int off) -> Tensor", &resample_bwd);
   m.def("fir_clip_fwd(Tensor x, Tensor h, int Lin) -> Tensor", &fir_clip_fwd);
@@ -772,14 +747,10 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("fir_wgrad(Tensor dy, Tensor x, int L, int taps) -> Tensor", &fir_wgrad);
   m.def("ir_update(Tensor partials, Tensor(a!) h, Tensor(b!) h_rev, Tensor(c!) m, Tensor(d!) v, int k, float lr, float beta1, float beta2, "
         "float eps) -> ()", &ir_update);
-  m.def("logmel_fwd(int audio, Tensor wav, Tensor(a!) state, int L, bool power2, bool to_db, float lo, float hi) -> Tensor", &logmel_fwd);
-  m.def("logmel_bwd(int audio, Tensor dmel, Tensor state, int L, bool power2, bool to_db, float lo, float hi) -> Tensor", &logmel_bwd);
-  m.def("mel_guidance(int audio, Tensor wav, Tensor? mask, Tensor ref, Tensor(a!) state, int L, int Lfull, bool power2, bool to_db, float lo, float hi, "
-        "float gscale) -> (Tensor, Tensor)", &mel_guidance);
-  m.def("mel_guidance_noisy(int audio, Tensor wav, Tensor? mask, Tensor ref, Tensor(a!) state, int L, int Lfull, bool power2, bool to_db, float lo, "
-        "float hi, float gscale, Tensor? noise, Tensor? noise_mag, float sigma) -> (Tensor, Tensor)", &mel_guidance_noisy);
-  m.def("mel_guidance_shaped(int audio, Tensor wav, Tensor? mask, Tensor ref, Tensor(a!) state, int L, int Lfull, bool power2, bool to_db, float lo, "
-        "float hi, float gscale, Tensor? noise, Tensor? noise_mag, float sigma, Tensor? thr) -> (Tensor, Tensor)", &mel_guidance_shaped);
+  m.def("logmel_fwd(int audio, Tensor wav, Tensor(a!) state, int L, bool power2, bool to_db, float lo, float hi, *, Tensor(b!)? out=None) -> Tensor", &logmel_fwd);
+  m.def("logmel_bwd(int audio, Tensor dmel, Tensor state, int L, bool power2, bool to_db, float lo, float hi, *, Tensor(a!)? dwav=None) -> Tensor", &logmel_bwd);
+  m.def("mel_guidance(int audio, Tensor wav, Tensor? mask, Tensor ref, Tensor(a!) state, int L, int Lfull, bool power2, bool to_db, float lo, "
+        "float hi, float gscale, Tensor? noise=None, Tensor? noise_mag=None, float sigma=0.0, Tensor? thr=None) -> (Tensor, Tensor)", &mel_guidance);
   m.def("clip_fwd(Tensor x, Tensor thr, int L) -> Tensor", &clip_fwd);
   m.def("clip_bwd(Tensor dy, Tensor wav, Tensor thr, int Lfull) -> Tensor", &clip_bwd);
   m.def("declip_project(Tensor wav, Tensor measurement, Tensor thr, int L) -> Tensor", &declip_project);
@@ -788,7 +759,7 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("drc_bwd(Tensor dy, Tensor x, Tensor state, Tensor tape, int Lfull, float threshold_db, float slope, float knee_db, float a_att, float a_rel, "
         "float makeup_db) -> Tensor", &drc_bwd);
   m.def("noise_add(Tensor y, Tensor noise, float sigma) -> Tensor", &noise_add);
-  m.def("tf_gain(int audio, Tensor x, Tensor gain_t, int L, int Lfull) -> Tensor", &tf_gain);
+  m.def("tf_gain(int audio, Tensor x, Tensor gain_t, int L, int Lfull, *, Tensor(a!)? out=None) -> Tensor", &tf_gain);
   m.def("tf_curve(int audio, Tensor x, Tensor curve, int L, int Lfull) -> Tensor", &tf_curve);
   m.def("tf_wgrad(int audio, Tensor dy, Tensor x, int L) -> Tensor", &tf_wgrad);
   m.def("eq_update(Tensor partials, Tensor(a!) g, Tensor(b!) m, Tensor(c!) v, int k, float lr, float beta1, float beta2, float eps, bool peak) "
@@ -799,19 +770,18 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("stem_mix_bwd(Tensor dmix, float[]? gains, int K, int Lfull) -> Tensor", &stem_mix_bwd);
   m.def("stem_project(Tensor x, Tensor y, float[]? gains, int L) -> Tensor", &stem_project);
   m.def("stft_mag_fwd(int audio, Tensor wav, Tensor(a!) state, int L) -> Tensor", &stft_mag_fwd);
-  m.def("stft_mag_bwd(int audio, Tensor dmag, Tensor state, int L, int Lfull) -> Tensor", &stft_mag_bwd);
+  m.def("stft_mag_bwd(int audio, Tensor dmag, Tensor state, int L, int Lfull, *, Tensor(a!)? dwav=None) -> Tensor", &stft_mag_bwd);
   m.def("melscale_fwd(int audio, Tensor mag, float lo, float hi) -> Tensor", &melscale_fwd);
-  m.def("unet_fwd(int model, Tensor x, Tensor t, Tensor? class_labels, Tensor(a!) ws) -> Tensor", &unet_fwd);
-  m.def("unet_fwd_ctx(int model, Tensor x, Tensor t, Tensor? class_labels, Tensor c0, Tensor c1, Tensor bias1, Tensor(a!) ws) -> Tensor", &unet_fwd_ctx);
+  m.def("unet_fwd(int model, Tensor x, Tensor t, Tensor? class_labels, Tensor(a!) ws, Tensor? c0=None, Tensor? c1=None, Tensor? bias1=None, *, "
+        "int? out_channels=None) -> Tensor", &unet_fwd);
   m.def("vae_dec_fwd(int model, Tensor z, float z_scale, bool keep_state, bool want_f32, int scale_factor, Tensor(a!) ws) -> (Tensor, Tensor?)", &vae_dec_fwd);
   m.def("vae_dec_bwd(int model, Tensor dmel, float z_scale, int latent_channels, int scale_factor) -> Tensor", &vae_dec_bwd);
   m.def("vae_enc_fwd(int model, Tensor mel, float log_floor, int latent_channels, int scale_factor, Tensor(a!) ws) -> Tensor", &vae_enc_fwd);
   m.def("latent_init(Tensor moments, int h, int w, Tensor? eps, Tensor? noise, float sqrt_abar, float scaling_factor, float sqrt_1m_abar, "
         "bool want_x) -> (Tensor, Tensor, Tensor?)", &latent_init);
   m.def("grad_normalize_(Tensor(a!) dwav, float target) -> Tensor", &grad_normalize_);
-  m.def("hifigan_fwd(int model, Tensor mel, Tensor(a!) ws) -> Tensor", &hifigan_fwd);
+  m.def("hifigan_fwd(int model, Tensor mel, Tensor(a!) ws, int s0=0, int s1=0) -> Tensor", &hifigan_fwd);
   m.def("hifigan_bwd(int model, Tensor dwav, int frames, int model_in_dim) -> Tensor", &hifigan_bwd);
-  m.def("hifigan_fwd_dead(int model, Tensor mel, int s0, int s1, Tensor(a!) ws) -> Tensor", &hifigan_fwd_dead);
   m.def("hifigan_dead_plan(int model, int stages) -> int[]", &hifigan_dead_plan);
   m.def("htsat_fwd(int model, Tensor mel, bool keep_state, Tensor(a!) ws) -> Tensor", &htsat_fwd);
   m.def("htsat_bwd(int model, Tensor dfeat, Tensor? scale, int frames, int bins) -> Tensor", &htsat_bwd);

@@ -142,9 +142,9 @@ class HifiGanEngine(_Engine):
         lib = L.lib()
         ws = self._workspace(("h", B, T), lib.dmx_hifigan_workspace_bytes(self._h, B, T))
         self._shape = (B, T)
-        if dead is not None and self.dead_span_enabled and int(dead[1]) > int(dead[0]):
-            return ops.hip.hifigan_fwd_dead(self._h.value, mel, int(dead[0]), int(dead[1]), ws)
-        return ops.hip.hifigan_fwd(self._h.value, mel, ws)
+        live = dead is not None and self.dead_span_enabled and int(dead[1]) > int(dead[0])
+        s0, s1 = (int(dead[0]), int(dead[1])) if live else (0, 0)                    # an empty span: the plain forward
+        return ops.hip.hifigan_fwd(self._h.value, mel, ws, s0, s1)
 
     def dead_plan(self):
         """What the last forward skipped, per upsampling stage: dicts of pair-kernel slabs per clip `skipped` / `total` (forward and
@@ -292,7 +292,7 @@ class UNetEngine(_Engine):
 
     def forward(self, x, t, class_labels=None, encoder_hidden_states=None, encoder_hidden_states_1=None,
                 encoder_attention_mask_1=None):
-        """x (B, C, h, w) fp32, t (B,) fp32, class_labels (B, class_embed_dim) fp32 -> eps fp32 like x.
+        """x (B, C, h, w) fp32, t (B,) fp32, class_labels (B, class_embed_dim) fp32 -> eps (B, out_channels, h, w) fp32.
         AudioLDM2: encoder_hidden_states (B, 8, 768), encoder_hidden_states_1 (B, L, 1024) + mask (B, L)."""
         assert x.dtype == torch.float32 and x.is_cuda and x.is_contiguous()
         B, _, h, w = x.shape
@@ -302,12 +302,9 @@ class UNetEngine(_Engine):
             class_labels = class_labels.to(device=dev, dtype=torch.float32).contiguous()
         lib = L.lib()
         out_ch = self.cfg["out_channels"]
-        eps_like_x = out_ch == self.cfg["in_channels"]       # what the op schema returns; any other U-Net has the ctypes spelling only
         if self._n_ctx == 0:
             ws = self._workspace(("u", B, h, w), lib.dmx_unet_workspace_bytes(self._h, B, h, w))
-            if eps_like_x:
-                return ops.hip.unet_fwd(self._h.value, x, t, class_labels, ws)
-            return ops.ctypes_hip.unet_fwd(self._h.value, x, t, class_labels, ws, out_channels=out_ch)
+            return ops.hip.unet_fwd(self._h.value, x, t, class_labels, ws, out_channels=out_ch)
         c0 = encoder_hidden_states.to(device=dev, dtype=torch.float32).contiguous()
         c1 = encoder_hidden_states_1.to(device=dev, dtype=torch.float32)
         m1 = encoder_attention_mask_1
@@ -320,9 +317,7 @@ class UNetEngine(_Engine):
         bias1 = ((1.0 - m1) * -10000.0).contiguous()
         n0, n1 = c0.shape[1], c1.shape[1]
         ws = self._workspace(("u", B, h, w, n0, n1), lib.dmx_unet_workspace_bytes_ctx(self._h, B, h, w, n0, n1))
-        if eps_like_x:
-            return ops.hip.unet_fwd_ctx(self._h.value, x, t, class_labels, c0, c1, bias1, ws)
-        return ops.ctypes_hip.unet_fwd_ctx(self._h.value, x, t, class_labels, c0, c1, bias1, ws, out_channels=out_ch)
+        return ops.hip.unet_fwd(self._h.value, x, t, class_labels, ws, c0, c1, bias1, out_channels=out_ch)
 
 
 HTSAT_DEFAULT = dict(spec_size=256, num_mel_bins=64, patch_size=4, patch_embeds_hidden_size=96, window_size=8, depths=[2, 2, 6, 2],

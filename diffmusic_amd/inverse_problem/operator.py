@@ -75,17 +75,13 @@ class SpectralFrontend:
         B = wav.shape[0]
         st = self._get_state(B, length, wav.device)
         self._last = (B, length, power2, to_db, lo, hi)
-        args = (self._h.value, wav, st, int(length), bool(power2), bool(to_db), float(lo), float(hi))
-        if out is None and self.n_mels == 64:                # the op allocates its (B, frames, 64) result
-            return ops.hip.logmel_fwd(*args)
-        return ops.ctypes_hip.logmel_fwd(*args, out=out, n_mels=self.n_mels)
+        return ops.hip.logmel_fwd(self._h.value, wav, st, int(length), bool(power2), bool(to_db), float(lo), float(hi), out=out)
 
     def transform_bwd(self, dmel, dwav=None):
+        """dwav: caller-owned (B, >= length) gradient with any row stride."""
         B, length, power2, to_db, lo, hi = self._last
-        args = (self._h.value, dmel.contiguous(), self._state, int(length), bool(power2), bool(to_db), float(lo), float(hi))
-        if dwav is None:
-            return ops.hip.logmel_bwd(*args)
-        return ops.ctypes_hip.logmel_bwd(*args, dwav=dwav)   # caller-owned (B, >= length) gradient, any row stride
+        return ops.hip.logmel_bwd(self._h.value, dmel.contiguous(), self._state, int(length), bool(power2), bool(to_db), float(lo), float(hi),
+                                  dwav=dwav)
 
     def fused(self, length):
         """True when the fused STFT -> mel kernels (csrc/stft_mel.hip: n_fft = 1024) cover this handle and clip length."""
@@ -94,16 +90,15 @@ class SpectralFrontend:
     def guidance(self, wav, length, ref, mask=None, power2=True, to_db=True, lo=_NEG, hi=_POS, gscale=1.0, noise=None, noise_mag=None,
                  sigma=0.0, thr=None):
         """Fused guidance pair: loss[b] = ||ref[b] - transform(wav[b, :length] * mask)||_2 and dwav = gscale * dloss/dwav, (B, wav.shape[1])
-        with zeros past `length` -- one forward and one backward launch, no spectrum in HBM (dmx_audio_guidance_{fwd,bwd}).
+        with zeros past `length` -- one forward and one backward launch, no spectrum in HBM (op `mel_guidance`).
         noise (B, >= length) / noise_mag (B, bins, frames; power2 False): standard-normal draws entering as wav * mask + sigma * noise,
-        resp. |STFT| + sigma * noise_mag, inside both kernels (dmx_audio_guidance_{fwd,bwd}_ex).
-        thr (B) fp32: per-clip hard-clip thresholds, y = clip(wav * mask, thr) + sigma * noise inside both kernels
-        (dmx_audio_guidance_{fwd,bwd}_shaped, which the entry points above forward to with null pointers: one call serves all)."""
+        resp. |STFT| + sigma * noise_mag, inside both kernels.
+        thr (B) fp32: per-clip hard-clip thresholds, y = clip(wav * mask, thr) + sigma * noise inside both kernels."""
         assert wav.dtype == torch.float32 and wav.is_cuda and wav.stride(1) == 1 and ref.dtype == torch.float32 and ref.is_contiguous()
         B, full = wav.shape
         st = self._get_state(B, length, wav.device)
-        return ops.hip.mel_guidance_shaped(self._h.value, wav, mask, ref, st, int(length), int(full), bool(power2), bool(to_db), float(lo),
-                                           float(hi), float(gscale), noise, noise_mag, float(sigma), thr)
+        return ops.hip.mel_guidance(self._h.value, wav, mask, ref, st, int(length), int(full), bool(power2), bool(to_db), float(lo),
+                                    float(hi), float(gscale), noise, noise_mag, float(sigma), thr)
 
     def stft_mag(self, wav, length):
         B = wav.shape[0]
@@ -112,12 +107,10 @@ class SpectralFrontend:
 
     def stft_mag_bwd(self, dmag, length, dwav):
         """dmag (B, bins, frames) w.r.t. the magnitude of the last stft_mag call -> dwav (B, >=length) (overwritten)."""
-        return ops.ctypes_hip.stft_mag_bwd(self._h.value, dmag, self._state, int(length), dwav.shape[1], dwav=dwav)
+        return ops.hip.stft_mag_bwd(self._h.value, dmag, self._state, int(length), dwav.shape[1], dwav=dwav)
 
     def melscale(self, mag, lo=_NEG, hi=_POS):
-        if self.n_mels == 64:                                # the op allocates its (B, frames, 64) result
-            return ops.hip.melscale_fwd(self._h.value, mag.contiguous(), float(lo), float(hi))
-        return ops.ctypes_hip.melscale_fwd(self._h.value, mag.contiguous(), float(lo), float(hi), n_mels=self.n_mels)
+        return ops.hip.melscale_fwd(self._h.value, mag.contiguous(), float(lo), float(hi))
 
 
 class ModelMelFrontend:
@@ -145,13 +138,10 @@ class ModelMelFrontend:
 
 
 def l2_loss(ref, pred, want_grad=True, gscale=1.0):
-    """per-clip ||ref - pred||_2 over all trailing dims; ref may have batch 1 (broadcast)."""
+    """per-clip ||ref - pred||_2 over all trailing dims; ref may have batch 1 (broadcast), pred is contiguous."""
     ref = ref.contiguous()
-    assert ref[0].numel() == pred[0].numel(), (ref.shape, pred.shape)
-    if pred.is_contiguous():                                 # the op takes contiguous tensors and always returns the gradient
-        loss, dpred = ops.hip.l2norm(ref, pred, float(gscale))
-        return loss, (dpred if want_grad else None)
-    return ops.ctypes_hip.l2norm(ref, pred, float(gscale), want_grad=want_grad)
+    assert ref[0].numel() == pred[0].numel() and pred.is_contiguous(), (ref.shape, pred.shape, pred.stride())
+    return ops.hip.l2norm(ref, pred, float(gscale), want_grad=want_grad)
 
 
 def _as_f32_cuda(x):
@@ -338,8 +328,8 @@ def _masked(x, length, mask):
     """-> (x[:, :length] * mask, adjoint) for a (1, length) mask on x's device, or None for the plain crop: a per-sample mask is its own
     transpose, and the transpose of the crop is the zero-pad."""
     def adjoint(dy, full):
-        return ops.ctypes_hip.mask_mul(dy, mask, dy.shape[1], full)
-    return ops.ctypes_hip.mask_mul(x, mask, length, length), adjoint
+        return ops.hip.mask_mul(dy, mask, dy.shape[1], int(full))
+    return ops.hip.mask_mul(x, mask, int(length), int(length)), adjoint
 
 
 class IdentityOperator(_MelOperator):                     # operator.py:17-45
@@ -1055,7 +1045,7 @@ class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 
         B = g.shape[0]
         loss, dg = l2_loss(ref.reshape(ref.shape[0], -1), g.reshape(B, -1))
         df = gram_backward(f, dg.reshape(g.shape))
-        inv_scale = ops.ctypes_hip.grad_normalize_(df.reshape(B, -1), 64.0)          # in place on df
+        inv_scale = ops.hip.grad_normalize_(df.reshape(B, -1), 64.0)          # in place on df
         return loss, self.engine.backward(df, scale=inv_scale)[:, None]
 
     @torch.no_grad()

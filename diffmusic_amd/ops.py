@@ -5,14 +5,17 @@ compiled from csrc_torch/torch_ops.cpp into lib/libdiffmusic_torch_ops.so and lo
     prev, x0 = ops.hip.sched_update(1, x, eps, x0, g0, inv_scale, None, a_t, a_p, sigma, rate, 1e-8, False)
 
 The facades (`Scheduler.step`, `Pipeline.__call__`, the operators, the engines) call `ops.hip.<name>` and nothing else: it resolves,
-per call, to `torch.ops.diffmusic_hip.<name>` (default) or to the ctypes function of the same name and positional signature
-(`_ctypes_ops.py`, also exposed as `ops.ctypes_hip`); both end in the same `extern "C"` launchers on torch's current HIP stream.
-DMX_TORCH_OPS=0 selects the ctypes binding; so does DMX_LIB_PATH (a dev build of libdiffmusic_hip.so: the op library links the
-in-tree one) and an op library that cannot be loaded (missing, or built against another torch): one warning, then ctypes -- the
-same HIP kernels either way.  This module is the only place that knows which binding carries a launch.  A facade names
-`ops.ctypes_hip.<name>` itself only where its inputs need what the op schema cannot express (the keyword-only parameters of
-`_ctypes_ops.py`: caller-owned or strided outputs, prediction type / clip range, 64-bit Philox seeds).  Neither binding has a
-CPU fallback: without libdiffmusic_hip.so everything raises."""
+per call, to `torch.ops.diffmusic_hip.<name>` (default) or to the ctypes function of the same name and signature
+(`_ctypes_ops.py`, also exposed as `ops.ctypes_hip` for tests); both end in the same `extern "C"` launchers on torch's current HIP
+stream.  DMX_TORCH_OPS=0 selects the ctypes binding; so does DMX_LIB_PATH (a dev build of libdiffmusic_hip.so: the op library links
+the in-tree one) and an op library that cannot be loaded (missing, or built against another torch): one warning, then ctypes -- the
+same HIP kernels either way.  This module is the only place that knows which binding carries a launch: no facade names a binding.
+
+There is one op per operation.  What an operation can do beyond its plain form -- a caller-owned or strided output (`out`, `dwav`,
+`grad_out`), prediction type / clip range, the guidance pair's noise and clip thresholds, a vocoder dead span, the U-Net's context
+tensors and output channels -- is a defaulted argument of that op, identical in both bindings (tests/test_abi.py compares names,
+order, keyword-only split and defaults).  The C ABI keeps its additive ladder (_ex / _shaped / _ctx / _dead) for C callers; the op
+layer calls the longest rung.  Neither binding has a CPU fallback: without libdiffmusic_hip.so everything raises."""
 import inspect
 import os
 import warnings

@@ -213,13 +213,9 @@ class GuidedDDIMScheduler:
         t, a_t, a_p, sigma = self._scalars(timestep, eta)
         x = sample.detach().to(torch.float32).contiguous()
         e = model_output.detach().to(torch.float32).contiguous()
-        # epsilon prediction, no clipping: the reference's configs, and what the op schemas express.  The DDIM parent's other branches
-        # (sample / v_prediction, clip_sample) are C-ABI entry points that take the type and the clip range: the ctypes spelling only.
-        plain = self._ptype == 0 and self._clip_r == 0.0
-        if plain:
-            x0 = ops.hip.sched_pred_x0(x, e, a_t)
-        else:
-            x0 = ops.ctypes_hip.sched_pred_x0(x, e, a_t, ptype=self._ptype, clip_r=self._clip_r)
+        # epsilon prediction without clipping (ptype 0, clip_r 0: the reference's configs) or the DDIM parent's other branches (sample /
+        # v_prediction, clip_sample)
+        x0 = ops.hip.sched_pred_x0(x, e, a_t, ptype=self._ptype, clip_r=self._clip_r)
         mode = _MODE[self.mode]
         noise = None
         if self.mode in ("dps", "mpgd") and eta > 0:
@@ -245,10 +241,8 @@ class GuidedDDIMScheduler:
         grad_out = torch.empty_like(x) if self.debug_keep_grad and self.mode != "ddim" else None
         upd = (mode, x, e, x0, g0, inv_scale, noise, a_t, a_p, sigma, float(rate), float(eps), not self.per_clip_norm)
         with stage("sched_update"):
-            if plain and grad_out is None:
-                prev, x0_out = ops.hip.sched_update(*upd)          # x0_out: MPGD's guided x0, None for every other mode
-            else:
-                prev, x0_out = ops.ctypes_hip.sched_update(*upd, ptype=self._ptype, clip_r=self._clip_r, grad_out=grad_out)
+            # x0_out: MPGD's guided x0, None for every other mode
+            prev, x0_out = ops.hip.sched_update(*upd, ptype=self._ptype, clip_r=self._clip_r, grad_out=grad_out)
         self.last_grad = grad_out
         if loss.numel() == 1 and self.mode != "ddim":
             loss = loss.reshape(())

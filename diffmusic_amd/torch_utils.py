@@ -31,5 +31,7 @@ def randn_philox(shape, seeds, offset=0, device="cuda"):
     from . import ops
     if len(seeds) != int(shape[0]):
         raise ValueError(f"need one seed per clip: got {len(seeds)} for batch {int(shape[0])}")
-    # the op's int[] seeds are signed 64-bit and its batch is capped at 64; the ctypes spelling takes any seed modulo 2^64
-    return ops.ctypes_hip.randn_philox(shape, seeds, offset, device)
+    def fold(v):                                             # modulo 2^64 into the signed 64-bit range of the op's ints: the same bits
+        v = int(v) & 0xFFFFFFFFFFFFFFFF
+        return v - 2 ** 64 if v >= 2 ** 63 else v
+    return ops.hip.randn_philox([int(d) for d in shape], [fold(s) for s in seeds], fold(offset), torch.device(device))

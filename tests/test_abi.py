@@ -79,8 +79,8 @@ def test_torch_op_library_loads_and_registers_every_stage_op(monkeypatch, tmp_pa
 
 def test_ctypes_ops_have_the_positional_signatures_of_the_registered_ops():
     """The two bindings are one surface: every op registered in csrc_torch/torch_ops.cpp has a function of its name in
-    diffmusic_amd/_ctypes_ops.py whose positional parameters are the schema's arguments, in order and by name; whatever else the
-    ctypes function takes is keyword-only and has a default, so a call written for the op is a call of the function."""
+    diffmusic_amd/_ctypes_ops.py with the schema's arguments: the same names in the same order, the same positional / keyword-only
+    split and the same default values, so a call written for one is a call of the other."""
     import inspect
     from diffmusic_amd.build import build_torch_ops
     from diffmusic_amd import ops
@@ -91,10 +91,29 @@ def test_ctypes_ops_have_the_positional_signatures_of_the_registered_ops():
     assert len(registered) >= 26 and len(set(registered)) == len(registered)
     assert sorted(registered) == sorted(ops.OP_NAMES)
     P = inspect.Parameter
+    defaulted = 0
     for name in ops.OP_NAMES:
-        want = [a.name for a in getattr(h, name).default._schema.arguments]
+        want = [(a.name, a.kwarg_only, a.has_default_value(), a.default_value if a.has_default_value() else None)
+                for a in getattr(h, name).default._schema.arguments]
         params = list(inspect.signature(getattr(ops.ctypes_hip, name)).parameters.values())
-        assert [p.name for p in params if p.kind == P.POSITIONAL_OR_KEYWORD] == want, name
-        assert all(p.default is P.empty for p in params if p.kind == P.POSITIONAL_OR_KEYWORD), name
-        extra = [p for p in params if p.kind != P.POSITIONAL_OR_KEYWORD]
-        assert all(p.kind == P.KEYWORD_ONLY and p.default is not P.empty for p in extra), name
+        assert all(p.kind in (P.POSITIONAL_OR_KEYWORD, P.KEYWORD_ONLY) for p in params), name
+        got = [(p.name, p.kind == P.KEYWORD_ONLY, p.default is not P.empty, None if p.default is P.empty else p.default) for p in params]
+        assert got == want, (name, got, want)
+        assert all(type(g[3]) is type(w[3]) for g, w in zip(got, want)), (name, got, want)      # 0 is not 0.0 is not False
+        defaulted += sum(w[2] for w in want)
+    assert defaulted >= 20                                              # the schemas do carry defaults for this to compare
+
+
+def test_only_ops_py_names_a_binding():
+    """No module of the package other than ops.py (which picks the binding) and _ctypes_ops.py (which is one) mentions `ctypes_hip`: a
+    facade calls `ops.hip.<name>` and nothing else."""
+    pkg = os.path.join(ROOT, "diffmusic_amd")
+    seen = 0
+    for dp, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                seen += 1
+                path = os.path.join(dp, f)
+                if os.path.relpath(path, pkg) not in ("ops.py", "_ctypes_ops.py"):
+                    assert "ctypes_hip" not in open(path).read(), path
+    assert seen >= 10

@@ -122,5 +122,8 @@ def test_new_entry_points_are_additive():
     assert "#define DMX_ABI_VERSION 4 " in hdr and _lib.ABI_VERSION == 4
     for s in ("dmx_audio_guidance_fwd_shaped", "dmx_audio_guidance_bwd_shaped", "dmx_clip_fwd", "dmx_clip_bwd", "dmx_declip_project"):
         assert s in _lib._SIGS and s in _lib.ADDED_IN_V4 and f"int {s}(" in hdr and f"#pragma weak {s}" in src, s
-    for name in ("mel_guidance_shaped", "clip_fwd", "clip_bwd", "declip_project"):
+    for name in ("mel_guidance", "clip_fwd", "clip_bwd", "declip_project"):
         assert name in ops.OP_NAMES and f'm.def("{name}(' in src, name
+    from diffmusic_amd.build import build_torch_ops
+    assert os.path.exists(build_torch_ops())
+    assert [a.name for a in ops.load().mel_guidance.default._schema.arguments][-4:] == ["noise", "noise_mag", "sigma", "thr"]

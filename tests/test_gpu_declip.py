@@ -125,15 +125,15 @@ def test_no_threshold_and_a_huge_threshold_are_bitwise_noops(case):
     args = (fe._h.value, wav, mask, ref, st, L, full, power2, to_db, float(lo), float(hi), 1.0)
     huge = torch.full((B,), 3e38, device="cuda")
     for binding in (ops.load(), ops.ctypes_hip):
-        loss0, d0 = binding.mel_guidance(*args)
-        loss1, d1 = binding.mel_guidance_shaped(*args, None, None, 0.0, None)
+        loss0, d0 = binding.mel_guidance(*args)                                   # the defaults omitted ...
+        loss1, d1 = binding.mel_guidance(*args, None, None, 0.0, None)            # ... and passed
         assert torch.equal(loss0, loss1) and torch.equal(d0, d1), name
-        loss2, d2 = binding.mel_guidance_shaped(*args, None, None, 0.0, huge)
+        loss2, d2 = binding.mel_guidance(*args, None, None, 0.0, huge)
         assert torch.equal(loss0, loss2) and torch.equal(d0, d2), name
-        lossn, dn = binding.mel_guidance_noisy(*args, z, None, 0.05)
-        loss3, d3 = binding.mel_guidance_shaped(*args, z, None, 0.05, None)
+        lossn, dn = binding.mel_guidance(*args, z, None, 0.05)
+        loss3, d3 = binding.mel_guidance(*args, z, None, 0.05, None)
         assert torch.equal(lossn, loss3) and torch.equal(dn, d3), name
-        loss4, d4 = binding.mel_guidance_shaped(*args, z, None, 0.05, huge)
+        loss4, d4 = binding.mel_guidance(*args, z, None, 0.05, huge)
         assert torch.equal(lossn, loss4) and torch.equal(dn, d4), name
         assert not torch.equal(loss0, lossn)
     a, b = fe.guidance(wav, L, ref, mask, power2, to_db, lo, hi), fe.guidance(wav, L, ref, mask, power2, to_db, lo, hi, thr=huge)

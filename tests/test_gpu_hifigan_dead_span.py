@@ -139,9 +139,9 @@ def test_both_bindings():
     hole = HOLES[0][0]
     eng.forward(mel)                                                     # (sizes the workspace)
     ws = eng._ws["buf"]
-    wav = ops.load().hifigan_fwd_dead(eng._h.value, mel, hole[0], hole[1], ws)
+    wav = ops.load().hifigan_fwd(eng._h.value, mel, ws, hole[0], hole[1])
     plan = list(ops.load().hifigan_dead_plan(eng._h.value, 4))
-    assert torch.equal(ops.ctypes_hip.hifigan_fwd_dead(eng._h.value, mel, hole[0], hole[1], ws), wav)
+    assert torch.equal(ops.ctypes_hip.hifigan_fwd(eng._h.value, mel, ws, hole[0], hole[1]), wav)
     assert ops.ctypes_hip.hifigan_dead_plan(eng._h.value, 4) == plan and sum(plan[0::4]) > 0
 
 

@@ -530,11 +530,11 @@ def test_new_ops_equal_ctypes_path():
         fe, wav, mask, ref, kw, sigma, B = _kernel_problem(case)
         st = fe._get_state(B, L, wav.device)
         args = (fe._h.value, wav, mask, ref, st, L, full, power2, to_db, lo, hi, 0.5, kw.get("noise"), kw.get("noise_mag"), sigma)
-        a, b = h.mel_guidance_noisy(*args), ops.ctypes_hip.mel_guidance_noisy(*args)
+        a, b = h.mel_guidance(*args), ops.ctypes_hip.mel_guidance(*args)
         assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), name
         plain = h.mel_guidance(*args[:12])
         assert not torch.equal(plain[0], a[0])
-        quiet = h.mel_guidance_noisy(*args[:12], None, None, 0.0)                 # no additive input: the old op's bits
+        quiet = h.mel_guidance(*args[:12], None, None, 0.0)                       # no additive input: the bits of the defaults
         assert torch.equal(quiet[0], plain[0]) and torch.equal(quiet[1], plain[1])
     g = torch.Generator().manual_seed(2)
     for n, shift in ((4096, 0), (4099, 0), (3, 0), (1001, 1)):                    # float4 body + tail, tiny, and a 4-byte-aligned pointer

@@ -2,7 +2,7 @@
 against the float64 model of tests/spectral_cases.py, inside the element-wise bound built from the number formats alone; exact zeros
 where the contract says zero; every output buffer pre-filled with NaN and the sentinel intact wherever nothing may be written.
 
-Each case runs through the public SpectralFrontend methods; the caller-owned / strided forms go through ops.ctypes_hip or, for the
+Each case runs through the public SpectralFrontend methods, the caller-owned / strided forms (`out=`, `dwav=`) included; for the
 guidance pair with a caller-owned mel and a strided gradient, the two C entry points the public method itself calls.  The largest
 error / bound ratio per route and output kind is carried in every assertion message and printed by the last test (`-s`)."""
 import ctypes as C

@@ -11,7 +11,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("dmx_audio_guidance_fwd_ex", "dmx_audio_guidance_bwd_ex", "dmx_noise_add")
-NEW_OPS = ("mel_guidance_noisy", "noise_add")
+NEW_OPS = ("mel_guidance", "noise_add")
 
 
 def test_get_noiser_streams():
@@ -148,7 +148,7 @@ def test_new_ops_exist_in_both_bindings():
     for name in NEW_OPS:
         assert name in ops.OP_NAMES and callable(getattr(ops.ctypes_hip, name))
         assert str(getattr(h, name).default._schema).startswith(f"diffmusic_hip::{name}(")
-    old = str(h.mel_guidance.default._schema)
-    assert old.endswith("float gscale) -> (Tensor, Tensor)") and "noise" not in old       # the existing op keeps its schema
+    args = [a.name for a in h.mel_guidance.default._schema.arguments]
+    assert args[-4:] == ["noise", "noise_mag", "sigma", "thr"] and args[-5] == "gscale"   # the one op carries the noise and the clip
     with pytest.raises(RuntimeError, match="GPU tensor"):
         h.noise_add(torch.zeros(4), torch.zeros(4), 0.5)                                   # no CPU fallback
