@@ -366,10 +366,9 @@ __device__ __forceinline__ void gn_parts_quads(const GnRegion& R, int g, int cpg
   q1 = min(gq1, R.qoff + R.cq) - R.qoff;
 }
 // Block-wide: (mean, rstd) of every group of image b into s_mean / s_rstd.  Thread t < (nth / G) * G owns group t % G and the slots
-// t / G, t / G + nth / G, ... of every region.  STAGED: the image's partial sums were copied to LDS first (`s_buf`, region r at float2
+// t / G, t / G + nth / G, ... of every region.  The image's partial sums were copied to LDS first (`s_buf`, region r at float2
 // offset soff[r], slot-major like the global layout) -- one coalesced round trip for the whole workgroup instead of a dependent load per
 // item (the direct form cost the fused mid-size plan 8 us per launch).  `s_red` holds nth floats.
-template <bool STAGED>
 __device__ __forceinline__ void gn_parts_combine(const GnParts& sp, int b, int C, int G, float eps, float* s_red, float* s_mean, float* s_rstd,
                                                  const float2* s_buf, const int* soff) {
   const int tid = threadIdx.x, nth = blockDim.x, nslice = nth / G, cpg = C / G;
@@ -382,35 +381,8 @@ __device__ __forceinline__ void gn_parts_combine(const GnParts& sp, int b, int C
       int q0, q1;
       gn_parts_quads(R, g, cpg, q0, q1);
       if (q1 <= q0) continue;
-      const int ns = gn_parts_nslots(R, b), slots = (R.P + R.tm - 1) / R.tm + 1;
-      const float2* src = STAGED ? s_buf + soff[r] : reinterpret_cast<const float2*>(R.part) + (long long)b * slots * R.nq;
-      const int nq = q1 - q0;
-      if (!STAGED && nq <= 2) {
-        // straight from global memory (the big tensors, whose partial sums do not fit LDS): 8 slots x <= 2 quads of loads in flight per
-        // thread, then the same additions in the same order as the plain loop below (a thread of the 64000-pixel tensors walks 31 slots:
-        // one dependent round trip each cost the one-workgroup-per-image launch 23 us)
-        for (int j0 = slice; j0 < ns; j0 += 8 * nslice) {
-          float2 v[8][2];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            const int j = j0 + u * nslice;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) v[u][q] = (j < ns && q < nq) ? src[j * R.nq + q0 + q] : make_float2(0.f, 0.f);
-          }
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            const int j = j0 + u * nslice;
-            if (j >= ns) break;
-            const int rows = gn_parts_rows(R, b, j);
-            if (rows <= 0) continue;
-            float sv = 0.f, qv = 0.f;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) if (q < nq) { sv += v[u][q].x; qv += v[u][q].y; }
-            f(sv, qv, (float)rows * 4.f * (float)nq);
-          }
-        }
-        continue;
-      }
+      const int ns = gn_parts_nslots(R, b);
+      const float2* src = s_buf + soff[r];
       for (int j = slice; j < ns; j += nslice) {
         const int rows = gn_parts_rows(R, b, j);
         if (rows <= 0) continue;
@@ -444,23 +416,23 @@ __device__ __forceinline__ void gn_parts_combine(const GnParts& sp, int b, int C
   __syncthreads();
 }
 
-// grid (nchunk, B).  y != nullptr: finalize + apply in one launch (every workgroup repeats the small combine; workgroup 0 of an image also
-// writes stats / scale / shift for callers that keep a tape).  y == nullptr: statistics only (launched with one workgroup per image).
-template <int NT>
-__global__ __launch_bounds__(NT) void gn_parts_kernel(const act_t* __restrict__ x, act_t* __restrict__ y, const GnParts sp,
+// grid (nchunk, B), 256 threads: finalize + apply in one launch for images whose partial sums are small (every workgroup repeats the
+// combine; workgroup 0 of an image also writes stats / scale / shift for callers that keep a tape).
+__global__ __launch_bounds__(256) void gn_parts_kernel(const act_t* __restrict__ x, act_t* __restrict__ y, const GnParts sp,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
                                                      float* __restrict__ stats, float* __restrict__ scale, float* __restrict__ shift,
-                                                     int P, int C, int G, int rpb, int ppb, float eps, int silu, int stage_f2) {
+                                                     int P, int C, int G, int rpb, int ppb, float eps, int silu) {
+  constexpr int NT = 256;
   __shared__ float s_red[NT];
   __shared__ float s_mean[64], s_rstd[64];
   __shared__ int s_off[8];
-  extern __shared__ __attribute__((aligned(16))) float2 s_stage[];     // stage_f2 > 0: room for the image's partial sums (float2 count)
+  extern __shared__ __attribute__((aligned(16))) float2 s_stage[];     // room for the image's partial sums
   const int b = blockIdx.y, cpg = C / G, tid = threadIdx.x;
   // what does not depend on the statistics is requested first (this thread's affine parameters and its first rows of x), so that one memory
   // round trip covers them together with the partial sums
   const int cpr = C >> 3;
   const int col = tid % cpr, row = tid / cpr, c0 = col << 3;
-  const bool active = y && row < rpb;
+  const bool active = row < rpb;
   const int p0 = blockIdx.x * ppb, p1 = min(P, p0 + ppb);
   const long long base = (long long)b * P * C + c0;
   float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0, b0 = g0, b1 = g0;
@@ -475,7 +447,7 @@ __global__ __launch_bounds__(NT) void gn_parts_kernel(const act_t* __restrict__ 
       for (int u = 0; u < 4; ++u) xv0[u] = *reinterpret_cast<const uint4*>(x + base + (long long)(p + u * rpb) * C);
     }
   }
-  if (stage_f2 > 0) {
+  {
     int off = 0;
     for (int r = 0; r < sp.n; ++r) {
       const GnRegion& R = sp.r[r];
@@ -493,9 +465,7 @@ __global__ __launch_bounds__(NT) void gn_parts_kernel(const act_t* __restrict__ 
       off += cnt;
     }
     __syncthreads();
-    gn_parts_combine<true>(sp, b, C, G, eps, s_red, s_mean, s_rstd, s_stage, s_off);
-  } else {
-    gn_parts_combine<false>(sp, b, C, G, eps, s_red, s_mean, s_rstd, nullptr, nullptr);
+    gn_parts_combine(sp, b, C, G, eps, s_red, s_mean, s_rstd, s_stage, s_off);
   }
   if (blockIdx.x == 0) {
     if (tid < G) { stats[((long long)b * G + tid) * 2] = s_mean[tid]; stats[((long long)b * G + tid) * 2 + 1] = s_rstd[tid]; }
@@ -541,6 +511,71 @@ __global__ __launch_bounds__(NT) void gn_parts_kernel(const act_t* __restrict__ 
   for (; p < p1; p += rpb) body(*reinterpret_cast<const uint4*>(x + base + (long long)p * C), base + (long long)p * C);
 }
 
+// ---- one workgroup per (group, image): the combine of the partial sums on a (G, B) grid.  The one-workgroup-per-image form left 248 of
+// the 256 CUs idle at B = 8 while one workgroup walked an image's 256 KB of slots; a group's share is 8 KB, one round trip per sweep.
+// f(v, rows) over this thread's (slot, quad) items of group g of image b, region after region: item i = slot * nq + quad of a region goes
+// to thread i % blockDim, 8 loads in flight per thread.  The item set depends on (region geometry, thread id) alone, never on b or B, and
+// the threads are summed by a fixed tree (block_sum), so an image's statistics are the same bits at any batch position and batch size.
+// (One list of items over all regions, to have the loads of the four parity regions in flight together, was slower: choosing the region
+// per item cost more than the three round trips it saved -- 9.0 against 6.2 us with one region, 18 against 12 us with four.)
+template <class F>
+__device__ __forceinline__ void gn_parts_group_items(const GnParts& sp, int b, int g, int cpg, F&& f) {
+  const int tid = threadIdx.x, nth = blockDim.x;
+  for (int r = 0; r < sp.n; ++r) {
+    const GnRegion& R = sp.r[r];
+    int q0, q1;
+    gn_parts_quads(R, g, cpg, q0, q1);
+    if (q1 <= q0) continue;                      // (a source of a concatenation that holds none of this group's channels)
+    const int ns = gn_parts_nslots(R, b), slots = (R.P + R.tm - 1) / R.tm + 1, nq = q1 - q0, items = ns * nq;
+    const float2* src = reinterpret_cast<const float2*>(R.part) + (long long)b * slots * R.nq + q0;
+    for (int i0 = tid; i0 < items; i0 += 8 * nth) {
+      float2 v[8];
+      int rows[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = i0 + u * nth, j = i / nq;
+        rows[u] = i < items ? gn_parts_rows(R, b, j) : 0;
+        v[u] = rows[u] > 0 ? src[j * R.nq + (i - j * nq)] : make_float2(0.f, 0.f);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) if (rows[u] > 0) f(v[u], rows[u]);
+    }
+  }
+}
+
+// grid (G, B), 256 threads: (mean, rstd) of group g of image b, and scale / shift of its channels.  Items = (region, slot, quad): the 4
+// channels of a quad over the rows of a slot as (n, mean, M2), Chan-combined in two sweeps like gn_parts_combine (total -> mean, then
+// M2 + n (mean_i - mean)^2; the second sweep re-reads the group's 8 KB from L2).  The count needs no sum: the slots of a region cover
+// its P rows exactly once.
+__global__ __launch_bounds__(256) void gn_parts_stats_kernel(const GnParts sp, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                             float* __restrict__ stats, float* __restrict__ scale, float* __restrict__ shift,
+                                                             int C, int G, float eps) {
+  __shared__ float sh[16];
+  const int g = blockIdx.x, b = blockIdx.y, cpg = C / G, tid = threadIdx.x;
+  long long cnt = 0;
+  for (int r = 0; r < sp.n; ++r) {
+    int q0, q1;
+    gn_parts_quads(sp.r[r], g, cpg, q0, q1);
+    if (q1 > q0) cnt += 4ll * sp.r[r].P * (q1 - q0);
+  }
+  const float nt = fmaxf((float)cnt, 1.f);
+  float a = 0.f;
+  gn_parts_group_items(sp, b, g, cpg, [&](const float2& v, int rows) { (void)rows; a += v.x; });
+  const float mean = block_sum(a, sh) / nt;
+  float m2 = 0.f;
+  gn_parts_group_items(sp, b, g, cpg, [&](const float2& v, int rows) {
+    const float nv = 4.f * (float)rows, mi = v.x / nv, d = mi - mean;
+    m2 += fmaxf(v.y - v.x * mi, 0.f) + nv * d * d;
+  });
+  const float rstd = rsqrtf(block_sum(m2, sh) / nt + eps);
+  if (tid == 0) { stats[((long long)b * G + g) * 2] = mean; stats[((long long)b * G + g) * 2 + 1] = rstd; }
+  for (int c = g * cpg + tid; c < (g + 1) * cpg; c += blockDim.x) {
+    const float s = rstd * gamma[c];
+    scale[(long long)b * C + c] = s;
+    shift[(long long)b * C + c] = beta[c] - mean * s;
+  }
+}
+
 // backward finalize: per (b,c) coefficients k0, k1 with dx = scale*dy*act'(z) + k0 + k1*x
 __global__ __launch_bounds__(1024) void gn_bwd_finalize_kernel(const float* __restrict__ partial, const float* __restrict__ stats,
                                        float* __restrict__ k0, float* __restrict__ k1,
@@ -578,59 +613,21 @@ __global__ __launch_bounds__(1024) void gn_bwd_finalize_kernel(const float* __re
 
 // backward finalize from PRODUCER-written partial sums (EPI_GNBWD, gemm_epilogue.h): per slot and 4-channel quad (sum dxh, sum dxh (x - mean))
 // with dxh = dy act'(z) gamma rstd; per group  c1 = sum dxh / n,  c2 = rstd * sum dxh (x - mean) / n,  then k0 / k1 as above.
-// One workgroup per image; thread t owns group t % G and the slots t / G, t / G + blockDim / G, ... (plain sums: no conditioning issue,
-// every term is a product of O(1) factors); batches of 8 loads in flight per thread.
-__global__ __launch_bounds__(1024) void gn_bwd_parts_finalize_kernel(const GnParts sp, const float* __restrict__ stats,
-                                                                      float* __restrict__ k0, float* __restrict__ k1, int P, int C, int G) {
-  __shared__ float s_red[1024];
-  __shared__ float s_c1[64], s_c2[64];
-  const int b = blockIdx.x, cpg = C / G, tid = threadIdx.x, nth = blockDim.x, nslice = nth / G;
-  const bool act = tid < nslice * G;
-  const int g = tid % G, slice = tid / G;
+// One workgroup per (group, image) on a (G, B) grid, 256 threads; items and summation order as gn_parts_stats_kernel (plain sums: no
+// conditioning issue, every term is a product of O(1) factors).
+__global__ __launch_bounds__(256) void gn_bwd_parts_finalize_kernel(const GnParts sp, const float* __restrict__ stats,
+                                                                     float* __restrict__ k0, float* __restrict__ k1, int P, int C, int G) {
+  __shared__ float sh[16];
+  const int g = blockIdx.x, b = blockIdx.y, cpg = C / G;
   float a1 = 0.f, a2 = 0.f;
-  if (act) {
-    for (int r = 0; r < sp.n; ++r) {
-      const GnRegion& R = sp.r[r];
-      int q0, q1;
-      gn_parts_quads(R, g, cpg, q0, q1);
-      if (q1 <= q0) continue;
-      const int ns = gn_parts_nslots(R, b), slots = (R.P + R.tm - 1) / R.tm + 1, nq = q1 - q0;
-      const float2* src = reinterpret_cast<const float2*>(R.part) + (long long)b * slots * R.nq;
-      const int items = ((ns - slice + nslice - 1) / nslice) * nq;             // (slot, quad) pairs of this thread
-      for (int i0 = 0; i0 < items; i0 += 8) {
-        float2 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int i = i0 + u, j = slice + (i / nq) * nslice, q = q0 + i % nq;
-          v[u] = (i < items && j < ns && gn_parts_rows(R, b, j) > 0) ? src[j * R.nq + q] : make_float2(0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { a1 += v[u].x; a2 += v[u].y; }
-      }
-    }
-  }
-  auto reduce = [&](float v) -> float {
-    __syncthreads();
-    if (act) s_red[slice * G + g] = v;
-    __syncthreads();
-    float t = 0.f;
-    if (tid < G) for (int k = 0; k < nslice; ++k) t += s_red[k * G + tid];
-    return t;
-  };
-  const float t1 = reduce(a1), t2 = reduce(a2);
-  if (tid < G) {
-    const float n = (float)P * cpg;
-    const float mean = stats[((long long)b * G + tid) * 2], rstd = stats[((long long)b * G + tid) * 2 + 1];
-    s_c1[tid] = t1 / n;
-    s_c2[tid] = rstd * t2 / n;                 // (the producer summed dxh (x - mean))
-    (void)mean;
-  }
-  __syncthreads();
-  for (int c = tid; c < C; c += nth) {
-    const int gg = c / cpg;
-    const float mean = stats[((long long)b * G + gg) * 2], rstd = stats[((long long)b * G + gg) * 2 + 1];
-    k0[(long long)b * C + c] = -s_c1[gg] + s_c2[gg] * rstd * mean;
-    k1[(long long)b * C + c] = -s_c2[gg] * rstd;
+  gn_parts_group_items(sp, b, g, cpg, [&](const float2& v, int rows) { (void)rows; a1 += v.x; a2 += v.y; });
+  const float t1 = block_sum(a1, sh), t2 = block_sum(a2, sh);
+  const float n = (float)P * cpg;
+  const float mean = stats[((long long)b * G + g) * 2], rstd = stats[((long long)b * G + g) * 2 + 1];
+  const float c1 = t1 / n, c2 = rstd * t2 / n;          // (the producer summed dxh (x - mean))
+  for (int c = g * cpg + threadIdx.x; c < (g + 1) * cpg; c += blockDim.x) {
+    k0[(long long)b * C + c] = -c1 + c2 * rstd * mean;
+    k1[(long long)b * C + c] = -c2 * rstd;
   }
 }
 
@@ -1222,21 +1219,19 @@ int dmx_groupnorm_fwd(const act_t* x, act_t* y, const float* gamma, const float*
       if ((long long)B * parts->r[r].P >= (1ll << 31) / 2) return DMX_ERR_SHAPE;        // (32-bit row arithmetic in the combine)
       f2 += (long long)(parts->r[r].P / parts->r[r].tm + 2) * parts->r[r].nq;
     }
-    const int stage = f2 * 8 <= 144 * 1024 ? (int)f2 : 0;                           // staged through LDS when it fits
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_parts_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_parts_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-      attr_set = true;
-    }
-    if (y && P <= 8192 && (C >> 3) <= 256) {      // mid-size images: finalize + apply in one launch
+    if (f2 >= (1ll << 30)) return DMX_ERR_SHAPE;                                     // (32-bit item arithmetic in the combine)
+    // Mid-size images whose partial sums are small: combine + apply in one launch, every workgroup repeats the combine from LDS.  The
+    // repeat grows with the partial sums and a launch does not: at B = 8 the one launch took 9.8 against 12.4 us for two at P = 1000,
+    // C = 256 (8 KB of partial sums per image), but 25.3 against 18.1 us at the VAE's P = 4000, C = 512 (64 KB); the sizes between
+    // put the break-even near 32 KB (profiles/gn_combine_ab.txt).  The plan depends on the image's shape alone, never on the batch.
+    if (y && P <= 8192 && (C >> 3) <= 256 && f2 * 8 < 32 * 1024) {
       if (nchunk > GN_FUSED_MAXCHUNK) { nchunk = GN_FUSED_MAXCHUNK; ppb = cdiv(P, nchunk); nchunk = cdiv(P, ppb); }
-      hipLaunchKernelGGL(gn_parts_kernel<256>, dim3(nchunk, B), dim3(256), (size_t)stage * 8, st, x, y, *parts, gamma, beta, stats, scale, shift,
-                         P, C, G, rpb, ppb, eps, silu, stage);
+      hipLaunchKernelGGL(gn_parts_kernel, dim3(nchunk, B), dim3(256), (size_t)f2 * 8, st, x, y, *parts, gamma, beta, stats, scale, shift,
+                         P, C, G, rpb, ppb, eps, silu);
       return CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(gn_parts_kernel<1024>, dim3(1, B), dim3(1024), (size_t)stage * 8, st, x, (act_t*)nullptr, *parts, gamma, beta, stats, scale,
-                       shift, P, C, G, rpb, ppb, eps, silu, stage);
+    // everything else: one workgroup per (group, image) for the statistics, then the apply pass
+    hipLaunchKernelGGL(gn_parts_stats_kernel, dim3(G, B), dim3(256), 0, st, *parts, gamma, beta, stats, scale, shift, C, G, eps);
     if (y) hipLaunchKernelGGL(gn_apply_kernel, dim3(nchunk, B), dim3(nt), 0, st, x, scale, shift, y, P, C, rpb, ppb, silu);
     return CHECK_LAUNCH();
   }
@@ -1284,8 +1279,13 @@ int dmx_groupnorm_bwd(const act_t* x, const act_t* dy, const act_t* add, act_t* 
   gn_geom(P, C, nt, rpb, nchunk, ppb);
   if (parts && parts->n > 0 && ((C / G) & 3) == 0) {
     // the dgrad launch that produced dy left the two backward sums per slot and quad (EPI_GNBWD): no pass over x and dy for them
-    for (int r = 0; r < parts->n; ++r) if ((long long)B * parts->r[r].P >= (1ll << 30)) return DMX_ERR_SHAPE;
-    hipLaunchKernelGGL(gn_bwd_parts_finalize_kernel, dim3(B), dim3(1024), 0, st, *parts, stats, k0, k1, P, C, G);
+    long long f2 = 0;
+    for (int r = 0; r < parts->n; ++r) {
+      if ((long long)B * parts->r[r].P >= (1ll << 30)) return DMX_ERR_SHAPE;
+      f2 += (long long)(parts->r[r].P / parts->r[r].tm + 2) * parts->r[r].nq;
+    }
+    if (f2 >= (1ll << 30)) return DMX_ERR_SHAPE;                                     // (32-bit item arithmetic in the combine)
+    hipLaunchKernelGGL(gn_bwd_parts_finalize_kernel, dim3(G, B), dim3(256), 0, st, *parts, stats, k0, k1, P, C, G);
     hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(nchunk, B), dim3(nt), 0, st, x, dy, scale, shift, k0, k1, add, dx, P, C,
                        rpb, ppb, silu);
     return CHECK_LAUNCH();
