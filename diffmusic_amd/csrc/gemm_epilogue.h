@@ -518,7 +518,10 @@ __device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmDesc& p, f32x4 
       stage_out(reinterpret_cast<act_t*>(p.C), p.ldc, [&](const f32x4& a, float (&o)[4]) { o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; });
       if constexpr (BITS) { if (bits2 && !(flags & EPI_LRELU2)) emit_bits(); }
       if constexpr (GNS) { if (flags & EPI_GNSTATS) emit_gn(); }
-      if constexpr (GNB) { if (flags & EPI_GNBWD) emit_gnb(); }
+      // (only chunks that hold rows of image gn_b0: a wave tile that starts past its image's last row -- image-aligned M tiling, P = 700 on
+      //  128-row tiles, P = 64 on 512-row tiles -- has gn_b0 past its image, past the batch for the last images, and emit_gnb reads the tape
+      //  of image gn_b0 before it looks at a row: up to N floats beyond gnb_scale / gnb_shift / gnb_stats)
+      if constexpr (GNB) { if ((flags & EPI_GNBWD) && m0 + h * CH < mend) emit_gnb(); }
       if constexpr (GNS || GNB) {
         if ((flags & (EPI_GNSTATS | EPI_GNBWD)) && m0 + h * CH < mend) {          // this chunk = slot (m0 + h CH - image start) / 64 of its image
 #pragma unroll
