@@ -296,6 +296,41 @@ def drc_bwd(dy, x, state, tape, Lfull, threshold_db, slope, knee_db, a_att, a_re
     return d
 
 
+def _warp_delay_stride(who, delay, like, B, length):
+    K = -(-length // 64) + 1
+    assert delay.is_cuda and delay.device == like.device and delay.dtype == torch.float32 and delay.is_contiguous() and \
+        tuple(delay.shape) in ((K,), (B, K)), (who, tuple(delay.shape), "expected", (K,), "or", (B, K))
+    return 0 if delay.dim() == 1 else K
+
+
+def warp_fwd(x, delay, length):
+    """x (B, >= length) with any row stride, delay (H + 1) for every clip or (B, H + 1), H = ceil(length / 64), contiguous fp32 knots in
+    samples -> (B, length): the clip read along the delay curve, four-point Catmull-Rom (csrc/warp.hip)."""
+    if not x.is_cuda:
+        raise RuntimeError("warp_fwd: tensors must be on the GPU (no CPU fallback)")
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] >= length >= 1 and length <= 1 << 30, \
+        ("warp_fwd", x.shape, length)
+    B = x.shape[0]
+    ds = _warp_delay_stride("warp_fwd", delay, x, B, length)
+    y = torch.empty(B, length, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_warp_fwd(_p(x), x.stride(0), _p(delay), ds, _p(y), min(B, 65536), length, _stream()), "warp_fwd")
+    return y
+
+
+def warp_bwd(dy, delay, length, full):
+    """dy (B, length) contiguous, delay as for `warp_fwd` -> (B, full): the transpose of `warp_fwd` applied to dy, a gather without atomics,
+    zeros past `length`."""
+    if not dy.is_cuda:
+        raise RuntimeError("warp_bwd: tensors must be on the GPU (no CPU fallback)")
+    assert dy.dtype == torch.float32 and dy.dim() == 2 and dy.is_contiguous() and dy.shape[1] == length >= 1 and length <= full <= 1 << 30, \
+        ("warp_bwd", dy.shape, length, full)
+    B = dy.shape[0]
+    ds = _warp_delay_stride("warp_bwd", delay, dy, B, length)
+    d = torch.empty(B, full, dtype=torch.float32, device=dy.device)
+    _lib.check(_lib.lib().dmx_warp_bwd(_p(dy), _p(delay), ds, _p(d), min(B, 65536), length, full, _stream()), "warp_bwd")
+    return d
+
+
 def tf_gain(audio, x, gain_t, L, Lfull, *, out=None):
     """x (B, >= L) with any row stride, gain_t (frames, 513) shared or (B, frames, 513), frames = ceil(L / 256) + 3 -> (B, Lfull): the
     time-frequency gain A(x[:, :L]) (csrc/tf_gain.hip), +0 past L.  A is symmetric: the same call is the transpose.

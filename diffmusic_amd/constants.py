@@ -10,6 +10,7 @@ MUSIC_SOURCE_SEPARATION = "music_source_separation"           # extension: stems
 MUSIC_SPECTRAL_INPAINTING = "music_spectral_inpainting"       # extension: a gain on a region of the spectrogram (TimeFrequencyMaskOperator)
 MUSIC_BLIND_EQUALIZATION = "music_blind_equalization"         # extension: an unknown EQ curve, fitted (BlindEqualizationOperator)
 MUSIC_DECOMPRESSION = "music_decompression"                   # extension: dynamic-range compression undone (DynamicRangeOperator)
+MUSIC_WOW_FLUTTER = "music_wow_flutter"                       # extension: a varying playback speed undone (TimeWarpOperator)
 DDIM, DPS, MPGD, DSG, DITTO, DIFFMUSIC = "ddim", "dps", "mpgd", "dsg", "ditto", "diffmusic"
 NULL_TEXT, TAG, CLAP = "null_text", "tag", "clap"
 WAV_FORM, MEL_SPECTROGRAM = "wav_form", "mel_spectrogram"

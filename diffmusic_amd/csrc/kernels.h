@@ -114,6 +114,10 @@ int dmx_tf_wgrad(const DmxStftMelTables& t, const float* x, long long x_stride, 
 // waveshape.hip it needs no handle: its launchers are the C ABI's own dmx_drc_fwd / dmx_drc_bwd (include/diffmusic_hip.h)
 constexpr int DMX_DRC_BLOCK = 64;                        // samples per sidechain block; state (B, 3, H) and tape (B, H), H = ceil(L / 64)
 
+// ---- warp.hip (wow and flutter: a clip read along a given delay curve, four-point Catmull-Rom, and the transpose as a gather; one launch
+// per direction).  Like waveshape.hip it needs no handle: its launchers are the C ABI's own dmx_warp_fwd / dmx_warp_bwd
+constexpr int DMX_WARP_BLOCK = 64;                       // samples per knot interval; a curve is H + 1 knots, H = ceil(L / 64)
+
 // ---- sched.hip
 int dmx_pred_x0(const float* x, const float* eps, float* x0, long long n, float sqrt_a, float sqrt_1ma, hipStream_t st);
 int dmx_pred_x0_ex(const float* x, const float* m, float* x0, long long n, float sqrt_a, float sqrt_1ma, int ptype, float clip_r, hipStream_t st);

@@ -46,6 +46,8 @@
 #pragma weak dmx_audio_eq_update
 #pragma weak dmx_drc_fwd
 #pragma weak dmx_drc_bwd
+#pragma weak dmx_warp_fwd
+#pragma weak dmx_warp_bwd
 
 namespace {
 
@@ -376,6 +378,36 @@ at::Tensor drc_bwd(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& 
   ok(dmx_drc_bwd(dy.data_ptr<float>(), dy.stride(0), x.data_ptr<float>(), x.stride(0), state.data_ptr<float>(), tape.data_ptr<uint8_t>(),
                  work.data_ptr<float>(), d.data_ptr<float>(), Lfull, (int)std::min<int64_t>(B, 65536), (int)L, (int)Lfull, (float)threshold_db, (float)slope,
                  (float)knee_db, (float)a_att, (float)a_rel, (float)makeup_db, cur_stream()), "drc_bwd");
+  return d;
+}
+// wow and flutter (include/diffmusic_hip.h dmx_warp_fwd / dmx_warp_bwd): x (B, >= length) -> (B, length) read along the delay curve;
+// delay (H + 1) for every clip or (B, H + 1), H = ceil(length / 64), contiguous; the transpose takes dy (B, length) and returns (B, full)
+static int64_t warp_delay_stride(const at::Tensor& delay, int64_t B, int64_t length, const at::Tensor& like) {
+  const int64_t K = (length + 63) / 64 + 1;
+  f32_cuda(delay, "delay");
+  TORCH_CHECK(delay.device() == like.device() && ((delay.dim() == 1 && delay.size(0) == K) || (delay.dim() == 2 && delay.size(0) == B && delay.size(1) == K)),
+              "delay must be (", K, ") or (", B, ", ", K, ") = ceil(length / 64) + 1 knots on the clips' device");
+  return delay.dim() == 1 ? 0 : K;
+}
+at::Tensor warp_fwd(const at::Tensor& x, const at::Tensor& delay, int64_t length) {
+  rows_ok(x, length, "x");
+  TORCH_CHECK(length <= (int64_t(1) << 30), "length must be <= 2^30");
+  const int64_t B = x.size(0), ds = warp_delay_stride(delay, B, length, x);
+  DMX_DEVICE_OF(x);
+  at::Tensor y = at::empty({B, length}, x.options());
+  ok(dmx_warp_fwd(x.data_ptr<float>(), x.stride(0), delay.data_ptr<float>(), ds, y.data_ptr<float>(), (int)std::min<int64_t>(B, 65536), (int)length,
+                  cur_stream()), "warp_fwd");
+  return y;
+}
+at::Tensor warp_bwd(const at::Tensor& dy, const at::Tensor& delay, int64_t length, int64_t full) {
+  f32_cuda(dy, "dy");
+  TORCH_CHECK(dy.dim() == 2 && length >= 1 && dy.size(1) == length && full >= length && full <= (int64_t(1) << 30),
+              "dy must be contiguous (B, length) fp32 with 1 <= length <= full <= 2^30");
+  const int64_t B = dy.size(0), ds = warp_delay_stride(delay, B, length, dy);
+  DMX_DEVICE_OF(dy);
+  at::Tensor d = at::empty({B, full}, dy.options());
+  ok(dmx_warp_bwd(dy.data_ptr<float>(), delay.data_ptr<float>(), ds, d.data_ptr<float>(), (int)std::min<int64_t>(B, 65536), (int)length, (int)full,
+                  cur_stream()), "warp_bwd");
   return d;
 }
 // time-frequency gain (include/diffmusic_hip.h dmx_audio_tf_gain): x (B, >= L), gain_t (frames, 513) shared or (B, frames, 513) -> (B, Lfull)
@@ -720,10 +752,12 @@ TORCH_LIBRARY(diffmusic_hip, m) {
                                                          {"dmx_audio_tf_wgrad", (const void*)&dmx_audio_tf_wgrad},
                                                          {"dmx_audio_eq_update", (const void*)&dmx_audio_eq_update},
                                                          {"dmx_drc_fwd", (const void*)&dmx_drc_fwd},
-                                                         {"dmx_drc_bwd", (const void*)&dmx_drc_bwd}};
+                                                         {"dmx_drc_bwd", (const void*)&dmx_drc_bwd},
+                                                         {"dmx_warp_fwd", (const void*)&dmx_warp_fwd},
+                                                         {"dmx_warp_bwd", (const void*)&dmx_warp_bwd}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
-                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression entry points): rebuild with `python -m diffmusic_amd.build --force`");
+                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter entry points): rebuild with `python -m diffmusic_amd.build --force`");
   }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
@@ -758,6 +792,8 @@ TORCH_LIBRARY(diffmusic_hip, m) {
         &drc_fwd);
   m.def("drc_bwd(Tensor dy, Tensor x, Tensor state, Tensor tape, int Lfull, float threshold_db, float slope, float knee_db, float a_att, float a_rel, "
         "float makeup_db) -> Tensor", &drc_bwd);
+  m.def("warp_fwd(Tensor x, Tensor delay, int length) -> Tensor", &warp_fwd);
+  m.def("warp_bwd(Tensor dy, Tensor delay, int length, int full) -> Tensor", &warp_bwd);
   m.def("noise_add(Tensor y, Tensor noise, float sigma) -> Tensor", &noise_add);
   m.def("tf_gain(int audio, Tensor x, Tensor gain_t, int L, int Lfull, *, Tensor(a!)? out=None) -> Tensor", &tf_gain);
   m.def("tf_curve(int audio, Tensor x, Tensor curve, int L, int Lfull) -> Tensor", &tf_curve);

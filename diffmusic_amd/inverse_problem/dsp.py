@@ -171,3 +171,62 @@ def drc_static_curve(level_db, threshold_db, ratio, knee_db):
     d = np.asarray(level_db, dtype=np.float64) - threshold_db
     knee = k * (d + 0.5 * knee_db) ** 2 / (2.0 * knee_db) if knee_db > 0 else np.zeros_like(d)
     return np.where(2.0 * d < -knee_db, 0.0, np.where(2.0 * d <= knee_db, knee, k * d))
+
+
+# ---- wow and flutter (TimeWarpOperator; csrc/warp.hip): a delay curve in samples, one knot per 64 samples, linear between the knots
+WARP_BLOCK = 64
+WARP_MAX_DELAY = 4096.0      # |d[j]|: a quarter of a second at 16 kHz; an fp32 delay of that size still resolves 2.4e-4 of a sample
+WARP_MAX_STEP = 16.0         # |d[j+1] - d[j]|: the local speed within +-25 %, the read position strictly increasing
+
+
+def warp_knots(length):
+    """H + 1 = ceil(length / 64) + 1: the number of knots of the delay curve of a clip of `length` samples."""
+    length = int(length)
+    if length < 1:
+        raise ValueError(f"length = {length!r}: at least one sample")
+    return -(-length // WARP_BLOCK) + 1
+
+
+def check_warp_curve(delay, name="delay"):
+    """The contract of a delay curve ((K,) or (B, K) numpy fp32 knots in samples), refused by name: finite, |d[j]| <= 4096,
+    |d[j+1] - d[j]| <= 16.  Returns the array."""
+    d = np.asarray(delay)
+    if d.dtype != np.float32 or d.ndim not in (1, 2) or d.shape[-1] < 2 or d.shape[0] < 1:
+        raise ValueError(f"{name} has shape {d.shape} and dtype {d.dtype}: fp32 knots (K,) for every clip or (B, K), K = warp_knots(length) >= 2")
+    if not np.isfinite(d).all():
+        raise ValueError(f"{name}: every knot must be finite")
+    worst = float(np.abs(d).max())
+    if worst > WARP_MAX_DELAY:
+        raise ValueError(f"{name}: |d[j]| reaches {worst!r} samples, the limit is {WARP_MAX_DELAY:g}")
+    step = float(np.abs(np.diff(d.astype(np.float64), axis=-1)).max())
+    if step > WARP_MAX_STEP:
+        raise ValueError(f"{name}: |d[j+1] - d[j]| reaches {step!r} samples per block of {WARP_BLOCK}, the limit is {WARP_MAX_STEP:g} "
+                         "(a local speed within +-25 %)")
+    return d
+
+
+def wow_curve(length, sample_rate, components=(), speed_percent=0.0):
+    """The knots (warp_knots(length),) np.float32 of the delay curve, in samples, of a transport that runs `speed_percent` off speed and
+    whose speed is modulated by `components` = ((rate_hz, depth_percent, phase_deg), ...) (phase optional) -- wow below about 6 Hz,
+    flutter above:
+
+        delta(t) = fs * [speed / 100 * t + sum_c depth_c / 100 * (sin(2 pi f_c t + p_c) - sin p_c) / (2 pi f_c)],    t = 64 j / fs
+
+    the integral of the relative speed error, zero at t = 0; positive = reading ahead (the medium ran fast).  Computed in float64 and rounded
+    once to fp32.  A result outside the contract of the curve (`check_warp_curve`) is refused by name."""
+    K = warp_knots(length)
+    sample_rate, speed_percent = float(sample_rate), float(speed_percent)
+    if not (math.isfinite(sample_rate) and sample_rate > 0):
+        raise ValueError(f"sample_rate = {sample_rate!r}: a positive finite rate")
+    if not math.isfinite(speed_percent):
+        raise ValueError(f"speed_percent = {speed_percent!r}: a finite percentage")
+    t = np.arange(K, dtype=np.float64) * WARP_BLOCK / sample_rate
+    delta = speed_percent / 100.0 * t
+    for c in components:
+        c = tuple(float(v) for v in c)
+        if len(c) not in (2, 3) or not all(math.isfinite(v) for v in c) or c[0] <= 0:
+            raise ValueError(f"components: {c!r} is not (rate_hz > 0, depth_percent[, phase_deg]), all finite")
+        rate, depth, phase = c[0], c[1], math.radians(c[2]) if len(c) == 3 else 0.0
+        w = 2.0 * math.pi * rate
+        delta = delta + depth / 100.0 * (np.sin(w * t + phase) - math.sin(phase)) / w
+    return check_warp_curve((sample_rate * delta).astype(np.float32), "wow_curve")

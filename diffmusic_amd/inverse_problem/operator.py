@@ -976,6 +976,73 @@ class DynamicRangeOperator(_MelOperator):
         return y, adjoint
 
 
+class TimeWarpOperator(_MelOperator):
+    """Wow and flutter (extension; the first operator that MOVES samples in time): the playback speed was not the recording speed, and it
+    varied -- tape, cassette, vinyl and film transfers.  Per clip, x zero outside [0, L) (csrc/warp.hip):
+
+        delta(64 j + r) = d[j] + (r / 64) (d[j+1] - d[j])      the delay curve: H + 1 = dsp.warp_knots(L) knots in samples, one per 64 samples
+        y[n] = x(n + delta(n))                                 four-point Catmull-Rom on the taps i - 1 .. i + 2, i = n + floor(delta)
+
+    Positive delta reads ahead: the medium ran fast.  forward = noiser(A(x)), transform = clamp(wav2mel, -80, 80) like the
+    IdentityOperator's.  A is linear and materialised (`_on_load` is None): a guided step is the identity's plus `warp_fwd` and `warp_bwd`,
+    one launch each; `adjoint` is the transpose as a gather, without atomics.
+
+    delay: (H + 1,) -- one curve for every clip -- or (B, H + 1), fp32 knots; `dsp.wow_curve` builds one from speed components.  It is GIVEN,
+    not fitted, and checked here, by name, on the host copy: finite, |d[j]| <= 4096, |d[j+1] - d[j]| <= 16.  The curve belongs to ONE clip
+    length: `apply`, `forward` and `guidance` raise a ValueError naming `warp_knots(length)` for any other (inside a TrackOperator build it
+    for the track's length).  With per-clip curves the batch must be B, and the pipelines refuse `lanes > 1` and `shard=True` (the curves
+    are indexed by batch position); a shared curve has no such state.  The front end and the device copy are made on first use, so the
+    operator can be built without a GPU.  `dead_span` is None: the curve moves every sample."""
+
+    def __init__(self, sample_rate=16000, delay=None, noiser=None):
+        if not (math.isfinite(float(sample_rate)) and float(sample_rate) > 0):
+            raise ValueError(f"sample_rate = {sample_rate!r}: a positive finite rate")
+        if delay is None:
+            raise ValueError("delay: the knots of the delay curve, (warp_knots(length),) or (B, warp_knots(length)) (dsp.wow_curve builds one)")
+        d = torch.as_tensor(delay).detach().to(device="cpu", dtype=torch.float32).contiguous()
+        dsp.check_warp_curve(d.numpy(), "delay")
+        self.sample_rate, self.noiser = sample_rate, noiser
+        self.per_clip = d.dim() == 2
+        self.delay = d.clone()                                # host copy
+        self._delay_dev = None
+        self._init_mel(sample_rate, lazy=True)
+
+    @property
+    def knots(self):
+        return self.delay.shape[-1]
+
+    def _check(self, batch, length):
+        K = dsp.warp_knots(length)
+        if self.knots != K:
+            raise ValueError(f"TimeWarpOperator holds a delay curve of shape {tuple(self.delay.shape)}; a clip of {length} samples needs "
+                             f"warp_knots({length}) = {K} knots")
+        if self.per_clip and self.delay.shape[0] != batch:
+            raise ValueError(f"TimeWarpOperator holds {self.delay.shape[0]} per-clip delay curve(s), the batch has {batch} clip(s): expected "
+                             f"({batch}, {K})")
+
+    def delay_on(self, device):
+        """The knots on `device` (one tensor, kept)."""
+        if self._delay_dev is None or self._delay_dev.device != device:
+            self._delay_dev = self.delay.to(device)
+        return self._delay_dev
+
+    def forward(self, data, **kwargs):
+        self._check(data.shape[0], data.shape[-1])            # before the tensor has to be on the GPU
+        return super().forward(data, **kwargs)
+
+    def guidance(self, wav, length, measurement, supervised_space, **kw):
+        self._check(wav.shape[0], length)
+        return super().guidance(wav, length, measurement, supervised_space, **kw)
+
+    def apply(self, x, length, **kw):
+        self._check(x.shape[0], length)
+        d = self.delay_on(x.device)
+
+        def adjoint(dy, full):                                # A is linear: the transpose needs neither x nor a tape
+            return ops.hip.warp_bwd(dy.contiguous(), d, int(length), int(full))
+        return ops.hip.warp_fwd(x, d, int(length)), adjoint
+
+
 class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 (unrunnable in the reference: run.py:213-214)
     """Style guidance with BUILD-DEFINED semantics (the reference's `clap_model.get_gram_matrix`
     does not exist anywhere): `forward(x) = noiser(x)` (identity, operator.py:270-271) and

@@ -21,7 +21,8 @@ from ..torch_utils import randn_tensor
 from ..profiling import stage
 from ..inverse_problem.noise import step_sigma
 from ..inverse_problem.mixture import MixtureOperator
-from ..inverse_problem.operator import BlindDereverberationOperator, BlindEqualizationOperator, TimeFrequencyMaskOperator
+from ..inverse_problem.operator import BlindDereverberationOperator, BlindEqualizationOperator, TimeFrequencyMaskOperator, \
+    TimeWarpOperator
 from .. import parallel
 
 
@@ -459,6 +460,13 @@ class MusicLDMPipeline:
                                  "by batch position, and a lane sees only its own clips")
             if shard or group is not None:
                 raise ValueError("TimeFrequencyMaskOperator with per-clip gains cannot be sharded over ranks (shard / group): its gains are "
+                                 "indexed by batch position, and a rank sees only its own clips")
+        if isinstance(op, TimeWarpOperator) and op.per_clip:              # (one shared curve has no per-position state)
+            if int(self.lanes if lanes is None else lanes) > 1:
+                raise ValueError("TimeWarpOperator with per-clip delay curves cannot run as clip lanes (lanes > 1): its curves are indexed "
+                                 "by batch position, and a lane sees only its own clips")
+            if shard or group is not None:
+                raise ValueError("TimeWarpOperator with per-clip delay curves cannot be sharded over ranks (shard / group): its curves are "
                                  "indexed by batch position, and a rank sees only its own clips")
         if isinstance(op, BlindEqualizationOperator):
             if int(self.lanes if lanes is None else lanes) > 1:

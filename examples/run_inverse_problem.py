@@ -15,6 +15,7 @@ embedding file (`--prompt_embeds x.npy`, (B, 512) CLAP text embeddings for Music
     python examples/run_inverse_problem.py -c dps -t music_spectral_inpainting --tf_box 2000,4000,2,2.5 --hum 50,5      # a spectral hole + hum
     python examples/run_inverse_problem.py -c dps -t music_blind_equalization --eq_lowpass 3000,4      # the EQ curve is fitted, not given
     python examples/run_inverse_problem.py -c dps -t music_decompression --drc_threshold_db -30 --drc_ratio inf      # undo a limiter
+    python examples/run_inverse_problem.py -c dps -t music_wow_flutter --wow 0.5,1 --wow 9,0.2 --speed_pct 0.5      # wow, flutter and a drift
 
 `--track_overlap_s S` restores a recording longer than the model window whole (track mode, inverse_problem/track.py): the first `--wav`
 (or a synthetic 2.5-window signal) becomes overlapping windows under one loss and one stitched file is written.  Without the flag a
@@ -32,6 +33,11 @@ either the `points` of configs/inverse_problem/music_blind_equalization.yaml are
 `-t music_decompression` measures through a dynamic-range compressor with given parameters (DynamicRangeOperator): `--drc_threshold_db`,
 `--drc_ratio` (>= 1, `inf` = a limiter), `--drc_knee_db`, `--drc_attack_ms`, `--drc_release_ms`, `--drc_makeup_db`; a flag that is not
 given takes its value from configs/inverse_problem/music_decompression.yaml.
+
+`-t music_wow_flutter` measures through a playback speed that was off and varied (TimeWarpOperator; the delay curve is given, not fitted):
+`--wow RATE_HZ,DEPTH_PCT[,PHASE_DEG]` (repeatable: one speed-modulation component each) and `--speed_pct P` (a constant speed error);
+a flag that is not given takes its value from configs/inverse_problem/music_wow_flutter.yaml.  The curve is built for the clip's length,
+in track mode for the track's.
 
 `-t music_source_separation` restores K stems from their mixture under one loss (inverse_problem/mixture.py), one prompt embedding per
 stem: `--wav` names the stems whose gain-weighted sum (`--gains`) is the measurement (SI-SDR per stem is printed), `--mixture mix.wav
@@ -55,20 +61,23 @@ from diffmusic_amd.pipelines import get_pipeline                                
 from diffmusic_amd.schedulers import get_scheduler                                  # noqa: E402
 
 TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation", "music_declipping",
-         "music_blind_dereverberation", "music_source_separation", "music_spectral_inpainting", "music_blind_equalization", "music_decompression")
+         "music_blind_dereverberation", "music_source_separation", "music_spectral_inpainting", "music_blind_equalization", "music_decompression",
+         "music_wow_flutter")
 SEPARATION = "music_source_separation"
 SPECTRAL = "music_spectral_inpainting"
 BLIND_EQ = "music_blind_equalization"
 DECOMPRESSION = "music_decompression"
+WOW_FLUTTER = "music_wow_flutter"
 DRC_FLAGS = ("threshold_db", "ratio", "knee_db", "attack_ms", "release_ms", "makeup_db")
 
 
-def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None, tf_boxes=None, eq_true=None, drc=None):
+def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None, tf_boxes=None, eq_true=None, drc=None, warp=None):
     """run.py:157-212: one operator per task, constructor arguments from the data / model config.  `audio_length_in_s`: the length the
     operator acts on when it is not the model window (a track).  `clip_threshold`: music_declipping's threshold(s), a float or one value
     per clip (`threshold_for_sdr` of the clean clips).  `tf_boxes`: music_spectral_inpainting's boxes (`spectral_boxes`).  `eq_true`:
     music_blind_equalization's true curve (`equalization_curve`), kept on the operator for `forward`.  `drc`: music_decompression's
-    parameters (`compressor_params`)."""
+    parameters (`compressor_params`).  `warp`: music_wow_flutter's speed components (`warp_params`); the delay curve is built here, for the
+    length the operator acts on."""
     noiser = P.get_noiser(**cfg.inverse_problem.noise)
     d, scale = cfg.data, 1
     seconds = cfg.model.pipe.audio_length_in_s if audio_length_in_s is None else audio_length_in_s
@@ -108,6 +117,11 @@ def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=
         if drc is None:
             raise ValueError("music_decompression needs drc (compressor_params(args, cfg))")
         op = P.DynamicRangeOperator(sample_rate=d.sample_rate, noiser=noiser, **drc)
+    elif task == WOW_FLUTTER:
+        if warp is None:
+            raise ValueError("music_wow_flutter needs warp (warp_params(args, cfg))")
+        curve = P.wow_curve(int(seconds * d.sample_rate), d.sample_rate, **warp)
+        op = P.TimeWarpOperator(sample_rate=d.sample_rate, delay=curve, noiser=noiser)
     else:
         raise ValueError(f"Unknown task: {task}")
     return op, scale
@@ -191,6 +205,9 @@ def parse_args(argv=None):
     for flag, what in zip(DRC_FLAGS, ("threshold in dB", "ratio >= 1, inf = a limiter", "knee width in dB, 0 = hard knee", "attack time in ms",
                                       "release time in ms", "make-up gain in dB")):
         ap.add_argument(f"--drc_{flag}", type=float, default=None, help=f"music_decompression: the compressor's {what} (default: the task's config)")
+    ap.add_argument("--wow", action="append", default=None, metavar="RATE_HZ,DEPTH_PCT[,PHASE_DEG]",
+                    help="music_wow_flutter: one speed-modulation component (repeatable; default: the task's config)")
+    ap.add_argument("--speed_pct", type=float, default=None, help="music_wow_flutter: constant speed error in percent (default: the task's config)")
     ap.add_argument("--strength", type=float, default=1.0, help="share of num_inference_steps a warm start runs (diffusers' img2img rule)")
     return ap.parse_args(argv)
 
@@ -315,6 +332,36 @@ def compressor_params(args, cfg=None):
     return out
 
 
+def warp_params(args, cfg=None, length=16000, sample_rate=16000):
+    """The argument rules of -t music_wow_flutter -> the keyword arguments of `wow_curve`: `components` from every --wow flag (the config's
+    `wow` list without one) and `speed_percent` from --speed_pct (the config's `speed_pct`).  A curve for `length` samples is built once
+    here so that `wow_curve`'s own refusals come before any GPU work.  Any other task refuses the flags."""
+    if args.task != WOW_FLUTTER:
+        if args.wow is not None or args.speed_pct is not None:
+            raise SystemExit(f"--{'wow' if args.wow is not None else 'speed_pct'} belongs to -t {WOW_FLUTTER}")
+        return None
+    ip = cfg.inverse_problem if cfg is not None else {}
+    if args.wow is not None:
+        components = []
+        for text in args.wow:
+            try:
+                c = tuple(float(v) for v in text.split(","))
+            except ValueError:
+                raise SystemExit(f"--wow {text!r}: RATE_HZ,DEPTH_PCT[,PHASE_DEG]")
+            if len(c) not in (2, 3):
+                raise SystemExit(f"--wow {text!r}: RATE_HZ,DEPTH_PCT[,PHASE_DEG]")
+            components.append(c)
+    else:
+        components = [tuple(float(v) for v in c) for c in (ip.get("wow") or ())]
+    speed = args.speed_pct if args.speed_pct is not None else float(ip.get("speed_pct") or 0.0)
+    out = dict(components=tuple(components), speed_percent=float(speed))
+    try:
+        P.wow_curve(length, sample_rate, **out)
+    except ValueError as e:
+        raise SystemExit(f"-t {WOW_FLUTTER}: {e}")
+    return out
+
+
 def separation_stems(args):
     """The argument rules of -t music_source_separation -> K, the number of stems; any other task refuses the separation flags."""
     if args.task != SEPARATION:
@@ -403,7 +450,7 @@ def run_separation(args, cfg, K):
 def main(argv=None):
     args = parse_args(argv)
     overrides = [f"data={args.data}", f"model={args.model}"]
-    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL, BLIND_EQ, DECOMPRESSION):
+    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL, BLIND_EQ, DECOMPRESSION, WOW_FLUTTER):
         overrides.append(f"inverse_problem={args.task}")
     stems = separation_stems(args)
     if args.project and args.task not in ("music_declipping", SEPARATION):
@@ -412,6 +459,7 @@ def main(argv=None):
     tf_boxes = spectral_boxes(args, cfg)
     eq_true = equalization_curve(args, cfg)
     drc = compressor_params(args, cfg)
+    warp = warp_params(args, cfg, length=int(cfg.model.pipe.audio_length_in_s * cfg.data.sample_rate), sample_rate=cfg.data.sample_rate)
     if stems is not None:
         if args.model != "musicldm":
             raise SystemExit("this driver feeds MusicLDM's class-embedding conditioning; AudioLDM2 needs its T5 / GPT-2 states (see bench.py --workload)")
@@ -428,7 +476,7 @@ def main(argv=None):
     if args.track_overlap_s is None:
         gt = load_clips(args.wav, args.batch, sr, length, args.seed).to(device)
         thr = P.threshold_for_sdr(gt, args.clip_sdr_db) if args.task == "music_declipping" else None
-        op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr, tf_boxes=tf_boxes, eq_true=eq_true, drc=drc)
+        op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr, tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp)
         B = gt.shape[0]
     else:
         if args.task == "music_generation":
@@ -438,7 +486,7 @@ def main(argv=None):
         layout = P.TrackLayout(T, length, int(round(args.track_overlap_s * sr)))
         thr = float(P.threshold_for_sdr(gt, args.clip_sdr_db)[0]) if args.task == "music_declipping" else None
         inner, scale = build_operator(args.task, cfg, args.mask_type, audio_length_in_s=P.seconds_for_samples(T, sr), clip_threshold=thr,
-                                      tf_boxes=tf_boxes, eq_true=eq_true, drc=drc)
+                                      tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp)
         op = P.TrackOperator(inner, layout)
         B = layout.num_windows
         sched_kw["per_clip_norm"] = False                                          # one loss, norms over all windows

@@ -35,7 +35,8 @@ extern "C" {
  * and dmx_stem_mix_fwd / dmx_stem_mix_bwd / dmx_stem_project (source separation: the stems of a mixture as the batch) and dmx_audio_tf_gain /
  * dmx_audio_tf_frames (time-frequency masking: a real gain on the STFT) and dmx_audio_tf_curve / dmx_audio_tf_wgrad /
  * dmx_audio_tf_wgrad_segments / dmx_audio_eq_update (blind equalisation: a fitted gain curve per clip) and dmx_drc_fwd / dmx_drc_bwd
- * (de-compression: a dynamic-range compressor and the transpose of its Jacobian) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * (de-compression: a dynamic-range compressor and the transpose of its Jacobian) and dmx_warp_fwd / dmx_warp_bwd (wow and flutter: a clip
+ * read along a delay curve, and the transpose) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
  * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
@@ -280,6 +281,20 @@ int dmx_drc_fwd(const float* x, long long x_stride, float* y, long long y_stride
 int dmx_drc_bwd(const float* dy, long long dy_stride, const float* x, long long x_stride, const float* state, const unsigned char* tape,
                 float* work, float* dx, long long dx_stride, int batch, int L, int Lfull, float threshold_db, float slope, float knee_db,
                 float a_att, float a_rel, float makeup_db, void* stream);
+/* Wow and flutter on materialised waveforms (csrc/warp.hip): the clip, taken as zero outside [0, L), read at
+ * n + delta(n), where delta is linear between the H + 1 knots of `delay` (fp32, in samples, one knot per 64 samples, H = ceil(L / 64));
+ * four-point Catmull-Rom on the taps i - 1 .. i + 2, i = n + floor(delta), a tap outside the clip skipped.  delay_stride = 0: one curve for
+ * every clip; otherwise >= H + 1 floats between the clips' curves.  Contract on the curve, checked by the callers on the host: finite,
+ * |d[j]| <= 4096, |d[j+1] - d[j]| <= 16.  Outside it the results are unspecified but every access stays inside the buffers, and a
+ * non-finite delta(n) gives y[n] = NaN.
+ *   warp_fwd   y[b, 0:L] = A x, y (batch, L) contiguous
+ *   warp_bwd   dx[b, 0:L] = A^T dy, +0 on [L, full); dy (batch, L) and dx (batch, full) contiguous.  A gather: no atomics
+ * One launch each, bit-reproducible and independent of the batch position.  A NaN at x[m] makes exactly the y[n] NaN whose four taps
+ * include m (a zero weight does not shield it), a NaN at dy[n] exactly the dx[m] among the taps of n; other clips are untouched.
+ * DMX_ERR_SHAPE, with nothing written, for a null pointer, batch outside 1 .. 65535, L < 1, full < L, a length above 2^30, x_stride < L,
+ * or a delay stride that is neither 0 nor at least H + 1. */
+int dmx_warp_fwd(const float* x, long long x_stride, const float* delay, long long delay_stride, float* y, int batch, int L, void* stream);
+int dmx_warp_bwd(const float* dy, const float* delay, long long delay_stride, float* dx, int batch, int L, int full, void* stream);
 /* out[i] = y[i] + scale * z[i], i < n (the noiser on a materialised measurement A(x): super-resolution, dereverberation, wav_form) */
 int dmx_noise_add(const float* y, const float* z, float* out, long long n, float scale, void* stream);
 /* PhaseRetrievalOperator.forward: |torch.stft(wav)| as (B, n_fft/2+1, frames) fp32 */
