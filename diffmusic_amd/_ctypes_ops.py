@@ -331,6 +331,41 @@ def warp_bwd(dy, delay, length, full):
     return d
 
 
+def warp_wgrad(dy, x, delay, length):
+    """dy = dLoss/dy (B, length) contiguous, x (B, >= length) with any row stride, delay as for `warp_fwd` -> part (B, H, 2): the gradient of
+    the loss in the fine knots as one pair per block of 64 samples, dd[j] = part[:, j, 0] + part[:, j - 1, 1] (csrc/warp_fit.hip)."""
+    if not x.is_cuda:
+        raise RuntimeError("warp_wgrad: tensors must be on the GPU (no CPU fallback)")
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] >= length >= 1 and length <= 1 << 30, \
+        ("warp_wgrad", x.shape, length)
+    B = x.shape[0]
+    assert dy.is_cuda and dy.device == x.device and dy.dtype == torch.float32 and dy.is_contiguous() and tuple(dy.shape) == (B, length), \
+        ("warp_wgrad", dy.shape, (B, length))
+    ds = _warp_delay_stride("warp_wgrad", delay, x, B, length)
+    part = torch.empty(B, -(-length // 64), 2, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_warp_wgrad(_p(dy), _p(x), x.stride(0), _p(delay), ds, _p(part), min(B, 65536), length, _stream()), "warp_wgrad")
+    return part
+
+
+def warp_update(part, coarse, m, v, fine, length, knot_stride, k, lr, beta1, beta2, eps, max_delay, mean):
+    """One Adam step on the coarse knots from the pairs of `warp_wgrad`, minus the mean of the stepped knots when `mean`, the clamp to
+    +-max_delay, and the expansion into the fine curve; coarse, m, v (B, P + 1) and fine (B, H + 1) are updated IN PLACE, P = ceil(H /
+    knot_stride), k the 1-based count of updates since the last reset.  A clip whose gradient or step is not finite keeps its state."""
+    if not part.is_cuda:
+        raise RuntimeError("warp_update: tensors must be on the GPU (no CPU fallback)")
+    assert 1 <= length <= 1 << 30 and 1 <= knot_stride <= 64, ("warp_update", length, knot_stride)
+    H = -(-length // 64)
+    P = -(-H // knot_stride)
+    assert part.dtype == torch.float32 and part.dim() == 3 and part.is_contiguous() and part.shape[0] >= 1 and \
+        tuple(part.shape[1:]) == (H, 2), ("warp_update", tuple(part.shape), (H, 2))
+    B = part.shape[0]
+    for t, n in ((coarse, P + 1), (m, P + 1), (v, P + 1), (fine, H + 1)):
+        assert t.is_cuda and t.device == part.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, n), \
+            ("warp_update", tuple(t.shape), (B, n))
+    _lib.check(_lib.lib().dmx_warp_update(_p(part), _p(coarse), _p(m), _p(v), _p(fine), B, length, int(knot_stride), int(k), float(lr),
+                                          float(beta1), float(beta2), float(eps), float(max_delay), 1 if mean else 0, _stream()), "warp_update")
+
+
 def tf_gain(audio, x, gain_t, L, Lfull, *, out=None):
     """x (B, >= L) with any row stride, gain_t (frames, 513) shared or (B, frames, 513), frames = ceil(L / 256) + 3 -> (B, Lfull): the
     time-frequency gain A(x[:, :L]) (csrc/tf_gain.hip), +0 past L.  A is symmetric: the same call is the transpose.

@@ -118,6 +118,10 @@ constexpr int DMX_DRC_BLOCK = 64;                        // samples per sidechai
 // per direction).  Like waveshape.hip it needs no handle: its launchers are the C ABI's own dmx_warp_fwd / dmx_warp_bwd
 constexpr int DMX_WARP_BLOCK = 64;                       // samples per knot interval; a curve is H + 1 knots, H = ceil(L / 64)
 
+// ---- warp_fit.hip (blind wow and flutter: the gradient of a loss in the knots of the delay curve as one pair per block, and the Adam +
+// projection update of a coarse curve with its expansion into the fine one; one launch each).  No handle either: its launchers are the C
+// ABI's own dmx_warp_wgrad / dmx_warp_update; the position arithmetic is warp.hip's, from warp_common.h
+
 // ---- sched.hip
 int dmx_pred_x0(const float* x, const float* eps, float* x0, long long n, float sqrt_a, float sqrt_1ma, hipStream_t st);
 int dmx_pred_x0_ex(const float* x, const float* m, float* x0, long long n, float sqrt_a, float sqrt_1ma, int ptype, float clip_r, hipStream_t st);

@@ -48,6 +48,8 @@
 #pragma weak dmx_drc_bwd
 #pragma weak dmx_warp_fwd
 #pragma weak dmx_warp_bwd
+#pragma weak dmx_warp_wgrad
+#pragma weak dmx_warp_update
 
 namespace {
 
@@ -410,6 +412,38 @@ at::Tensor warp_bwd(const at::Tensor& dy, const at::Tensor& delay, int64_t lengt
                   cur_stream()), "warp_bwd");
   return d;
 }
+// blind wow and flutter (include/diffmusic_hip.h dmx_warp_wgrad / dmx_warp_update): the gradient of a loss in the fine knots as one pair
+// per block, part (B, H, 2), and the Adam + projection update of the coarse curve with its expansion; coarse, m, v and fine are written
+at::Tensor warp_wgrad(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& delay, int64_t length) {
+  rows_ok(x, length, "x");
+  f32_cuda(dy, "dy");
+  TORCH_CHECK(length <= (int64_t(1) << 30), "length must be <= 2^30");
+  TORCH_CHECK(dy.dim() == 2 && dy.size(0) == x.size(0) && dy.size(1) == length && dy.device() == x.device(),
+              "dy must be contiguous (B, length) fp32 on x's device");
+  const int64_t B = x.size(0), H = (length + 63) / 64, ds = warp_delay_stride(delay, B, length, x);
+  DMX_DEVICE_OF(x);
+  at::Tensor part = at::empty({B, H, 2}, x.options());
+  ok(dmx_warp_wgrad(dy.data_ptr<float>(), x.data_ptr<float>(), x.stride(0), delay.data_ptr<float>(), ds, part.data_ptr<float>(),
+                    (int)std::min<int64_t>(B, 65536), (int)length, cur_stream()), "warp_wgrad");
+  return part;
+}
+void warp_update(const at::Tensor& part, at::Tensor coarse, at::Tensor m, at::Tensor v, at::Tensor fine, int64_t length, int64_t knot_stride,
+                 int64_t k, double lr, double beta1, double beta2, double eps, double max_delay, bool mean) {
+  f32_cuda(part, "part");
+  TORCH_CHECK(length >= 1 && length <= (int64_t(1) << 30) && knot_stride >= 1 && knot_stride <= 64, "1 <= length <= 2^30 and 1 <= knot_stride <= 64");
+  const int64_t H = (length + 63) / 64, P = (H + knot_stride - 1) / knot_stride;
+  TORCH_CHECK(part.dim() == 3 && part.size(0) >= 1 && part.size(1) == H && part.size(2) == 2, "part must be (B, ", H, ", 2)");
+  DMX_DEVICE_OF(part);
+  const int64_t B = part.size(0);
+  for (const at::Tensor* t : {&coarse, &m, &v}) {
+    f32_cuda(*t, "coarse / m / v");
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == P + 1 && t->device() == part.device(), "coarse, m and v must be (", B, ", ", P + 1, ") on part's device");
+  }
+  f32_cuda(fine, "fine");
+  TORCH_CHECK(fine.dim() == 2 && fine.size(0) == B && fine.size(1) == H + 1 && fine.device() == part.device(), "fine must be (", B, ", ", H + 1, ") on part's device");
+  ok(dmx_warp_update(part.data_ptr<float>(), coarse.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), fine.data_ptr<float>(), (int)B,
+                     (int)length, (int)knot_stride, (int)k, lr, beta1, beta2, eps, max_delay, mean ? 1 : 0, cur_stream()), "warp_update");
+}
 // time-frequency gain (include/diffmusic_hip.h dmx_audio_tf_gain): x (B, >= L), gain_t (frames, 513) shared or (B, frames, 513) -> (B, Lfull)
 // out: caller-owned (B, >= Lfull) fp32 with any row stride; only out[:, :Lfull] is written
 at::Tensor tf_gain(int64_t audio, const at::Tensor& x, const at::Tensor& gain_t, int64_t L, int64_t Lfull, const std::optional<at::Tensor>& out) {
@@ -754,10 +788,12 @@ TORCH_LIBRARY(diffmusic_hip, m) {
                                                          {"dmx_drc_fwd", (const void*)&dmx_drc_fwd},
                                                          {"dmx_drc_bwd", (const void*)&dmx_drc_bwd},
                                                          {"dmx_warp_fwd", (const void*)&dmx_warp_fwd},
-                                                         {"dmx_warp_bwd", (const void*)&dmx_warp_bwd}};
+                                                         {"dmx_warp_bwd", (const void*)&dmx_warp_bwd},
+                                                         {"dmx_warp_wgrad", (const void*)&dmx_warp_wgrad},
+                                                         {"dmx_warp_update", (const void*)&dmx_warp_update}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
-                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter entry points): rebuild with `python -m diffmusic_amd.build --force`");
+                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter / blind-wow-and-flutter entry points): rebuild with `python -m diffmusic_amd.build --force`");
   }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
@@ -794,6 +830,9 @@ TORCH_LIBRARY(diffmusic_hip, m) {
         "float makeup_db) -> Tensor", &drc_bwd);
   m.def("warp_fwd(Tensor x, Tensor delay, int length) -> Tensor", &warp_fwd);
   m.def("warp_bwd(Tensor dy, Tensor delay, int length, int full) -> Tensor", &warp_bwd);
+  m.def("warp_wgrad(Tensor dy, Tensor x, Tensor delay, int length) -> Tensor", &warp_wgrad);
+  m.def("warp_update(Tensor part, Tensor(a!) coarse, Tensor(b!) m, Tensor(c!) v, Tensor(d!) fine, int length, int knot_stride, int k, float lr, "
+        "float beta1, float beta2, float eps, float max_delay, bool mean) -> ()", &warp_update);
   m.def("noise_add(Tensor y, Tensor noise, float sigma) -> Tensor", &noise_add);
   m.def("tf_gain(int audio, Tensor x, Tensor gain_t, int L, int Lfull, *, Tensor(a!)? out=None) -> Tensor", &tf_gain);
   m.def("tf_curve(int audio, Tensor x, Tensor curve, int L, int Lfull) -> Tensor", &tf_curve);

@@ -205,6 +205,33 @@ def check_warp_curve(delay, name="delay"):
     return d
 
 
+# ---- blind wow and flutter (BlindTimeWarpOperator; csrc/warp_fit.hip): the curve lives on coarse knots, one every `knot_stride` fine knots
+WARP_KNOT_STRIDES = (1, 2, 4, 8, 16, 32, 64)
+
+
+def warp_coarse_knots(length, knot_stride):
+    """P + 1 = ceil(H / knot_stride) + 1 coarse knots carry the curve of a clip of `length` samples (H = ceil(length / 64) blocks)."""
+    if knot_stride not in WARP_KNOT_STRIDES or isinstance(knot_stride, bool):
+        raise ValueError(f"knot_stride = {knot_stride!r}: a power of two from 1 to 64 (fine knots per coarse knot)")
+    return -(-(warp_knots(length) - 1) // int(knot_stride)) + 1
+
+
+def warp_expand(coarse, length, knot_stride):
+    """Coarse knots (P + 1,) or (B, P + 1) -> the fine knots (H + 1,) or (B, H + 1) np.float32 that `warp_update` writes, in its arithmetic:
+    d[S p + q] = fmaf(q / S, c[p+1] - c[p], c[p]), the difference rounded to fp32 first, q = 0 giving c[p] itself."""
+    c = np.asarray(coarse, dtype=np.float32)
+    K, n = warp_knots(length), warp_coarse_knots(length, knot_stride)
+    if c.ndim not in (1, 2) or c.shape[-1] != n:
+        raise ValueError(f"coarse has shape {c.shape}: ({n},) or (B, {n}) = warp_coarse_knots({length}, {knot_stride}) knots")
+    j = np.arange(K)
+    p, q = j // knot_stride, j % knot_stride
+    c0 = c[..., p]
+    c1 = c[..., np.minimum(p + 1, n - 1)]                     # never used where p = P: q = 0 there
+    diff = (c1 - c0).astype(np.float32)
+    fine = ((q / knot_stride) * diff.astype(np.float64) + c0.astype(np.float64)).astype(np.float32)
+    return np.ascontiguousarray(np.where(q == 0, c0, fine))
+
+
 def wow_curve(length, sample_rate, components=(), speed_percent=0.0):
     """The knots (warp_knots(length),) np.float32 of the delay curve, in samples, of a transport that runs `speed_percent` off speed and
     whose speed is modulated by `components` = ((rate_hz, depth_percent, phase_deg), ...) (phase optional) -- wow below about 6 Hz,

@@ -1043,6 +1043,166 @@ class TimeWarpOperator(_MelOperator):
         return ops.hip.warp_fwd(x, d, int(length)), adjoint
 
 
+class BlindTimeWarpOperator(_MelOperator):
+    """Wow and flutter with an UNKNOWN delay curve (extension): the operator of `TimeWarpOperator` with one curve estimate per clip fitted
+    inside the guided loop, the way `BlindEqualizationOperator` fits its gain curve (csrc/warp_fit.hip).
+
+    The estimate lives on coarse knots c[0 .. P] (`warp_estimate`, (B, P + 1) fp32 on the GPU), one every S = `knot_stride` fine knots, P + 1
+    = dsp.warp_coarse_knots(L, S); the fine curve the kernels of section 8.10 read (`delay_estimate`, (B, H + 1)) is its linear
+    interpolation, `dsp.warp_expand`.  The coarse grid is the regulariser: one knot per 64 S samples.  One `guidance` call computes the loss
+    and the gradient w.r.t. the audio with the current fine curve (`warp_fwd`, `warp_bwd`), then `warp_wgrad` turns the same cotangent into
+    the gradient in the knots and `warp_update` takes one Adam step on c, subtracts the mean of the knots (anchor="mean": a constant delay
+    is a shift of x, which the prior cannot tell apart), clamps every knot to +-max_delay and expands: two launches, no host sync.  A clip
+    whose gradient or step is not finite keeps its state.  max_delay <= min(4096, 8 S) keeps every curve the update writes inside the
+    contract of `warp_bwd` (|c| <= M gives fine steps of at most 2 M / S <= 16), so no slope projection is needed.
+
+    lr is in samples per step (Adam moves a knot by about lr per step); the default is a caller's knob, not a tuned value.
+    forward(data, delay=None) makes the measurement with the TRUE fine curve ((H + 1,) or (B, H + 1), `dsp.wow_curve` builds one) and keeps
+    it as `true_delay`.  init: "zero" or a coarse curve (P + 1,) / (B, P + 1), finite and within +-max_delay, mean-subtracted per row under
+    anchor="mean".  The state is made on first use and again when the batch, length or device changes; reset_cache() (every
+    `set_timesteps`) and restart() (NaN-retry) put it back, so two identical pipeline calls give the same bits.
+    `guidance(..., update_warp=False)` freezes the estimate; `delay=` (fine knots) pins the curve of one call and never updates.
+
+    The curve is piecewise linear on 64 S-sample knots and boxed to +-8 S samples; a constant delay is not identified under
+    anchor="mean"; the fit needs band-limited content (the gradient runs through a cubic's derivative of x).  The state is indexed by batch
+    position, so the pipelines refuse `lanes > 1` and `shard=True`.  dead_span stays None.  k, the count of updates since the last reset,
+    is kept on the host and shared by the clips."""
+
+    def __init__(self, sample_rate=16000, noiser=None, knot_stride=16, max_delay=128.0, lr=0.1, betas=(0.9, 0.999), adam_eps=1e-8, init="zero",
+                 anchor="mean"):
+        if not (math.isfinite(float(sample_rate)) and float(sample_rate) > 0):
+            raise ValueError(f"sample_rate = {sample_rate!r}: a positive finite rate")
+        if isinstance(knot_stride, bool) or knot_stride not in dsp.WARP_KNOT_STRIDES:
+            raise ValueError(f"knot_stride = {knot_stride!r}: a power of two from 1 to 64 (fine knots per coarse knot)")
+        box = min(dsp.WARP_MAX_DELAY, 8.0 * knot_stride)
+        if not (isinstance(max_delay, (int, float)) and math.isfinite(max_delay) and 0 < max_delay <= box):
+            raise ValueError(f"max_delay = {max_delay!r}: positive and at most min(4096, 8 * knot_stride) = {box:g} samples, which keeps every "
+                             "fitted curve inside the contract of the transpose (fine steps of at most 16)")
+        if not (isinstance(lr, (int, float)) and math.isfinite(lr) and lr > 0):
+            raise ValueError(f"lr = {lr!r}: a positive number (samples per step)")
+        if len(betas) != 2 or not all(isinstance(b, (int, float)) and 0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"betas = {betas!r}: two numbers in [0, 1)")
+        if not (isinstance(adam_eps, (int, float)) and math.isfinite(adam_eps) and adam_eps >= 0):
+            raise ValueError(f"adam_eps = {adam_eps!r}: a non-negative number")
+        if anchor not in ("mean", "none"):
+            raise ValueError(f"anchor = {anchor!r}: 'mean' or 'none'")
+        self.sample_rate, self.noiser, self.anchor = sample_rate, noiser, anchor
+        self.knot_stride, self.max_delay = int(knot_stride), float(np.float32(max_delay))
+        self.lr, self.betas, self.adam_eps = float(lr), (float(betas[0]), float(betas[1])), float(adam_eps)
+        if isinstance(init, str):
+            if init != "zero":
+                raise ValueError(f"init = {init!r}: 'zero' or a coarse curve (P + 1,) / (B, P + 1)")
+            start = None
+        else:
+            start = torch.as_tensor(init, dtype=torch.float32).detach().cpu()
+            if start.dim() not in (1, 2) or start.shape[-1] < 2 or start.numel() == 0:
+                raise ValueError(f"init has shape {tuple(start.shape)}: (P + 1,) or (B, P + 1) coarse knots")
+            start = start.reshape(-1, start.shape[-1]).clone()
+            if not bool(torch.isfinite(start).all()) or float(start.abs().max()) > self.max_delay:
+                raise ValueError(f"init: finite knots within +-max_delay = {self.max_delay:g} samples")
+            if anchor == "mean":
+                start = (start - start.mean(dim=1, keepdim=True)).clamp_(-self.max_delay, self.max_delay)
+        self._start = start                                   # host, None (zeros), (1, P + 1) for every clip or (B, P + 1)
+        self.true_delay = None
+        self._c = self._m = self._v = self._d = None
+        self._length = None
+        self.k = 0
+        self._init_mel(sample_rate, lazy=True)
+
+    # ---- the estimate and its optimiser state
+    def _start_rows(self, batch, length):
+        """host (batch, P + 1) fp32: the coarse curve every trajectory starts from"""
+        n = dsp.warp_coarse_knots(length, self.knot_stride)
+        if self._start is None:
+            return torch.zeros(batch, n)
+        if self._start.shape[1] != n or self._start.shape[0] not in (1, batch):
+            raise ValueError(f"init holds {self._start.shape[0]} coarse curve(s) of {self._start.shape[1]} knots; a batch of {batch} clip(s) of "
+                             f"{length} samples needs (1 or {batch}) x warp_coarse_knots({length}, {self.knot_stride}) = {n}")
+        return self._start.expand(batch, n)
+
+    def _fill(self, batch, length):
+        start = self._start_rows(batch, length)
+        self._c.copy_(start)
+        self._d.copy_(torch.from_numpy(dsp.warp_expand(start.numpy(), length, self.knot_stride)))
+        self._m.zero_()
+        self._v.zero_()
+        self.k = 0
+
+    def _state(self, batch, length, device):
+        """The estimate with its Adam moments and fine curve on `device`; made on first use and when the batch, length or device changes."""
+        if self._c is None or self._c.shape[0] != batch or self._length != length or self._c.device != device:
+            n = dsp.warp_coarse_knots(length, self.knot_stride)
+            self._start_rows(batch, length)                   # refuses a mismatched init before anything is allocated
+            self._c, self._m, self._v = (torch.empty(batch, n, dtype=torch.float32, device=device) for _ in range(3))
+            self._d = torch.empty(batch, dsp.warp_knots(length), dtype=torch.float32, device=device)
+            self._length = length
+            self._fill(batch, length)
+        return self._d
+
+    @property
+    def warp_estimate(self):
+        """(B, P + 1) fp32 coarse knots on the GPU, updated in place by every guided step; None before the first call."""
+        return self._c
+
+    @property
+    def delay_estimate(self):
+        """(B, H + 1) fp32 fine knots on the GPU: `dsp.warp_expand` of `warp_estimate`, what `warp_fwd` / `warp_bwd` read."""
+        return self._d
+
+    def _to_start(self):
+        if self._c is not None:
+            self._fill(self._c.shape[0], self._length)
+        self.k = 0
+
+    def reset_cache(self):
+        super().reset_cache()
+        self._to_start()
+
+    def restart(self):
+        self._to_start()
+
+    # ---- A
+    def _fine_rows(self, delay, batch, length, what):
+        """(H + 1,) / (1, H + 1) / (batch, H + 1) fine knots -> host (batch, H + 1) fp32, the contract checked by name"""
+        d = torch.as_tensor(delay).detach().to(device="cpu", dtype=torch.float32).contiguous()
+        dsp.check_warp_curve(d.numpy(), what)
+        K = dsp.warp_knots(length)
+        d = d.reshape(-1, d.shape[-1])
+        if d.shape[1] != K or d.shape[0] not in (1, batch):
+            raise ValueError(f"{what} has shape {tuple(d.shape)}: a batch of {batch} clip(s) of {length} samples needs (warp_knots({length}),) = "
+                             f"({K},) or ({batch}, {K})")
+        return d.expand(batch, K)
+
+    def forward(self, data, delay=None, **kwargs):
+        B, L = data.shape[0], data.shape[-1]
+        if delay is None:
+            if self.true_delay is None:
+                raise ValueError("BlindTimeWarpOperator.forward needs the true delay curve of the measurement: delay=(warp_knots(length),) or "
+                                 "(B, warp_knots(length)) fine knots (dsp.wow_curve builds one); none was given and none is kept")
+            delay = self._fine_rows(self.true_delay, B, L, "true_delay")
+        else:
+            delay = self.true_delay = self._fine_rows(delay, B, L, "delay").clone()
+        return super().forward(data, delay=delay, **kwargs)
+
+    def apply(self, x, length, delay=None, update_warp=True, **kw):
+        """delay: the fine curve(s) of this call instead of the estimate; the estimate is then neither used nor updated."""
+        B = x.shape[0]
+        d = self._state(B, int(length), x.device) if delay is None else self._fine_rows(delay, B, int(length), "delay").to(x.device).contiguous()
+
+        def adjoint(dy, full):
+            return ops.hip.warp_bwd(dy.contiguous(), d, int(length), int(full))
+        return ops.hip.warp_fwd(x, d, int(length)), adjoint
+
+    def after_cotangent(self, x, length, dy, delay=None, update_warp=True, **kw):
+        """c_k -> c_{k+1}: the knot gradient of this step's cotangent and one Adam + projection step, two launches, no host sync."""
+        if delay is not None or not update_warp:
+            return
+        part = ops.hip.warp_wgrad(dy.contiguous(), x, self._d, int(length))
+        self.k += 1
+        ops.hip.warp_update(part, self._c, self._m, self._v, self._d, int(length), self.knot_stride, self.k, self.lr, self.betas[0],
+                            self.betas[1], self.adam_eps, self.max_delay, self.anchor == "mean")
+
+
 class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 (unrunnable in the reference: run.py:213-214)
     """Style guidance with BUILD-DEFINED semantics (the reference's `clap_model.get_gram_matrix`
     does not exist anywhere): `forward(x) = noiser(x)` (identity, operator.py:270-271) and

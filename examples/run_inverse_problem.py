@@ -39,6 +39,11 @@ given takes its value from configs/inverse_problem/music_decompression.yaml.
 a flag that is not given takes its value from configs/inverse_problem/music_wow_flutter.yaml.  The curve is built for the clip's length,
 in track mode for the track's.
 
+`-t music_blind_wow_flutter` measures through the same kind of curve, which the restoration does not know (BlindTimeWarpOperator fits it
+inside the guided loop): `--wow` / `--speed_pct` build the TRUE curve of the synthetic measurement, `--warp_knot_stride S` (fine knots
+per coarse knot of the estimate, a power of two up to 64), `--warp_max_delay M` (samples, at most min(4096, 8 S)) and `--warp_lr`
+(samples per step) shape the fit; a flag that is not given takes its value from configs/inverse_problem/music_blind_wow_flutter.yaml.
+
 `-t music_source_separation` restores K stems from their mixture under one loss (inverse_problem/mixture.py), one prompt embedding per
 stem: `--wav` names the stems whose gain-weighted sum (`--gains`) is the measurement (SI-SDR per stem is printed), `--mixture mix.wav
 --stems K` separates a real mixture.  One file per stem is written; `--project` makes the stems sum to the mixture exactly.
@@ -62,22 +67,25 @@ from diffmusic_amd.schedulers import get_scheduler                              
 
 TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation", "music_declipping",
          "music_blind_dereverberation", "music_source_separation", "music_spectral_inpainting", "music_blind_equalization", "music_decompression",
-         "music_wow_flutter")
+         "music_wow_flutter", "music_blind_wow_flutter")
 SEPARATION = "music_source_separation"
 SPECTRAL = "music_spectral_inpainting"
 BLIND_EQ = "music_blind_equalization"
 DECOMPRESSION = "music_decompression"
 WOW_FLUTTER = "music_wow_flutter"
+BLIND_WOW = "music_blind_wow_flutter"
 DRC_FLAGS = ("threshold_db", "ratio", "knee_db", "attack_ms", "release_ms", "makeup_db")
 
 
-def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None, tf_boxes=None, eq_true=None, drc=None, warp=None):
+def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None, tf_boxes=None, eq_true=None, drc=None, warp=None,
+                   blind_warp=None):
     """run.py:157-212: one operator per task, constructor arguments from the data / model config.  `audio_length_in_s`: the length the
     operator acts on when it is not the model window (a track).  `clip_threshold`: music_declipping's threshold(s), a float or one value
     per clip (`threshold_for_sdr` of the clean clips).  `tf_boxes`: music_spectral_inpainting's boxes (`spectral_boxes`).  `eq_true`:
     music_blind_equalization's true curve (`equalization_curve`), kept on the operator for `forward`.  `drc`: music_decompression's
     parameters (`compressor_params`).  `warp`: music_wow_flutter's speed components (`warp_params`); the delay curve is built here, for the
-    length the operator acts on."""
+    length the operator acts on.  `blind_warp`: music_blind_wow_flutter's fit options (`blind_warp_params`); `warp` then describes the TRUE
+    curve, kept on the operator for `forward`."""
     noiser = P.get_noiser(**cfg.inverse_problem.noise)
     d, scale = cfg.data, 1
     seconds = cfg.model.pipe.audio_length_in_s if audio_length_in_s is None else audio_length_in_s
@@ -122,6 +130,14 @@ def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=
             raise ValueError("music_wow_flutter needs warp (warp_params(args, cfg))")
         curve = P.wow_curve(int(seconds * d.sample_rate), d.sample_rate, **warp)
         op = P.TimeWarpOperator(sample_rate=d.sample_rate, delay=curve, noiser=noiser)
+    elif task == BLIND_WOW:
+        if warp is None or blind_warp is None:
+            raise ValueError("music_blind_wow_flutter needs warp (warp_params(args, cfg)) and blind_warp (blind_warp_params(args, cfg))")
+        ip = cfg.inverse_problem
+        op = P.BlindTimeWarpOperator(sample_rate=d.sample_rate, noiser=noiser, betas=tuple(ip.get("betas") or (0.9, 0.999)),
+                                     adam_eps=float(ip.get("adam_eps") or 1e-8), init=ip.get("init") or "zero",
+                                     anchor=ip.get("anchor") or "mean", **blind_warp)
+        op.true_delay = torch.from_numpy(P.wow_curve(int(seconds * d.sample_rate), d.sample_rate, **warp)).reshape(1, -1)
     else:
         raise ValueError(f"Unknown task: {task}")
     return op, scale
@@ -208,6 +224,11 @@ def parse_args(argv=None):
     ap.add_argument("--wow", action="append", default=None, metavar="RATE_HZ,DEPTH_PCT[,PHASE_DEG]",
                     help="music_wow_flutter: one speed-modulation component (repeatable; default: the task's config)")
     ap.add_argument("--speed_pct", type=float, default=None, help="music_wow_flutter: constant speed error in percent (default: the task's config)")
+    ap.add_argument("--warp_knot_stride", type=int, default=None,
+                    help="music_blind_wow_flutter: fine knots per coarse knot of the estimate, a power of two up to 64 (default: the task's config)")
+    ap.add_argument("--warp_max_delay", type=float, default=None,
+                    help="music_blind_wow_flutter: the clamp of every knot in samples, at most min(4096, 8 * knot_stride) (default: the task's config)")
+    ap.add_argument("--warp_lr", type=float, default=None, help="music_blind_wow_flutter: Adam step of the curve in samples (default: the task's config)")
     ap.add_argument("--strength", type=float, default=1.0, help="share of num_inference_steps a warm start runs (diffusers' img2img rule)")
     return ap.parse_args(argv)
 
@@ -333,12 +354,12 @@ def compressor_params(args, cfg=None):
 
 
 def warp_params(args, cfg=None, length=16000, sample_rate=16000):
-    """The argument rules of -t music_wow_flutter -> the keyword arguments of `wow_curve`: `components` from every --wow flag (the config's
+    """The argument rules of -t music_wow_flutter (and of -t music_blind_wow_flutter, whose TRUE curve they build) -> the keyword arguments of `wow_curve`: `components` from every --wow flag (the config's
     `wow` list without one) and `speed_percent` from --speed_pct (the config's `speed_pct`).  A curve for `length` samples is built once
     here so that `wow_curve`'s own refusals come before any GPU work.  Any other task refuses the flags."""
-    if args.task != WOW_FLUTTER:
+    if args.task not in (WOW_FLUTTER, BLIND_WOW):
         if args.wow is not None or args.speed_pct is not None:
-            raise SystemExit(f"--{'wow' if args.wow is not None else 'speed_pct'} belongs to -t {WOW_FLUTTER}")
+            raise SystemExit(f"--{'wow' if args.wow is not None else 'speed_pct'} belongs to -t {WOW_FLUTTER} and -t {BLIND_WOW}")
         return None
     ip = cfg.inverse_problem if cfg is not None else {}
     if args.wow is not None:
@@ -358,7 +379,32 @@ def warp_params(args, cfg=None, length=16000, sample_rate=16000):
     try:
         P.wow_curve(length, sample_rate, **out)
     except ValueError as e:
-        raise SystemExit(f"-t {WOW_FLUTTER}: {e}")
+        raise SystemExit(f"-t {args.task}: {e}")
+    return out
+
+
+def blind_warp_params(args, cfg=None):
+    """The argument rules of -t music_blind_wow_flutter -> the keyword arguments `knot_stride`, `max_delay` and `lr` of the
+    BlindTimeWarpOperator: each from its --warp_* flag, else from the task's config, else the operator's default.  The operator's own
+    refusals (a stride that is no power of two up to 64, max_delay above min(4096, 8 * knot_stride)) come here, before any GPU work.  Any
+    other task refuses the flags."""
+    flags = dict(knot_stride=args.warp_knot_stride, max_delay=args.warp_max_delay, lr=args.warp_lr)
+    if args.task != BLIND_WOW:
+        for name, v in flags.items():
+            if v is not None:
+                raise SystemExit(f"--warp_{name} belongs to -t {BLIND_WOW}")
+        return None
+    ip = cfg.inverse_problem if cfg is not None else {}
+    out = dict(knot_stride=16, max_delay=128.0, lr=0.1)
+    for name, v in flags.items():
+        if v is None:
+            v = ip.get(name)
+        if v is not None:
+            out[name] = int(v) if name == "knot_stride" else float(v)
+    try:
+        P.BlindTimeWarpOperator(**out)
+    except ValueError as e:
+        raise SystemExit(f"-t {BLIND_WOW}: {e}")
     return out
 
 
@@ -450,7 +496,7 @@ def run_separation(args, cfg, K):
 def main(argv=None):
     args = parse_args(argv)
     overrides = [f"data={args.data}", f"model={args.model}"]
-    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL, BLIND_EQ, DECOMPRESSION, WOW_FLUTTER):
+    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL, BLIND_EQ, DECOMPRESSION, WOW_FLUTTER, BLIND_WOW):
         overrides.append(f"inverse_problem={args.task}")
     stems = separation_stems(args)
     if args.project and args.task not in ("music_declipping", SEPARATION):
@@ -460,6 +506,7 @@ def main(argv=None):
     eq_true = equalization_curve(args, cfg)
     drc = compressor_params(args, cfg)
     warp = warp_params(args, cfg, length=int(cfg.model.pipe.audio_length_in_s * cfg.data.sample_rate), sample_rate=cfg.data.sample_rate)
+    blind_warp = blind_warp_params(args, cfg)
     if stems is not None:
         if args.model != "musicldm":
             raise SystemExit("this driver feeds MusicLDM's class-embedding conditioning; AudioLDM2 needs its T5 / GPT-2 states (see bench.py --workload)")
@@ -476,7 +523,8 @@ def main(argv=None):
     if args.track_overlap_s is None:
         gt = load_clips(args.wav, args.batch, sr, length, args.seed).to(device)
         thr = P.threshold_for_sdr(gt, args.clip_sdr_db) if args.task == "music_declipping" else None
-        op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr, tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp)
+        op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr, tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp,
+                                   blind_warp=blind_warp)
         B = gt.shape[0]
     else:
         if args.task == "music_generation":
@@ -486,7 +534,7 @@ def main(argv=None):
         layout = P.TrackLayout(T, length, int(round(args.track_overlap_s * sr)))
         thr = float(P.threshold_for_sdr(gt, args.clip_sdr_db)[0]) if args.task == "music_declipping" else None
         inner, scale = build_operator(args.task, cfg, args.mask_type, audio_length_in_s=P.seconds_for_samples(T, sr), clip_threshold=thr,
-                                      tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp)
+                                      tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp, blind_warp=blind_warp)
         op = P.TrackOperator(inner, layout)
         B = layout.num_windows
         sched_kw["per_clip_norm"] = False                                          # one loss, norms over all windows
@@ -532,6 +580,11 @@ def main(argv=None):
         est, true = blind.eq_estimate.cpu(), blind.true_curve                      # the synthetic measurement knows its curve
         err = torch.linalg.vector_norm(est - true, dim=1) / torch.linalg.vector_norm(true, dim=1)
         print("equalisation curve estimate, relative error per clip: " + " ".join(f"{e:.3f}" for e in err.tolist()))
+    if isinstance(blind, P.BlindTimeWarpOperator) and blind.true_delay is not None and blind.delay_estimate is not None:
+        est, true = blind.delay_estimate.cpu(), blind.true_delay                   # the synthetic measurement knows its curve
+        true = true - true.mean(dim=1, keepdim=True) if blind.anchor == "mean" else true      # a constant delay is not identified
+        err = torch.linalg.vector_norm(est - true, dim=1) / torch.linalg.vector_norm(true, dim=1).clamp_min(1e-30)
+        print("delay curve estimate, relative error per clip (mean removed): " + " ".join(f"{e:.3f}" for e in err.tolist()))
     ref = gt.cpu().numpy()
     print(f"wrote {B} clip(s) to {out}; LSD {LogSpectralDistance().score(ref, audio[:, :length]):.4f}  MSE {MeanSquaredError().score(ref, audio[:, :length]):.6f}")
 

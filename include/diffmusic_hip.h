@@ -36,7 +36,7 @@ extern "C" {
  * dmx_audio_tf_frames (time-frequency masking: a real gain on the STFT) and dmx_audio_tf_curve / dmx_audio_tf_wgrad /
  * dmx_audio_tf_wgrad_segments / dmx_audio_eq_update (blind equalisation: a fitted gain curve per clip) and dmx_drc_fwd / dmx_drc_bwd
  * (de-compression: a dynamic-range compressor and the transpose of its Jacobian) and dmx_warp_fwd / dmx_warp_bwd (wow and flutter: a clip
- * read along a delay curve, and the transpose) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * read along a delay curve, and the transpose) and dmx_warp_wgrad / dmx_warp_update (blind wow and flutter: the delay curve fitted) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
  * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
@@ -295,6 +295,27 @@ int dmx_drc_bwd(const float* dy, long long dy_stride, const float* x, long long 
  * or a delay stride that is neither 0 nor at least H + 1. */
 int dmx_warp_fwd(const float* x, long long x_stride, const float* delay, long long delay_stride, float* y, int batch, int L, void* stream);
 int dmx_warp_bwd(const float* dy, const float* delay, long long delay_stride, float* dx, int batch, int L, int full, void* stream);
+/* Blind wow and flutter (csrc/warp_fit.hip): the delay curve of dmx_warp_fwd fitted inside the guided loop.  The
+ * estimate lives on coarse knots c[0 .. P], one every S = knot_stride fine knots (S a power of two in 1 .. 64, P = ceil(H / S)); the fine
+ * curve is d[S p + q] = fmaf(q / S, c[p+1] - c[p], c[p]).
+ *   warp_wgrad   from the cotangent dy = dLoss/dy (batch, L) contiguous at y = A_d x and x (batch, >= L): g[n] = dy[n] sum_k w'[k](f(n))
+ *                x[i(n) + k], w' the derivatives of the Catmull-Rom weights, out-of-clip taps skipped, NaN where delta(n) is not finite;
+ *                part[b, j, 0] = sum_r (1 - r / 64) g[64 j + r], part[b, j, 1] = sum_r (r / 64) g[64 j + r] over n < L, part (batch, H, 2)
+ *                contiguous.  The gradient in the fine knots is dd[j] = part[j, 0] + part[j - 1, 1].  No atomics, a fixed butterfly order:
+ *                the same bits on every call, whatever the batch and the clip's place in it; other clips never see a clip's NaN.
+ *   warp_update  dc[p] = sum over j ascending with |j - S p| < S, 0 <= j <= H of (1 - |j - S p| / S) dd[j]; Adam on (c, m, v) with the
+ *                arithmetic of dmx_ir_update (csrc/adam_step.h), k the 1-based count of updates; anchor = 1 ("mean") subtracts the mean of
+ *                the stepped knots, anchor = 0 ("none") does not; every knot is clamped to +-max_delay; c, m, v (batch, P + 1) and the
+ *                expanded fine curve (batch, H + 1) are written in place.  A clip with a non-finite dc[p], stepped knot or mean keeps all
+ *                four untouched (decided on the device).  0 < max_delay <= min(4096, 8 knot_stride) keeps every written curve inside the
+ *                contract of dmx_warp_bwd.
+ * One launch each.  DMX_ERR_SHAPE, with nothing written, for a null pointer, batch < 1 (wgrad: outside 1 .. 65535), L outside 1 .. 2^30,
+ * x_stride < L, a delay stride that is neither 0 nor at least H + 1, a knot_stride that is no power of two in 1 .. 64, k < 1, lr <= 0, a
+ * beta outside [0, 1), eps < 0, max_delay outside its range, an anchor other than 0 or 1. */
+int dmx_warp_wgrad(const float* dy, const float* x, long long x_stride, const float* delay, long long delay_stride, float* part, int batch,
+                   int L, void* stream);
+int dmx_warp_update(const float* part, float* coarse, float* m, float* v, float* fine, int batch, int L, int knot_stride, int k, double lr,
+                    double beta1, double beta2, double eps, double max_delay, int anchor, void* stream);
 /* out[i] = y[i] + scale * z[i], i < n (the noiser on a materialised measurement A(x): super-resolution, dereverberation, wav_form) */
 int dmx_noise_add(const float* y, const float* z, float* out, long long n, float scale, void* stream);
 /* PhaseRetrievalOperator.forward: |torch.stft(wav)| as (B, n_fft/2+1, frames) fp32 */
