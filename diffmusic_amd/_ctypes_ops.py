@@ -296,6 +296,95 @@ def drc_bwd(dy, x, state, tape, Lfull, threshold_db, slope, knee_db, a_att, a_re
     return d
 
 
+def _drc_table(who, theta, B, like):
+    assert theta.is_cuda and theta.device == like.device and theta.dtype == torch.float32 and theta.is_contiguous() and \
+        tuple(theta.shape) == (B, 8), (who, tuple(theta.shape), (B, 8))
+
+
+def _drc_tape(who, state, tape, B, H, like):
+    assert state.is_cuda and state.device == like.device and state.dtype == torch.float32 and state.is_contiguous() and \
+        tuple(state.shape) == (B, 3, H), (who, tuple(state.shape), (B, 3, H))
+    assert tape.is_cuda and tape.device == like.device and tape.dtype == torch.uint8 and tape.is_contiguous() and tuple(tape.shape) == (B, H), \
+        (who, tuple(tape.shape), (B, H))
+
+
+def drc_fwd_p(x, L, theta, knee_db):
+    """`drc_fwd` with the parameters of clip b read from theta[b] on the device: theta (B, 8) fp32, rows T, k, makeup, aA, aR, 1 - aA, 1 - aR,
+    k / (2 knee_db) (`dsp.drc_table` builds one).  -> (y, state, tape) as `drc_fwd`, bit-equal to it on a table of equal rows."""
+    if not x.is_cuda:
+        raise RuntimeError("drc_fwd_p: tensors must be on the GPU (no CPU fallback)")
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] >= L >= 1, ("drc_fwd_p", x.shape, L)
+    B, H = x.shape[0], -(-L // 64)
+    _drc_table("drc_fwd_p", theta, B, x)
+    y = torch.empty(B, L, dtype=torch.float32, device=x.device)
+    state = torch.empty(B, 3, H, dtype=torch.float32, device=x.device)
+    tape = torch.empty(B, H, dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.lib().dmx_drc_fwd_p(_p(x), x.stride(0), _p(y), L, _p(state), _p(tape), _p(theta), min(B, 65536), L, knee_db, _stream()),
+               "drc_fwd_p")
+    return y, state, tape
+
+
+def drc_bwd_p(dy, x, state, tape, theta, Lfull, knee_db):
+    """`drc_bwd` with the table of `drc_fwd_p` -> (dx (B, Lfull), work (B, 2, H): rows ds and dc, bq0 (B,): Bq[0] of each clip) -- what
+    `drc_pgrad` needs besides the state and the tape."""
+    if not dy.is_cuda:
+        raise RuntimeError("drc_bwd_p: tensors must be on the GPU (no CPU fallback)")
+    assert dy.dtype == torch.float32 and dy.dim() == 2 and dy.stride(1) == 1 and Lfull >= dy.shape[1] >= 1, ("drc_bwd_p", dy.shape, Lfull)
+    B, L = dy.shape
+    H = -(-L // 64)
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == B and x.shape[1] >= L and \
+        x.device == dy.device, ("drc_bwd_p", x.shape, dy.shape)
+    _drc_tape("drc_bwd_p", state, tape, B, H, dy)
+    _drc_table("drc_bwd_p", theta, B, dy)
+    work = torch.empty(B, 2, H, dtype=torch.float32, device=dy.device)
+    bq0 = torch.empty(B, dtype=torch.float32, device=dy.device)
+    d = torch.empty(B, Lfull, dtype=torch.float32, device=dy.device)
+    _lib.check(_lib.lib().dmx_drc_bwd_p(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(state), _p(tape), _p(theta), _p(work), _p(bq0), _p(d), Lfull,
+                                        min(B, 65536), L, Lfull, knee_db, _stream()), "drc_bwd_p")
+    return d, work, bq0
+
+
+def drc_pgrad(state, tape, work, bq0, theta, L, knee_db):
+    """state and tape of `drc_fwd_p`, work and bq0 of `drc_bwd_p` -> part (B, ceil(H / 256), 5): the gradient of the loss in (T, k, makeup,
+    ln aA, ln aR) as one row per segment of 256 blocks; the gradient is the sum over the segments (csrc/drc_fit.hip)."""
+    if not work.is_cuda:
+        raise RuntimeError("drc_pgrad: tensors must be on the GPU (no CPU fallback)")
+    assert 1 <= L <= 1 << 30, ("drc_pgrad", L)
+    H = -(-L // 64)
+    assert work.dtype == torch.float32 and work.dim() == 3 and work.is_contiguous() and work.shape[0] >= 1 and tuple(work.shape[1:]) == (2, H), \
+        ("drc_pgrad", tuple(work.shape), (2, H))
+    B = work.shape[0]
+    _drc_tape("drc_pgrad", state, tape, B, H, work)
+    _drc_table("drc_pgrad", theta, B, work)
+    assert bq0.is_cuda and bq0.device == work.device and bq0.dtype == torch.float32 and bq0.is_contiguous() and tuple(bq0.shape) == (B,), \
+        ("drc_pgrad", tuple(bq0.shape), (B,))
+    part = torch.empty(B, -(-H // 256), 5, dtype=torch.float32, device=work.device)
+    _lib.check(_lib.lib().dmx_drc_pgrad(_p(state), _p(tape), _p(work), _p(bq0), _p(theta), _p(part), min(B, 65536), L, knee_db, _stream()),
+               "drc_pgrad")
+    return part
+
+
+def drc_update(part, phi, m, v, theta, L, k, lr, beta1, beta2, eps, knee_db, lo, hi):
+    """One Adam step per parameter on phi = (T, k, makeup, ln aA, ln aR) from the rows of `drc_pgrad`, with its own lr[q] (0 freezes it), the
+    clamp to [lo[q], hi[q]] and the clip's new row of theta; phi, m, v (B, 5) and theta (B, 8) are updated IN PLACE, k the 1-based count of
+    updates since the last reset.  A clip whose gradient or step is not finite keeps its state."""
+    if not part.is_cuda:
+        raise RuntimeError("drc_update: tensors must be on the GPU (no CPU fallback)")
+    assert 1 <= L <= 1 << 30 and len(lr) == 5 and len(lo) == 5 and len(hi) == 5, ("drc_update", L, lr, lo, hi)
+    H = -(-L // 64)
+    assert part.dtype == torch.float32 and part.dim() == 3 and part.is_contiguous() and part.shape[0] >= 1 and \
+        tuple(part.shape[1:]) == (-(-H // 256), 5), ("drc_update", tuple(part.shape), (-(-H // 256), 5))
+    B = part.shape[0]
+    for t in (phi, m, v):
+        assert t.is_cuda and t.device == part.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, 5), \
+            ("drc_update", tuple(t.shape), (B, 5))
+    _drc_table("drc_update", theta, B, part)
+    five = C.c_double * 5
+    _lib.check(_lib.lib().dmx_drc_update(_p(part), _p(phi), _p(m), _p(v), _p(theta), B, L, int(k), five(*[float(a) for a in lr]), float(beta1),
+                                         float(beta2), float(eps), float(knee_db), five(*[float(a) for a in lo]),
+                                         five(*[float(a) for a in hi]), _stream()), "drc_update")
+
+
 def _warp_delay_stride(who, delay, like, B, length):
     K = -(-length // 64) + 1
     assert delay.is_cuda and delay.device == like.device and delay.dtype == torch.float32 and delay.is_contiguous() and \

@@ -171,6 +171,12 @@ _SIGS = {
                     [C.c_void_p]),
     "dmx_drc_bwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                               C.c_int, C.c_int, C.c_int] + [C.c_float] * 6 + [C.c_void_p]),
+    "dmx_drc_fwd_p": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                C.c_void_p]),
+    "dmx_drc_bwd_p": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong] + [C.c_void_p] * 6 + [C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                                                                                        C.c_float, C.c_void_p]),
+    "dmx_drc_pgrad": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "dmx_drc_update": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] + [C.c_double] * 3 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dmx_warp_fwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dmx_warp_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dmx_warp_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -218,7 +224,8 @@ ADDED_IN_V4 = ("dmx_vae_encoder_create", "dmx_vae_encoder_workspace_bytes", "dmx
                "dmx_fir_clip_fwd", "dmx_fir_clip_bwd", "dmx_fir_wgrad", "dmx_fir_wgrad_workspace_floats", "dmx_ir_update",
                "dmx_stem_mix_fwd", "dmx_stem_mix_bwd", "dmx_stem_project", "dmx_audio_tf_gain", "dmx_audio_tf_frames",
                "dmx_audio_tf_curve", "dmx_audio_tf_wgrad_segments", "dmx_audio_tf_wgrad", "dmx_audio_eq_update", "dmx_drc_fwd", "dmx_drc_bwd",
-               "dmx_warp_fwd", "dmx_warp_bwd", "dmx_warp_wgrad", "dmx_warp_update")
+               "dmx_warp_fwd", "dmx_warp_bwd", "dmx_warp_wgrad", "dmx_warp_update", "dmx_drc_fwd_p", "dmx_drc_bwd_p", "dmx_drc_pgrad",
+               "dmx_drc_update")
 
 _lib = None
 
@@ -228,7 +235,7 @@ def check_symbols(h, path=LIB_PATH):
     for name in ADDED_IN_V4:
         if not hasattr(h, name):
             raise RuntimeError(f"{path} reports ABI version {ABI_VERSION} but does not export `{name}` (a build from before the VAE "
-                               "encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter / blind-wow-and-flutter entry points): rebuild it (python -m diffmusic_amd.build --force)")
+                               "encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter / blind-wow-and-flutter / blind-de-compression entry points): rebuild it (python -m diffmusic_amd.build --force)")
 
 
 def lib():

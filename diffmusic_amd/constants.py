@@ -12,6 +12,7 @@ MUSIC_BLIND_EQUALIZATION = "music_blind_equalization"         # extension: an un
 MUSIC_DECOMPRESSION = "music_decompression"                   # extension: dynamic-range compression undone (DynamicRangeOperator)
 MUSIC_WOW_FLUTTER = "music_wow_flutter"                       # extension: a varying playback speed undone (TimeWarpOperator)
 MUSIC_BLIND_WOW_FLUTTER = "music_blind_wow_flutter"           # extension: an unknown delay curve, fitted (BlindTimeWarpOperator)
+MUSIC_BLIND_DECOMPRESSION = "music_blind_decompression"       # extension: unknown compressor settings, fitted (BlindDynamicRangeOperator)
 DDIM, DPS, MPGD, DSG, DITTO, DIFFMUSIC = "ddim", "dps", "mpgd", "dsg", "ditto", "diffmusic"
 NULL_TEXT, TAG, CLAP = "null_text", "tag", "clap"
 WAV_FORM, MEL_SPECTROGRAM = "wav_form", "mel_spectrogram"

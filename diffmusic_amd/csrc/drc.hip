@@ -21,6 +21,11 @@
 //                          dc[j] replaces ds[j] in `work`
 //             drc_apply_bwd   dp[j] = dc[j] c'[j] (10 / ln 10) / (p[j] + eps) per block in LDS (c' from the tape's region, never re-decided),
 //                          then dx = g dy + dp (2 / 64) x; zeros on [L, full)
+// Two parameter routes, one arithmetic (drc_common.h): dmx_drc_fwd / dmx_drc_bwd pass host scalars shared by the batch (ByValue);
+// dmx_drc_fwd_p / dmx_drc_bwd_p read row b of a device table theta (batch, 8) = T, k, makeup, aA, aR, 1 - aA, 1 - aR, k / (2 W) for clip b
+// (ByTable; section 8.12, the blind operator).  The power and apply-backward kernels index the row by blockIdx.y, a follower lane reads its
+// own coefficients once before the chain; the table's values are operands only, and a row with a non-finite entry makes its clip NaN from
+// block 0 on.  The table backward keeps ds beside dc (work is (batch, 2, H)) and Bq[0] of each clip for drc_fit.hip.
 // Reductions, in this order whatever the batch, the batch position or the load path: a lane adds its four terms left to right, then the
 // 16 lanes of a block add pairwise over lane distances 1, 2, 4, 8 (xor butterfly: every lane holds the same bits).  No atomics.
 // log10f and exp10f are the accurate library routines.  A NaN sample makes p, c and s NaN from its block on: the forward's outputs are NaN
@@ -31,20 +36,17 @@
 // across lanes by construction (one cache line per clip and chunk), which is what lane = clip costs at large batches.
 #include "dmx_common.h"
 #include "kernels.h"
+#include "drc_common.h"
 #include "../../include/diffmusic_hip.h"
 #include <cmath>
 void dmx_set_error(const char* fmt, ...);
 
 namespace {
 
-constexpr int R = DMX_DRC_BLOCK;      // samples per sidechain block
 constexpr int WG_BLOCKS = 16;         // blocks per workgroup of 256 threads x 4 samples
 constexpr int CHUNK = 16;             // blocks the follower prefetches ahead
-constexpr float EPS = 1e-10f;
 constexpr float C10 = 4.3429448190325175f;          // 10 / ln 10
 constexpr float NEG_LN10_20 = -0.11512925464970229f; // -(ln 10) / 20
-
-struct DrcParams { float T, k, W, halfW, kq, aA, aR, bA, bR, makeup; };
 
 __device__ __forceinline__ bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
@@ -74,15 +76,11 @@ __device__ __forceinline__ float block_sum(float v) {
   return v;
 }
 
-__device__ __forceinline__ float level_over_threshold(float p, float T) { return 10.f * log10f(p + EPS) - T; }
-__device__ __forceinline__ float block_gain(float s, float makeup) { return exp10f((makeup - s) * 0.05f); }
-
-// state (B, 3, H): rows p, G, s of a clip
-__device__ __forceinline__ float* state_row(float* state, int b, int H, int row) { return state + ((size_t)b * 3 + row) * H; }
-__device__ __forceinline__ const float* state_row(const float* state, int b, int H, int row) { return state + ((size_t)b * 3 + row) * H; }
-
+// Every kernel that reads a parameter is a template on its source (drc_common.h): ByValue is the host-scalar route of dmx_drc_fwd /
+// dmx_drc_bwd, ByTable the per-clip device table of dmx_drc_fwd_p / dmx_drc_bwd_p.  The arithmetic is one text for both.
+template <class Src>
 __global__ __launch_bounds__(256) void drc_power_kernel(const float* __restrict__ x, long long xs, float* __restrict__ state,
-                                                        unsigned char* __restrict__ tape, int L, int H, DrcParams P) {
+                                                        unsigned char* __restrict__ tape, int L, int H, Src src) {
   const int b = blockIdx.y;
   const long long i = 4ll * (blockIdx.x * 256 + threadIdx.x);
   const float* xr = x + (long long)b * xs;
@@ -94,12 +92,11 @@ __global__ __launch_bounds__(256) void drc_power_kernel(const float* __restrict_
   q = block_sum(q);
   const int j = (int)(i / R);
   if ((threadIdx.x & 15) != 0 || j >= H) return;
+  const DrcParams P = src.clip(b);
   const float p = q * (1.f / R);
   const float d = level_over_threshold(p, P.T);
-  int rg = 2;
-  float c = P.k * d;
-  if (2.f * d < -P.W) { rg = 0; c = 0.f; }
-  else if (2.f * d <= P.W) { rg = 1; const float t = d + P.halfW; c = P.kq * t * t; }
+  float c;
+  const int rg = curve_decide(d, P, c);
   state_row(state, b, H, 0)[j] = p;
   state_row(state, b, H, 2)[j] = c;                        // the follower replaces it by s[j]
   tape[(size_t)b * H + j] = (unsigned char)rg;
@@ -132,10 +129,12 @@ __device__ __forceinline__ float follow_steps(float* srow, unsigned char* trow, 
   return s;
 }
 
-__global__ __launch_bounds__(64) void drc_follow_kernel(float* __restrict__ state, unsigned char* __restrict__ tape, int B, int H, float aA,
-                                                        float aR) {
+template <class Src>
+__global__ __launch_bounds__(64) void drc_follow_kernel(float* __restrict__ state, unsigned char* __restrict__ tape, int B, int H, Src src) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
+  float aA, aR;
+  src.follower(b, aA, aR);                                 // once, before the chain
   float* srow = state_row(state, b, H, 2);
   unsigned char* trow = tape + (size_t)b * H;
   const int whole = H / CHUNK;
@@ -155,12 +154,14 @@ __global__ __launch_bounds__(64) void drc_follow_kernel(float* __restrict__ stat
   }
 }
 
+template <class Src>
 __global__ __launch_bounds__(256) void drc_apply_kernel(const float* __restrict__ x, long long xs, float* __restrict__ y, long long ys,
-                                                        float* __restrict__ state, int L, int H, float makeup) {
+                                                        float* __restrict__ state, int L, int H, Src src) {
   __shared__ float Gs[WG_BLOCKS + 1];
   const int b = blockIdx.y, tid = threadIdx.x, j0 = blockIdx.x * WG_BLOCKS;
   if (tid <= WG_BLOCKS) {
     const int j = j0 - 1 + tid;
+    const float makeup = src.makeup(b);
     float g = 0.f;
     if (j < H) {
       g = block_gain(j < 0 ? 0.f : state_row(state, b, H, 2)[j], makeup);
@@ -198,8 +199,14 @@ __device__ __forceinline__ void weighted_sums(const float* gr, bool gvec, const 
   Bq = block_sum(c);
 }
 
+// KEEP (the table route, for drc_fit.hip): a clip's work is two rows, ds and dc, and Bq[0] of the clip goes to bq0[b]
+template <bool KEEP>
+__device__ __forceinline__ size_t work_row(int b, int H) { return (size_t)b * H * (KEEP ? 2 : 1); }
+
+template <bool KEEP>
 __global__ __launch_bounds__(256) void drc_dgain_kernel(const float* __restrict__ dy, long long dys, const float* __restrict__ x, long long xs,
-                                                        const float* __restrict__ state, float* __restrict__ work, int L, int H) {
+                                                        const float* __restrict__ state, float* __restrict__ work, float* __restrict__ bq0, int L,
+                                                        int H) {
   __shared__ float As[WG_BLOCKS], Bs[WG_BLOCKS + 1];
   const int b = blockIdx.y, tid = threadIdx.x, j0 = blockIdx.x * WG_BLOCKS;
   const float* gr = dy + (long long)b * dys;
@@ -217,8 +224,9 @@ __global__ __launch_bounds__(256) void drc_dgain_kernel(const float* __restrict_
   if (tid < WG_BLOCKS && j < H) {
     float dG = As[tid];
     if (j + 1 < H) dG += Bs[tid + 1];
-    work[(size_t)b * H + j] = (state_row(state, b, H, 1)[j] * dG) * NEG_LN10_20;
+    work[work_row<KEEP>(b, H) + j] = (state_row(state, b, H, 1)[j] * dG) * NEG_LN10_20;
   }
+  if (KEEP && blockIdx.x == 0 && tid == 0) bq0[b] = Bs[0];
 }
 
 // one chunk of the backward recurrence: CHUNK blocks from `top` downwards
@@ -232,25 +240,29 @@ __device__ __forceinline__ void follow_bwd_load(const float* wrow, const unsigne
   }
 }
 template <bool GUARD>
-__device__ __forceinline__ float follow_bwd_steps(float* wrow, int top, const float (&d)[CHUNK], const unsigned char (&t)[CHUNK], float carry,
+__device__ __forceinline__ float follow_bwd_steps(float* orow, int top, const float (&d)[CHUNK], const unsigned char (&t)[CHUNK], float carry,
                                                   float aA, float aR, float bA, float bR) {
 #pragma unroll
   for (int k = 0; k < CHUNK; ++k) {
     if (!GUARD || top - k >= 0) {
       const bool att = (t[k] & 4) != 0;
       const float tot = d[k] + carry;
-      wrow[top - k] = (att ? aA : aR) * tot;
+      orow[top - k] = (att ? aA : aR) * tot;
       carry = (att ? bA : bR) * tot;
     }
   }
   return carry;
 }
 
+template <class Src>
 __global__ __launch_bounds__(64) void drc_follow_bwd_kernel(float* __restrict__ work, const unsigned char* __restrict__ tape, int B, int H,
-                                                            float aA, float aR, float bA, float bR) {
+                                                            Src src) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
-  float* wrow = work + (size_t)b * H;
+  float aA, aR, bA, bR;
+  src.follower_bwd(b, aA, aR, bA, bR);                     // once, before the chain
+  float* wrow = work + work_row<Src::TABLE>(b, H);         // ds
+  float* orow = wrow + (Src::TABLE ? H : 0);               // dc: over ds, or the row after it
   const unsigned char* trow = tape + (size_t)b * H;
   const int whole = H / CHUNK;
   float dn[CHUNK], dc[CHUNK];
@@ -261,21 +273,24 @@ __global__ __launch_bounds__(64) void drc_follow_bwd_kernel(float* __restrict__ 
 #pragma unroll
     for (int k = 0; k < CHUNK; ++k) { dc[k] = dn[k]; tc[k] = tn[k]; }
     if (m + 1 < whole) follow_bwd_load<false>(wrow, trow, H - 1 - (m + 1) * CHUNK, dn, tn);
-    carry = follow_bwd_steps<false>(wrow, H - 1 - m * CHUNK, dc, tc, carry, aA, aR, bA, bR);
+    carry = follow_bwd_steps<false>(orow, H - 1 - m * CHUNK, dc, tc, carry, aA, aR, bA, bR);
   }
   if (whole * CHUNK < H) {
     const int top = H - 1 - whole * CHUNK;
     follow_bwd_load<true>(wrow, trow, top, dn, tn);
-    follow_bwd_steps<true>(wrow, top, dn, tn, carry, aA, aR, bA, bR);
+    follow_bwd_steps<true>(orow, top, dn, tn, carry, aA, aR, bA, bR);
   }
 }
 
+template <class Src>
 __global__ __launch_bounds__(256) void drc_apply_bwd_kernel(const float* __restrict__ dy, long long dys, const float* __restrict__ x, long long xs,
                                                             const float* __restrict__ state, const unsigned char* __restrict__ tape,
                                                             const float* __restrict__ work, float* __restrict__ dx, long long dxs, int L,
-                                                            int full, int H, DrcParams P) {
+                                                            int full, int H, Src src) {
   __shared__ float Gs[WG_BLOCKS + 1], Ds[WG_BLOCKS];
   const int b = blockIdx.y, tid = threadIdx.x, j0 = blockIdx.x * WG_BLOCKS;
+  const DrcParams P = src.clip(b);
+  const float* dcrow = work + work_row<Src::TABLE>(b, H) + (Src::TABLE ? H : 0);
   if (tid <= WG_BLOCKS) {
     const int j = j0 - 1 + tid;
     Gs[tid] = j < 0 ? block_gain(0.f, P.makeup) : (j < H ? state_row(state, b, H, 1)[j] : 0.f);
@@ -286,10 +301,8 @@ __global__ __launch_bounds__(256) void drc_apply_bwd_kernel(const float* __restr
     if (j < H) {
       const int rg = tape[(size_t)b * H + j] & 3;
       const float p = state_row(state, b, H, 0)[j];
-      float slope = 0.f;
-      if (rg == 2) slope = P.k;
-      else if (rg == 1) slope = 2.f * P.kq * (level_over_threshold(p, P.T) + P.halfW);
-      dp = ((work[(size_t)b * H + j] * slope) * C10) / (p + EPS) * (2.f / R);
+      const float slope = curve_slope(p, rg, P);
+      dp = ((dcrow[j] * slope) * C10) / (p + EPS) * (2.f / R);
     }
     Ds[tid] = dp;
   }
@@ -329,41 +342,92 @@ bool drc_params(const char* who, float T, float slope, float knee, float aA, flo
 
 constexpr int MAX_L = 1 << 30;
 
+bool fwd_shapes(const char* who, const void* x, const void* y, const void* state, const void* tape, int batch, int L, long long x_stride,
+                long long y_stride) {
+  if (!x || !y || !state || !tape || batch < 1 || batch > 65535 || L < 1 || L > MAX_L || x_stride < L || y_stride < L) {
+    dmx_set_error("%s: x (batch, >= L), y (batch, L) with row strides >= L, state (batch, 3, H) and tape (batch, H) contiguous, "
+                  "H = ceil(L / 64), 1 <= batch <= 65535, 1 <= L <= 2^30", who);
+    return false;
+  }
+  return true;
+}
+bool bwd_shapes(const char* who, const char* work_shape, const void* dy, const void* x, const void* state, const void* tape, const void* work,
+                const void* dx, int batch, int L, int Lfull, long long dy_stride, long long x_stride, long long dx_stride) {
+  if (!dy || !x || !state || !tape || !work || !dx || batch < 1 || batch > 65535 || L < 1 || L > MAX_L || Lfull < L || Lfull > MAX_L ||
+      dy_stride < L || x_stride < L || dx_stride < Lfull) {
+    dmx_set_error("%s: dy and x (batch, >= L), dx (batch, Lfull >= L) with row strides >= their lengths, state (batch, 3, H), tape and "
+                  "work %s contiguous, H = ceil(L / 64), 1 <= batch <= 65535, 1 <= L <= Lfull <= 2^30", who, work_shape);
+    return false;
+  }
+  return true;
+}
+bool table_ok(const char* who, const float* theta, float knee) {
+  if (!theta || !(std::isfinite(knee) && knee >= 0.f && knee <= 200.f)) {
+    dmx_set_error("%s: theta (batch, 8) fp32 on the device, rows T, k, makeup, aA, aR, 1 - aA, 1 - aR, k / (2 knee_db), and 0 <= knee_db <= 200",
+                  who);
+    return false;
+  }
+  return true;
+}
+
+// the three launches of a direction, for either parameter source
+template <class Src>
+int launch_fwd(const float* x, long long x_stride, float* y, long long y_stride, float* state, unsigned char* tape, int batch, int L,
+               const Src& src, hipStream_t st) {
+  const int H = cdiv(L, R);
+  hipLaunchKernelGGL(drc_power_kernel<Src>, row_grid(L, batch), dim3(256), 0, st, x, x_stride, state, tape, L, H, src);
+  hipLaunchKernelGGL(drc_follow_kernel<Src>, dim3((unsigned)cdiv(batch, 64)), dim3(64), 0, st, state, tape, batch, H, src);
+  hipLaunchKernelGGL(drc_apply_kernel<Src>, row_grid(L, batch), dim3(256), 0, st, x, x_stride, y, y_stride, state, L, H, src);
+  return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
+}
+template <class Src>
+int launch_bwd(const float* dy, long long dy_stride, const float* x, long long x_stride, const float* state, const unsigned char* tape,
+               float* work, float* bq0, float* dx, long long dx_stride, int batch, int L, int Lfull, const Src& src, hipStream_t st) {
+  const int H = cdiv(L, R);
+  hipLaunchKernelGGL(drc_dgain_kernel<Src::TABLE>, row_grid(L, batch), dim3(256), 0, st, dy, dy_stride, x, x_stride, state, work, bq0, L, H);
+  hipLaunchKernelGGL(drc_follow_bwd_kernel<Src>, dim3((unsigned)cdiv(batch, 64)), dim3(64), 0, st, work, tape, batch, H, src);
+  hipLaunchKernelGGL(drc_apply_bwd_kernel<Src>, row_grid(Lfull, batch), dim3(256), 0, st, dy, dy_stride, x, x_stride, state, tape,
+                     (const float*)work, dx, dx_stride, L, Lfull, H, src);
+  return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
+}
+
 }  // namespace
 
 extern "C" int dmx_drc_fwd(const float* x, long long x_stride, float* y, long long y_stride, float* state, unsigned char* tape, int batch, int L,
                            float threshold_db, float slope, float knee_db, float a_att, float a_rel, float makeup_db, void* stream) {
-  if (!x || !y || !state || !tape || batch < 1 || batch > 65535 || L < 1 || L > MAX_L || x_stride < L || y_stride < L) {
-    dmx_set_error("drc_fwd: x (batch, >= L), y (batch, L) with row strides >= L, state (batch, 3, H) and tape (batch, H) contiguous, "
-                  "H = ceil(L / 64), 1 <= batch <= 65535, 1 <= L <= 2^30");
-    return DMX_ERR_SHAPE;
-  }
-  DrcParams P;
-  if (!drc_params("drc_fwd", threshold_db, slope, knee_db, a_att, a_rel, makeup_db, P)) return DMX_ERR_SHAPE;
-  const int H = cdiv(L, R);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(drc_power_kernel, row_grid(L, batch), dim3(256), 0, st, x, x_stride, state, tape, L, H, P);
-  hipLaunchKernelGGL(drc_follow_kernel, dim3((unsigned)cdiv(batch, 64)), dim3(64), 0, st, state, tape, batch, H, P.aA, P.aR);
-  hipLaunchKernelGGL(drc_apply_kernel, row_grid(L, batch), dim3(256), 0, st, x, x_stride, y, y_stride, state, L, H, P.makeup);
-  return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
+  if (!fwd_shapes("drc_fwd", x, y, state, tape, batch, L, x_stride, y_stride)) return DMX_ERR_SHAPE;
+  ByValue src;
+  if (!drc_params("drc_fwd", threshold_db, slope, knee_db, a_att, a_rel, makeup_db, src.P)) return DMX_ERR_SHAPE;
+  return launch_fwd(x, x_stride, y, y_stride, state, tape, batch, L, src, (hipStream_t)stream);
 }
 
 extern "C" int dmx_drc_bwd(const float* dy, long long dy_stride, const float* x, long long x_stride, const float* state, const unsigned char* tape,
                            float* work, float* dx, long long dx_stride, int batch, int L, int Lfull, float threshold_db, float slope, float knee_db,
                            float a_att, float a_rel, float makeup_db, void* stream) {
-  if (!dy || !x || !state || !tape || !work || !dx || batch < 1 || batch > 65535 || L < 1 || L > MAX_L || Lfull < L || Lfull > MAX_L ||
-      dy_stride < L || x_stride < L || dx_stride < Lfull) {
-    dmx_set_error("drc_bwd: dy and x (batch, >= L), dx (batch, Lfull >= L) with row strides >= their lengths, state (batch, 3, H), tape and "
-                  "work (batch, H) contiguous, H = ceil(L / 64), 1 <= batch <= 65535, 1 <= L <= Lfull <= 2^30");
+  if (!bwd_shapes("drc_bwd", "(batch, H)", dy, x, state, tape, work, dx, batch, L, Lfull, dy_stride, x_stride, dx_stride)) return DMX_ERR_SHAPE;
+  ByValue src;
+  if (!drc_params("drc_bwd", threshold_db, slope, knee_db, a_att, a_rel, makeup_db, src.P)) return DMX_ERR_SHAPE;
+  return launch_bwd(dy, dy_stride, x, x_stride, state, tape, work, nullptr, dx, dx_stride, batch, L, Lfull, src, (hipStream_t)stream);
+}
+
+// The same three launches per direction with the parameters of clip b read from theta[b, 0:8] on the device (drc_common.h, ByTable).  The
+// backward keeps what the parameter gradient needs: work is (batch, 2, H), rows ds and dc, and bq0 (batch,) holds Bq[0] of each clip.
+extern "C" int dmx_drc_fwd_p(const float* x, long long x_stride, float* y, long long y_stride, float* state, unsigned char* tape, const float* theta,
+                             int batch, int L, float knee_db, void* stream) {
+  if (!fwd_shapes("drc_fwd_p", x, y, state, tape, batch, L, x_stride, y_stride) || !table_ok("drc_fwd_p", theta, knee_db)) return DMX_ERR_SHAPE;
+  return launch_fwd(x, x_stride, y, y_stride, state, tape, batch, L, ByTable{theta, knee_db}, (hipStream_t)stream);
+}
+
+extern "C" int dmx_drc_bwd_p(const float* dy, long long dy_stride, const float* x, long long x_stride, const float* state,
+                             const unsigned char* tape, const float* theta, float* work, float* bq0, float* dx, long long dx_stride, int batch,
+                             int L, int Lfull, float knee_db, void* stream) {
+  if (!bwd_shapes("drc_bwd_p", "(batch, 2, H)", dy, x, state, tape, work, dx, batch, L, Lfull, dy_stride, x_stride, dx_stride) ||
+      !table_ok("drc_bwd_p", theta, knee_db))
+    return DMX_ERR_SHAPE;
+  if (!bq0) {
+    dmx_set_error("drc_bwd_p: bq0 (batch,) fp32 is required");
     return DMX_ERR_SHAPE;
   }
-  DrcParams P;
-  if (!drc_params("drc_bwd", threshold_db, slope, knee_db, a_att, a_rel, makeup_db, P)) return DMX_ERR_SHAPE;
-  const int H = cdiv(L, R);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(drc_dgain_kernel, row_grid(L, batch), dim3(256), 0, st, dy, dy_stride, x, x_stride, state, work, L, H);
-  hipLaunchKernelGGL(drc_follow_bwd_kernel, dim3((unsigned)cdiv(batch, 64)), dim3(64), 0, st, work, tape, batch, H, P.aA, P.aR, P.bA, P.bR);
-  hipLaunchKernelGGL(drc_apply_bwd_kernel, row_grid(Lfull, batch), dim3(256), 0, st, dy, dy_stride, x, x_stride, state, tape, work, dx, dx_stride,
-                     L, Lfull, H, P);
-  return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
+  return launch_bwd(dy, dy_stride, x, x_stride, state, tape, work, bq0, dx, dx_stride, batch, L, Lfull, ByTable{theta, knee_db},
+                    (hipStream_t)stream);
 }

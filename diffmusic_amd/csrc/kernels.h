@@ -114,6 +114,12 @@ int dmx_tf_wgrad(const DmxStftMelTables& t, const float* x, long long x_stride, 
 // waveshape.hip it needs no handle: its launchers are the C ABI's own dmx_drc_fwd / dmx_drc_bwd (include/diffmusic_hip.h)
 constexpr int DMX_DRC_BLOCK = 64;                        // samples per sidechain block; state (B, 3, H) and tape (B, H), H = ceil(L / 64)
 
+// ---- drc_fit.hip (blind de-compression: the gradient of a loss in the compressor's parameters as one row of five per segment of 256
+// blocks, and the Adam + box update of a clip's parameters with its table row; one launch each).  No handle either: its launchers are the
+// C ABI's own dmx_drc_pgrad / dmx_drc_update; the level and the static curve are drc.hip's, from drc_common.h
+constexpr int DMX_DRC_FIT_SEGMENT = 256;                 // blocks per partial row; part (B, ceil(H / 256), 5)
+constexpr int DMX_DRC_FIT_PARAMS = 5;                    // T, k, makeup, ln aA, ln aR
+
 // ---- warp.hip (wow and flutter: a clip read along a given delay curve, four-point Catmull-Rom, and the transpose as a gather; one launch
 // per direction).  Like waveshape.hip it needs no handle: its launchers are the C ABI's own dmx_warp_fwd / dmx_warp_bwd
 constexpr int DMX_WARP_BLOCK = 64;                       // samples per knot interval; a curve is H + 1 knots, H = ceil(L / 64)

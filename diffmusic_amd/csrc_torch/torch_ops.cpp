@@ -50,6 +50,10 @@
 #pragma weak dmx_warp_bwd
 #pragma weak dmx_warp_wgrad
 #pragma weak dmx_warp_update
+#pragma weak dmx_drc_fwd_p
+#pragma weak dmx_drc_bwd_p
+#pragma weak dmx_drc_pgrad
+#pragma weak dmx_drc_update
 
 namespace {
 
@@ -381,6 +385,85 @@ at::Tensor drc_bwd(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& 
                  work.data_ptr<float>(), d.data_ptr<float>(), Lfull, (int)std::min<int64_t>(B, 65536), (int)L, (int)Lfull, (float)threshold_db, (float)slope,
                  (float)knee_db, (float)a_att, (float)a_rel, (float)makeup_db, cur_stream()), "drc_bwd");
   return d;
+}
+// blind de-compression (include/diffmusic_hip.h dmx_drc_fwd_p / dmx_drc_bwd_p / dmx_drc_pgrad / dmx_drc_update): the compressor with one
+// parameter row per clip, theta (B, 8) fp32 on the device; the backward also returns work (B, 2, H) (rows ds, dc) and bq0 (B,), from which
+// drc_pgrad makes part (B, ceil(H / 256), 5); drc_update writes phi, m, v (B, 5) and theta
+static void drc_table_ok(const at::Tensor& theta, int64_t B, const at::Tensor& like) {
+  f32_cuda(theta, "theta");
+  TORCH_CHECK(theta.device() == like.device() && theta.dim() == 2 && theta.size(0) == B && theta.size(1) == 8, "theta must be (", B,
+              ", 8) on the clips' device");
+}
+static void drc_tape_ok(const at::Tensor& state, const at::Tensor& tape, int64_t B, int64_t H, const at::Tensor& like) {
+  f32_cuda(state, "state");
+  TORCH_CHECK(state.device() == like.device() && state.dim() == 3 && state.size(0) == B && state.size(1) == 3 && state.size(2) == H,
+              "state must be (", B, ", 3, ", H, ") on the clips' device");
+  TORCH_CHECK(tape.is_cuda() && tape.device() == like.device() && tape.scalar_type() == at::kByte && tape.is_contiguous() && tape.dim() == 2 &&
+              tape.size(0) == B && tape.size(1) == H, "tape must be contiguous uint8 (", B, ", ", H, ") on the clips' device");
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> drc_fwd_p(const at::Tensor& x, int64_t L, const at::Tensor& theta, double knee_db) {
+  rows_ok(x, L, "x");
+  TORCH_CHECK(L <= (int64_t(1) << 30), "L must be <= 2^30");
+  const int64_t B = x.size(0), H = (L + 63) / 64;
+  drc_table_ok(theta, B, x);
+  DMX_DEVICE_OF(x);
+  at::Tensor y = at::empty({B, L}, x.options());
+  at::Tensor state = at::empty({B, 3, H}, x.options());
+  at::Tensor tape = at::empty({B, H}, x.options().dtype(at::kByte));
+  ok(dmx_drc_fwd_p(x.data_ptr<float>(), x.stride(0), y.data_ptr<float>(), L, state.data_ptr<float>(), tape.data_ptr<uint8_t>(),
+                   theta.data_ptr<float>(), (int)std::min<int64_t>(B, 65536), (int)L, (float)knee_db, cur_stream()), "drc_fwd_p");
+  return {y, state, tape};
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> drc_bwd_p(const at::Tensor& dy, const at::Tensor& x, const at::Tensor& state, const at::Tensor& tape,
+                                                         const at::Tensor& theta, int64_t Lfull, double knee_db) {
+  TORCH_CHECK(dy.is_cuda(), "dy must be a GPU tensor (the diffmusic_hip ops have no CPU fallback)");
+  TORCH_CHECK(dy.scalar_type() == at::kFloat && dy.dim() == 2 && dy.stride(1) == 1 && dy.size(1) >= 1 && Lfull >= dy.size(1) &&
+              Lfull <= (int64_t(1) << 30), "dy must be (B, L) fp32 with 1 <= L <= Lfull <= 2^30");
+  const int64_t B = dy.size(0), L = dy.size(1), H = (L + 63) / 64;
+  rows_ok(x, L, "x");
+  TORCH_CHECK(x.size(0) == B && x.device() == dy.device(), "x must hold dy's clips");
+  drc_tape_ok(state, tape, B, H, dy);
+  drc_table_ok(theta, B, dy);
+  DMX_DEVICE_OF(dy);
+  at::Tensor work = at::empty({B, 2, H}, dy.options());
+  at::Tensor bq0 = at::empty({B}, dy.options());
+  at::Tensor d = at::empty({B, Lfull}, dy.options());
+  ok(dmx_drc_bwd_p(dy.data_ptr<float>(), dy.stride(0), x.data_ptr<float>(), x.stride(0), state.data_ptr<float>(), tape.data_ptr<uint8_t>(),
+                   theta.data_ptr<float>(), work.data_ptr<float>(), bq0.data_ptr<float>(), d.data_ptr<float>(), Lfull,
+                   (int)std::min<int64_t>(B, 65536), (int)L, (int)Lfull, (float)knee_db, cur_stream()), "drc_bwd_p");
+  return {d, work, bq0};
+}
+at::Tensor drc_pgrad(const at::Tensor& state, const at::Tensor& tape, const at::Tensor& work, const at::Tensor& bq0, const at::Tensor& theta,
+                     int64_t L, double knee_db) {
+  TORCH_CHECK(L >= 1 && L <= (int64_t(1) << 30), "1 <= L <= 2^30");
+  f32_cuda(work, "work");
+  const int64_t H = (L + 63) / 64, B = work.size(0);
+  TORCH_CHECK(work.dim() == 3 && B >= 1 && work.size(1) == 2 && work.size(2) == H, "work must be (B, 2, ", H, ")");
+  drc_tape_ok(state, tape, B, H, work);
+  drc_table_ok(theta, B, work);
+  f32_cuda(bq0, "bq0");
+  TORCH_CHECK(bq0.device() == work.device() && bq0.dim() == 1 && bq0.size(0) == B, "bq0 must be (", B, ",) on work's device");
+  DMX_DEVICE_OF(work);
+  at::Tensor part = at::empty({B, (H + 255) / 256, 5}, work.options());
+  ok(dmx_drc_pgrad(state.data_ptr<float>(), tape.data_ptr<uint8_t>(), work.data_ptr<float>(), bq0.data_ptr<float>(), theta.data_ptr<float>(),
+                   part.data_ptr<float>(), (int)std::min<int64_t>(B, 65536), (int)L, (float)knee_db, cur_stream()), "drc_pgrad");
+  return part;
+}
+void drc_update(const at::Tensor& part, at::Tensor phi, at::Tensor m, at::Tensor v, at::Tensor theta, int64_t L, int64_t k, at::ArrayRef<double> lr,
+                double beta1, double beta2, double eps, double knee_db, at::ArrayRef<double> lo, at::ArrayRef<double> hi) {
+  f32_cuda(part, "part");
+  TORCH_CHECK(L >= 1 && L <= (int64_t(1) << 30), "1 <= L <= 2^30");
+  TORCH_CHECK(lr.size() == 5 && lo.size() == 5 && hi.size() == 5, "lr, lo and hi must hold five numbers each (T, k, makeup, ln aA, ln aR)");
+  const int64_t H = (L + 63) / 64, B = part.size(0);
+  TORCH_CHECK(part.dim() == 3 && B >= 1 && part.size(1) == (H + 255) / 256 && part.size(2) == 5, "part must be (B, ", (H + 255) / 256, ", 5)");
+  for (const at::Tensor* t : {&phi, &m, &v}) {
+    f32_cuda(*t, "phi / m / v");
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == 5 && t->device() == part.device(), "phi, m and v must be (", B, ", 5) on part's device");
+  }
+  drc_table_ok(theta, B, part);
+  DMX_DEVICE_OF(part);
+  ok(dmx_drc_update(part.data_ptr<float>(), phi.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), theta.data_ptr<float>(), (int)B, (int)L,
+                    (int)k, lr.data(), beta1, beta2, eps, (float)knee_db, lo.data(), hi.data(), cur_stream()), "drc_update");
 }
 // wow and flutter (include/diffmusic_hip.h dmx_warp_fwd / dmx_warp_bwd): x (B, >= length) -> (B, length) read along the delay curve;
 // delay (H + 1) for every clip or (B, H + 1), H = ceil(length / 64), contiguous; the transpose takes dy (B, length) and returns (B, full)
@@ -790,10 +873,14 @@ TORCH_LIBRARY(diffmusic_hip, m) {
                                                          {"dmx_warp_fwd", (const void*)&dmx_warp_fwd},
                                                          {"dmx_warp_bwd", (const void*)&dmx_warp_bwd},
                                                          {"dmx_warp_wgrad", (const void*)&dmx_warp_wgrad},
-                                                         {"dmx_warp_update", (const void*)&dmx_warp_update}};
+                                                         {"dmx_warp_update", (const void*)&dmx_warp_update},
+                                                         {"dmx_drc_fwd_p", (const void*)&dmx_drc_fwd_p},
+                                                         {"dmx_drc_bwd_p", (const void*)&dmx_drc_bwd_p},
+                                                         {"dmx_drc_pgrad", (const void*)&dmx_drc_pgrad},
+                                                         {"dmx_drc_update", (const void*)&dmx_drc_update}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
-                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter / blind-wow-and-flutter entry points): rebuild with `python -m diffmusic_amd.build --force`");
+                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter / blind-wow-and-flutter / blind-de-compression entry points): rebuild with `python -m diffmusic_amd.build --force`");
   }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
@@ -828,6 +915,11 @@ TORCH_LIBRARY(diffmusic_hip, m) {
         &drc_fwd);
   m.def("drc_bwd(Tensor dy, Tensor x, Tensor state, Tensor tape, int Lfull, float threshold_db, float slope, float knee_db, float a_att, float a_rel, "
         "float makeup_db) -> Tensor", &drc_bwd);
+  m.def("drc_fwd_p(Tensor x, int L, Tensor theta, float knee_db) -> (Tensor, Tensor, Tensor)", &drc_fwd_p);
+  m.def("drc_bwd_p(Tensor dy, Tensor x, Tensor state, Tensor tape, Tensor theta, int Lfull, float knee_db) -> (Tensor, Tensor, Tensor)", &drc_bwd_p);
+  m.def("drc_pgrad(Tensor state, Tensor tape, Tensor work, Tensor bq0, Tensor theta, int L, float knee_db) -> Tensor", &drc_pgrad);
+  m.def("drc_update(Tensor part, Tensor(a!) phi, Tensor(b!) m, Tensor(c!) v, Tensor(d!) theta, int L, int k, float[] lr, float beta1, "
+        "float beta2, float eps, float knee_db, float[] lo, float[] hi) -> ()", &drc_update);
   m.def("warp_fwd(Tensor x, Tensor delay, int length) -> Tensor", &warp_fwd);
   m.def("warp_bwd(Tensor dy, Tensor delay, int length, int full) -> Tensor", &warp_bwd);
   m.def("warp_wgrad(Tensor dy, Tensor x, Tensor delay, int length) -> Tensor", &warp_wgrad);

@@ -173,6 +173,43 @@ def drc_static_curve(level_db, threshold_db, ratio, knee_db):
     return np.where(2.0 * d < -knee_db, 0.0, np.where(2.0 * d <= knee_db, knee, k * d))
 
 
+# ---- blind de-compression (BlindDynamicRangeOperator; csrc/drc_fit.hip): one parameter row per clip on the device
+DRC_TABLE_COLUMNS = ("threshold_db", "slope", "makeup_db", "a_att", "a_rel", "1 - a_att", "1 - a_rel", "slope / (2 knee_db)")
+
+
+def drc_table(threshold_db, slope, a_att, a_rel, makeup_db, knee_db, batch):
+    """(batch, 8) np.float32 rows T, k, makeup, aA, aR, 1 - aA, 1 - aR, k / (2 W) for `drc_fwd_p` / `drc_bwd_p`.  Each of the five parameters
+    is a scalar shared by the clips or holds one value per clip; each is rounded to fp32 first, and the derived entries are computed in
+    float64 from those fp32 values and rounded once -- exactly as the host side of `drc_fwd` derives them, so a table of the parameters of a
+    `drc_fwd` call gives its bits.  knee_db is the shared knee width W (k / (2 W) is 0 when W = 0)."""
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError(f"batch = {batch!r}: at least one clip")
+    knee = float(np.float32(knee_db))
+    if not (math.isfinite(knee) and 0.0 <= knee <= 200.0):
+        raise ValueError(f"knee_db = {knee_db!r}: a finite width in [0, 200]")
+    cols = []
+    for name, v in (("threshold_db", threshold_db), ("slope", slope), ("makeup_db", makeup_db), ("a_att", a_att), ("a_rel", a_rel)):
+        v = np.asarray(v, dtype=np.float64).reshape(-1)
+        if v.size not in (1, batch):
+            raise ValueError(f"{name} holds {v.size} values: one, or one per clip of a batch of {batch}")
+        cols.append(np.broadcast_to(v.astype(np.float32), (batch,)))
+    T, k, m, aA, aR = cols
+    out = np.empty((batch, 8), dtype=np.float32)
+    out[:, 0], out[:, 1], out[:, 2], out[:, 3], out[:, 4] = T, k, m, aA, aR
+    out[:, 5] = (1.0 - aA.astype(np.float64)).astype(np.float32)
+    out[:, 6] = (1.0 - aR.astype(np.float64)).astype(np.float32)
+    out[:, 7] = (k.astype(np.float64) / (2.0 * knee)).astype(np.float32) if knee > 0 else 0.0
+    return out
+
+
+def drc_time_ms(a, sample_rate):
+    """The time constant in milliseconds whose per-block coefficient is a: the inverse of `drc_coeffs` (0 for a = 1)."""
+    a = np.asarray(a, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        return np.where(a >= 1.0, 0.0, -DRC_BLOCK / (float(sample_rate) * np.log1p(-np.minimum(a, 1.0))) * 1e3)
+
+
 # ---- wow and flutter (TimeWarpOperator; csrc/warp.hip): a delay curve in samples, one knot per 64 samples, linear between the knots
 WARP_BLOCK = 64
 WARP_MAX_DELAY = 4096.0      # |d[j]|: a quarter of a second at 16 kHz; an fp32 delay of that size still resolves 2.4e-4 of a sample

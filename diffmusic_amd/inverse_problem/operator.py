@@ -1203,7 +1203,203 @@ class BlindTimeWarpOperator(_MelOperator):
                             self.betas[1], self.adam_eps, self.max_delay, self.anchor == "mean")
 
 
-class StyleGuidanceOperator(BaseOperator):                # operator.py:253-271 (unrunnable in the reference: run.py:213-214)
+class BlindDynamicRangeOperator(_MelOperator):
+    """De-compression with UNKNOWN compressor settings (extension): the operator of `DynamicRangeOperator` with one parameter estimate per
+    clip fitted inside the guided loop, the way `BlindTimeWarpOperator` fits its delay curve (csrc/drc_fit.hip).
+
+    Per clip the fitted vector is phi = (T, k, m, ln aA, ln aR): threshold in dB, slope k = 1 - 1 / ratio, make-up in dB and the logarithms
+    of the attack and release coefficients of `dsp.drc_coeffs`; the knee width `knee_db` is given and shared.  The kernels read the table
+    row theta[b] = (T, k, m, aA, aR, 1 - aA, 1 - aR, k / (2 W)) on the device (`drc_fwd_p`, `drc_bwd_p`: the three launches per direction of
+    the fixed operator).  One `guidance` call computes the loss and the gradient w.r.t. the audio with the current estimate, then
+    `drc_pgrad` turns what the backward follower left into the gradient in phi and `drc_update` takes one Adam step per parameter, clamps it
+    to its box and rewrites the row: two launches, no host sync.  A clip whose gradient or step is not finite keeps its state.
+
+    fit names the parameters that move: "threshold", "ratio", "makeup", "attack", "release"; the others stay at `init` (their lr is 0: value,
+    moments and table entries keep their bits).  lr is per parameter, in the parameter's own unit per step -- dB for threshold and makeup,
+    slope units for the ratio's k, natural-log units of the coefficient for attack and release; Adam moves a parameter by about lr per
+    step.  The defaults are callers' knobs, not tuned values.  The boxes: threshold_range and makeup_range in dB, time_range_ms for both
+    time constants, k in [0, 1].
+    forward(data, params=dict(threshold_db, ratio, attack_ms, release_ms, makeup_db)) makes the measurement with the TRUE parameters through
+    the fixed route (`drc_fwd`) and keeps them as `true_params`.  The state is made on first use and again when the batch or the device
+    changes; reset_cache() (every `set_timesteps`) and restart() (NaN-retry) put it back, so two identical pipeline calls give the same
+    bits.  `guidance(..., update_drc=False)` freezes the estimate; `params=` pins the parameters of one call and never updates.
+
+    The knee width is not fitted; the sidechain runs at block rate; threshold and make-up trade off against each other on material that
+    never leaves the compressed region.  The state is indexed by batch position, so the pipelines refuse `lanes > 1` and `shard=True`.
+    dead_span stays None.  k, the count of updates since the last reset, is kept on the host and shared by the clips."""
+
+    NAMES = ("threshold", "ratio", "makeup", "attack", "release")          # the order of phi
+    LR_KEYS = ("threshold", "slope", "makeup", "attack", "release")
+    INIT = dict(threshold_db=-12.0, ratio=2.0, attack_ms=5.0, release_ms=100.0, makeup_db=0.0)
+    LR = dict(threshold=0.25, slope=0.01, makeup=0.1, attack=0.02, release=0.02)
+
+    def __init__(self, sample_rate=16000, knee_db=6.0, noiser=None, fit=("threshold", "ratio", "makeup"), init=None, lr=None,
+                 betas=(0.9, 0.999), adam_eps=1e-8, threshold_range=(-60.0, 0.0), makeup_range=(-24.0, 24.0), time_range_ms=(0.5, 2000.0)):
+        if not (math.isfinite(float(sample_rate)) and float(sample_rate) > 0):
+            raise ValueError(f"sample_rate = {sample_rate!r}: a positive finite rate")
+        knee = float(knee_db)
+        if not (math.isfinite(knee) and 0.0 <= knee <= 200.0):
+            raise ValueError(f"knee_db = {knee_db!r}: a finite width in [0, 200]")
+        fit = (fit,) if isinstance(fit, str) else tuple(fit)
+        if not fit or any(n not in self.NAMES for n in fit) or len(set(fit)) != len(fit):
+            raise ValueError(f"fit = {fit!r}: one or more of {self.NAMES}, each once")
+        init = dict(self.INIT, **self._known("init", init, self.INIT))
+        lr = dict(self.LR, **self._known("lr", lr, self.LR))
+        for n, v in lr.items():
+            if not (isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) and v > 0):
+                raise ValueError(f"lr[{n!r}] = {v!r}: a positive number (the parameter's own unit per step)")
+        if len(betas) != 2 or not all(isinstance(b, (int, float)) and 0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"betas = {betas!r}: two numbers in [0, 1)")
+        if not (isinstance(adam_eps, (int, float)) and math.isfinite(adam_eps) and adam_eps >= 0):
+            raise ValueError(f"adam_eps = {adam_eps!r}: a non-negative number")
+
+        def span(name, r, lo, hi):
+            if len(r) != 2 or not all(isinstance(v, (int, float)) and math.isfinite(v) for v in r) or not lo <= r[0] <= r[1] <= hi:
+                raise ValueError(f"{name} = {r!r}: (low, high) with {lo} <= low <= high <= {hi}")
+            return float(r[0]), float(r[1])
+        t_lo, t_hi = span("threshold_range", threshold_range, -200.0, 200.0)
+        m_lo, m_hi = span("makeup_range", makeup_range, -200.0, 200.0)
+        if len(time_range_ms) != 2 or not all(isinstance(v, (int, float)) and math.isfinite(v) and v > 0 for v in time_range_ms) or \
+                time_range_ms[0] > time_range_ms[1]:
+            raise ValueError(f"time_range_ms = {time_range_ms!r}: (shortest, longest) positive times in milliseconds")
+        a_hi, a_lo = dsp.drc_coeffs(sample_rate, time_range_ms[0], time_range_ms[1])          # the short time has the large coefficient
+        ln_lo, ln_hi = math.log(float(a_lo)), math.log(float(a_hi))
+        self.sample_rate, self.noiser = sample_rate, noiser
+        self.knee_db = float(np.float32(knee))
+        self.fit, self.betas, self.adam_eps = fit, (float(betas[0]), float(betas[1])), float(adam_eps)
+        self.lr = tuple(float(lr[key]) if name in fit else 0.0 for name, key in zip(self.NAMES, self.LR_KEYS))
+        self.box_lo, self.box_hi = (t_lo, 0.0, m_lo, ln_lo, ln_lo), (t_hi, 1.0, m_hi, ln_hi, ln_hi)
+        self.init = init
+        self._start = self._phi_of(init, "init")                 # (5,) float64: inside the boxes, refused by name otherwise
+        for name, v, lo, hi in zip(self.NAMES, self._start, self.box_lo, self.box_hi):
+            if not lo - 1e-6 * max(1.0, abs(lo)) <= v <= hi + 1e-6 * max(1.0, abs(hi)):
+                raise ValueError(f"init: the {name} parameter starts outside its range (threshold_range, makeup_range, time_range_ms, "
+                                 "ratio >= 1)")
+        self.true_params = None
+        self._phi = self._m = self._v = self._theta = None
+        self._kept = None
+        self.k = 0
+        self._init_mel(sample_rate, lazy=True)
+
+    @staticmethod
+    def _known(what, given, known):
+        given = {} if given is None else dict(given)
+        for key in given:
+            if key not in known:
+                raise ValueError(f"{what}[{key!r}]: unknown key; the keys are {tuple(known)}")
+        return given
+
+    def _fixed(self, p, what):
+        """dict(threshold_db, ratio, attack_ms, release_ms, makeup_db) -> the six fp32 parameters of `drc_fwd`, refused by name"""
+        p = self._known(what, p, self.INIT)
+        if set(p) != set(self.INIT):
+            raise ValueError(f"{what} needs all of {tuple(self.INIT)}; got {tuple(p)}")
+        try:
+            return DynamicRangeOperator(sample_rate=self.sample_rate, knee_db=self.knee_db, **p).params
+        except ValueError as e:
+            raise ValueError(f"{what}: {e}") from None
+
+    def _phi_of(self, p, what):
+        T, k, _, aA, aR, mk = self._fixed(p, what)
+        return np.array([T, k, mk, math.log(aA), math.log(aR)], dtype=np.float64)
+
+    # ---- the estimate and its optimiser state
+    def _fill(self):
+        B = self._phi.shape[0]
+        T, k, mk, lnA, lnR = self._start
+        aA, aR = dsp.drc_coeffs(self.sample_rate, self.init["attack_ms"], self.init["release_ms"])
+        self._phi.copy_(torch.from_numpy(np.broadcast_to(self._start.astype(np.float32), (B, 5)).copy()))
+        self._theta.copy_(torch.from_numpy(dsp.drc_table(T, k, aA, aR, mk, self.knee_db, B)))
+        self._m.zero_()
+        self._v.zero_()
+        self.k = 0
+
+    def _state(self, batch, device):
+        """The table with phi and its Adam moments on `device`; made on first use and when the batch or the device changes."""
+        if self._phi is None or self._phi.shape[0] != batch or self._phi.device != device:
+            self._phi, self._m, self._v = (torch.empty(batch, 5, dtype=torch.float32, device=device) for _ in range(3))
+            self._theta = torch.empty(batch, 8, dtype=torch.float32, device=device)
+            self._fill()
+        return self._theta
+
+    @property
+    def drc_estimate(self):
+        """(B, 5) float64 on the host in user units: threshold_db, ratio, makeup_db, attack_ms, release_ms; None before the first call."""
+        if self._phi is None:
+            return None
+        phi = self._phi.detach().cpu().numpy().astype(np.float64)
+        with np.errstate(divide="ignore"):
+            ratio = 1.0 / (1.0 - phi[:, 1])
+        return np.stack([phi[:, 0], ratio, phi[:, 2], dsp.drc_time_ms(np.exp(phi[:, 3]), self.sample_rate),
+                         dsp.drc_time_ms(np.exp(phi[:, 4]), self.sample_rate)], axis=1)
+
+    @property
+    def phi_estimate(self):
+        """(B, 5) fp32 on the GPU: T, k, makeup, ln aA, ln aR, updated in place by every guided step; None before the first call."""
+        return self._phi
+
+    @property
+    def table_estimate(self):
+        """(B, 8) fp32 on the GPU: the rows `drc_fwd_p` / `drc_bwd_p` read."""
+        return self._theta
+
+    def _to_start(self):
+        if self._phi is not None:
+            self._fill()
+        self.k = 0
+        self._kept = None
+
+    def reset_cache(self):
+        super().reset_cache()
+        self._to_start()
+
+    def restart(self):
+        self._to_start()
+
+    # ---- A
+    def forward(self, data, params=None, **kwargs):
+        if params is None:
+            if self.true_params is None:
+                raise ValueError("BlindDynamicRangeOperator.forward needs the true parameters of the measurement: params=dict(threshold_db, "
+                                 "ratio, attack_ms, release_ms, makeup_db); none was given and none is kept")
+            params = self.true_params
+        else:
+            self._fixed(params, "params")                        # refused by name before it is kept
+            params = self.true_params = dict(params)
+        return super().forward(data, params=params, **kwargs)
+
+    def apply(self, x, length, params=None, update_drc=True, **kw):
+        """params: the parameters of this call instead of the estimate, through the fixed route; the estimate is then neither used nor
+        updated."""
+        if params is not None:
+            fixed = self._fixed(params, "params")
+            y, state, tape = ops.hip.drc_fwd(x, int(length), *fixed)
+
+            def adjoint(dy, full):
+                return ops.hip.drc_bwd(dy, x, state, tape, int(full), *fixed)
+            return y, adjoint
+        theta, W = self._state(x.shape[0], x.device), self.knee_db
+        y, state, tape = ops.hip.drc_fwd_p(x, int(length), theta, W)
+
+        def adjoint(dy, full):
+            dx, work, bq0 = ops.hip.drc_bwd_p(dy, x, state, tape, theta, int(full), W)
+            self._kept = (state, tape, work, bq0)                # what after_cotangent turns into the parameter gradient
+            return dx
+        return y, adjoint
+
+    def after_cotangent(self, x, length, dy, params=None, update_drc=True, **kw):
+        """phi_k -> phi_{k+1}: the parameter gradient of this step's cotangent and one Adam + box step, two launches, no host sync."""
+        kept, self._kept = self._kept, None
+        if params is not None or not update_drc or kept is None:
+            return
+        state, tape, work, bq0 = kept
+        part = ops.hip.drc_pgrad(state, tape, work, bq0, self._theta, int(length), self.knee_db)
+        self.k += 1
+        ops.hip.drc_update(part, self._phi, self._m, self._v, self._theta, int(length), self.k, list(self.lr), self.betas[0], self.betas[1],
+                           self.adam_eps, self.knee_db, list(self.box_lo), list(self.box_hi))
+
+
+class StyleGuidanceOperator(BaseOperator):               # operator.py:253-271 (unrunnable in the reference: run.py:213-214)
     """Style guidance with BUILD-DEFINED semantics (the reference's `clap_model.get_gram_matrix`
     does not exist anywhere): `forward(x) = noiser(x)` (identity, operator.py:270-271) and
 

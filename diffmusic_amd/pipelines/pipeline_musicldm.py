@@ -21,8 +21,8 @@ from ..torch_utils import randn_tensor
 from ..profiling import stage
 from ..inverse_problem.noise import step_sigma
 from ..inverse_problem.mixture import MixtureOperator
-from ..inverse_problem.operator import BlindDereverberationOperator, BlindEqualizationOperator, BlindTimeWarpOperator, \
-    TimeFrequencyMaskOperator, TimeWarpOperator
+from ..inverse_problem.operator import BlindDereverberationOperator, BlindDynamicRangeOperator, BlindEqualizationOperator, \
+    BlindTimeWarpOperator, TimeFrequencyMaskOperator, TimeWarpOperator
 from .. import parallel
 
 
@@ -481,6 +481,13 @@ class MusicLDMPipeline:
                                  "position, and a lane sees only its own clips")
             if shard or group is not None:
                 raise ValueError("BlindTimeWarpOperator cannot be sharded over ranks (shard / group): its delay-curve estimates are indexed "
+                                 "by batch position, and a rank sees only its own clips")
+        if isinstance(op, BlindDynamicRangeOperator):
+            if int(self.lanes if lanes is None else lanes) > 1:
+                raise ValueError("BlindDynamicRangeOperator cannot run as clip lanes (lanes > 1): its parameter estimates are indexed by batch "
+                                 "position, and a lane sees only its own clips")
+            if shard or group is not None:
+                raise ValueError("BlindDynamicRangeOperator cannot be sharded over ranks (shard / group): its parameter estimates are indexed "
                                  "by batch position, and a rank sees only its own clips")
         if not isinstance(op, BlindDereverberationOperator):
             return

@@ -44,6 +44,12 @@ inside the guided loop): `--wow` / `--speed_pct` build the TRUE curve of the syn
 per coarse knot of the estimate, a power of two up to 64), `--warp_max_delay M` (samples, at most min(4096, 8 S)) and `--warp_lr`
 (samples per step) shape the fit; a flag that is not given takes its value from configs/inverse_problem/music_blind_wow_flutter.yaml.
 
+`-t music_blind_decompression` measures through a compressor whose settings the restoration does not know (BlindDynamicRangeOperator fits
+them inside the guided loop): the `--drc_*` flags above are the TRUE parameters of the synthetic measurement (`--drc_knee_db` is the knee
+width both sides share: it is given, not fitted), `--drc_fit threshold,ratio,makeup[,attack,release]` names the parameters that move, and
+`--drc_init_threshold_db`, `--drc_init_ratio`, `--drc_init_attack_ms`, `--drc_init_release_ms`, `--drc_init_makeup_db` say where the fit
+starts; a flag that is not given takes its value from configs/inverse_problem/music_blind_decompression.yaml.
+
 `-t music_source_separation` restores K stems from their mixture under one loss (inverse_problem/mixture.py), one prompt embedding per
 stem: `--wav` names the stems whose gain-weighted sum (`--gains`) is the measurement (SI-SDR per stem is printed), `--mixture mix.wav
 --stems K` separates a real mixture.  One file per stem is written; `--project` makes the stems sum to the mixture exactly.
@@ -67,25 +73,28 @@ from diffmusic_amd.schedulers import get_scheduler                              
 
 TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation", "music_declipping",
          "music_blind_dereverberation", "music_source_separation", "music_spectral_inpainting", "music_blind_equalization", "music_decompression",
-         "music_wow_flutter", "music_blind_wow_flutter")
+         "music_wow_flutter", "music_blind_wow_flutter", "music_blind_decompression")
 SEPARATION = "music_source_separation"
 SPECTRAL = "music_spectral_inpainting"
 BLIND_EQ = "music_blind_equalization"
 DECOMPRESSION = "music_decompression"
 WOW_FLUTTER = "music_wow_flutter"
 BLIND_WOW = "music_blind_wow_flutter"
+BLIND_DRC = "music_blind_decompression"
+DRC_INIT_FLAGS = ("threshold_db", "ratio", "attack_ms", "release_ms", "makeup_db")
 DRC_FLAGS = ("threshold_db", "ratio", "knee_db", "attack_ms", "release_ms", "makeup_db")
 
 
 def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None, tf_boxes=None, eq_true=None, drc=None, warp=None,
-                   blind_warp=None):
+                   blind_warp=None, blind_drc=None):
     """run.py:157-212: one operator per task, constructor arguments from the data / model config.  `audio_length_in_s`: the length the
     operator acts on when it is not the model window (a track).  `clip_threshold`: music_declipping's threshold(s), a float or one value
     per clip (`threshold_for_sdr` of the clean clips).  `tf_boxes`: music_spectral_inpainting's boxes (`spectral_boxes`).  `eq_true`:
     music_blind_equalization's true curve (`equalization_curve`), kept on the operator for `forward`.  `drc`: music_decompression's
     parameters (`compressor_params`).  `warp`: music_wow_flutter's speed components (`warp_params`); the delay curve is built here, for the
     length the operator acts on.  `blind_warp`: music_blind_wow_flutter's fit options (`blind_warp_params`); `warp` then describes the TRUE
-    curve, kept on the operator for `forward`."""
+    curve, kept on the operator for `forward`.  `blind_drc`: music_blind_decompression's `operator` keyword arguments and the `true`
+    parameters of the measurement (`blind_drc_params`), the latter kept on the operator for `forward`."""
     noiser = P.get_noiser(**cfg.inverse_problem.noise)
     d, scale = cfg.data, 1
     seconds = cfg.model.pipe.audio_length_in_s if audio_length_in_s is None else audio_length_in_s
@@ -138,6 +147,11 @@ def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=
                                      adam_eps=float(ip.get("adam_eps") or 1e-8), init=ip.get("init") or "zero",
                                      anchor=ip.get("anchor") or "mean", **blind_warp)
         op.true_delay = torch.from_numpy(P.wow_curve(int(seconds * d.sample_rate), d.sample_rate, **warp)).reshape(1, -1)
+    elif task == BLIND_DRC:
+        if blind_drc is None:
+            raise ValueError("music_blind_decompression needs blind_drc (blind_drc_params(args, cfg))")
+        op = P.BlindDynamicRangeOperator(sample_rate=d.sample_rate, noiser=noiser, **blind_drc["operator"])
+        op.true_params = dict(blind_drc["true"])
     else:
         raise ValueError(f"Unknown task: {task}")
     return op, scale
@@ -221,6 +235,12 @@ def parse_args(argv=None):
     for flag, what in zip(DRC_FLAGS, ("threshold in dB", "ratio >= 1, inf = a limiter", "knee width in dB, 0 = hard knee", "attack time in ms",
                                       "release time in ms", "make-up gain in dB")):
         ap.add_argument(f"--drc_{flag}", type=float, default=None, help=f"music_decompression: the compressor's {what} (default: the task's config)")
+    ap.add_argument("--drc_fit", default=None, metavar="NAME,NAME,...",
+                    help="music_blind_decompression: the parameters that are fitted, of threshold, ratio, makeup, attack, release "
+                         "(default: the task's config)")
+    for flag in DRC_INIT_FLAGS:
+        ap.add_argument(f"--drc_init_{flag}", type=float, default=None,
+                        help=f"music_blind_decompression: where the fit of {flag} starts (default: the task's config)")
     ap.add_argument("--wow", action="append", default=None, metavar="RATE_HZ,DEPTH_PCT[,PHASE_DEG]",
                     help="music_wow_flutter: one speed-modulation component (repeatable; default: the task's config)")
     ap.add_argument("--speed_pct", type=float, default=None, help="music_wow_flutter: constant speed error in percent (default: the task's config)")
@@ -339,8 +359,8 @@ def compressor_params(args, cfg=None):
     value by name.  Any other task refuses the flags."""
     given = {flag: getattr(args, f"drc_{flag}") for flag in DRC_FLAGS if getattr(args, f"drc_{flag}") is not None}
     if args.task != DECOMPRESSION:
-        if given:
-            raise SystemExit(f"--drc_{next(iter(given))} belongs to -t {DECOMPRESSION}")
+        if given and args.task != BLIND_DRC:                                       # there they describe the measurement (blind_drc_params)
+            raise SystemExit(f"--drc_{next(iter(given))} belongs to -t {DECOMPRESSION} and -t {BLIND_DRC}")
         return None
     out = {}
     if cfg is not None:
@@ -406,6 +426,44 @@ def blind_warp_params(args, cfg=None):
     except ValueError as e:
         raise SystemExit(f"-t {BLIND_WOW}: {e}")
     return out
+
+
+def blind_drc_params(args, cfg=None):
+    """The argument rules of -t music_blind_decompression -> dict(operator=the keyword arguments of the BlindDynamicRangeOperator, true=the
+    parameters of the synthetic measurement).  The --drc_* flags of music_decompression give the TRUE compressor (--drc_knee_db the knee
+    width both sides share), --drc_fit the fitted names and --drc_init_* the start; each falls back to the task's config and then to the
+    operator's defaults.  The operator's own refusals come here, before any GPU work.  Any other task refuses --drc_fit and --drc_init_*."""
+    init = {flag: getattr(args, f"drc_init_{flag}") for flag in DRC_INIT_FLAGS if getattr(args, f"drc_init_{flag}") is not None}
+    if args.task != BLIND_DRC:
+        if args.drc_fit is not None:
+            raise SystemExit(f"--drc_fit belongs to -t {BLIND_DRC}")
+        if init:
+            raise SystemExit(f"--drc_init_{next(iter(init))} belongs to -t {BLIND_DRC}")
+        return None
+    ip = cfg.inverse_problem if cfg is not None else {}
+    true = dict(P.BlindDynamicRangeOperator.INIT, threshold_db=-24.0, ratio=4.0, makeup_db=3.0)
+    true.update({k: float(v) for k, v in dict(ip.get("true") or {}).items()})
+    true.update({flag: getattr(args, f"drc_{flag}") for flag in DRC_INIT_FLAGS if getattr(args, f"drc_{flag}") is not None})
+    op_kw = {}
+    for name in ("lr", "betas", "adam_eps", "threshold_range", "makeup_range", "time_range_ms"):
+        if ip.get(name) is not None:
+            v = ip.get(name)
+            op_kw[name] = {k: float(x) for k, x in dict(v).items()} if name == "lr" else (float(v) if name == "adam_eps" else tuple(float(x) for x in v))
+    knee = args.drc_knee_db if args.drc_knee_db is not None else ip.get("knee_db")
+    if knee is not None:
+        op_kw["knee_db"] = float(knee)
+    fit = args.drc_fit.split(",") if args.drc_fit is not None else ip.get("fit")
+    if fit is not None:
+        op_kw["fit"] = tuple(str(n).strip() for n in fit)
+    start = {k: float(v) for k, v in dict(ip.get("init") or {}).items()}
+    start.update(init)
+    if start:
+        op_kw["init"] = start
+    try:
+        P.BlindDynamicRangeOperator(**op_kw)._fixed(true, "the measurement's --drc_* parameters")
+    except ValueError as e:
+        raise SystemExit(f"-t {BLIND_DRC}: {e}")
+    return dict(operator=op_kw, true=true)
 
 
 def separation_stems(args):
@@ -496,7 +554,8 @@ def run_separation(args, cfg, K):
 def main(argv=None):
     args = parse_args(argv)
     overrides = [f"data={args.data}", f"model={args.model}"]
-    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL, BLIND_EQ, DECOMPRESSION, WOW_FLUTTER, BLIND_WOW):
+    if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL, BLIND_EQ, DECOMPRESSION, WOW_FLUTTER, BLIND_WOW,
+                     BLIND_DRC):
         overrides.append(f"inverse_problem={args.task}")
     stems = separation_stems(args)
     if args.project and args.task not in ("music_declipping", SEPARATION):
@@ -507,6 +566,7 @@ def main(argv=None):
     drc = compressor_params(args, cfg)
     warp = warp_params(args, cfg, length=int(cfg.model.pipe.audio_length_in_s * cfg.data.sample_rate), sample_rate=cfg.data.sample_rate)
     blind_warp = blind_warp_params(args, cfg)
+    blind_drc = blind_drc_params(args, cfg)
     if stems is not None:
         if args.model != "musicldm":
             raise SystemExit("this driver feeds MusicLDM's class-embedding conditioning; AudioLDM2 needs its T5 / GPT-2 states (see bench.py --workload)")
@@ -524,7 +584,7 @@ def main(argv=None):
         gt = load_clips(args.wav, args.batch, sr, length, args.seed).to(device)
         thr = P.threshold_for_sdr(gt, args.clip_sdr_db) if args.task == "music_declipping" else None
         op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr, tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp,
-                                   blind_warp=blind_warp)
+                                   blind_warp=blind_warp, blind_drc=blind_drc)
         B = gt.shape[0]
     else:
         if args.task == "music_generation":
@@ -534,7 +594,8 @@ def main(argv=None):
         layout = P.TrackLayout(T, length, int(round(args.track_overlap_s * sr)))
         thr = float(P.threshold_for_sdr(gt, args.clip_sdr_db)[0]) if args.task == "music_declipping" else None
         inner, scale = build_operator(args.task, cfg, args.mask_type, audio_length_in_s=P.seconds_for_samples(T, sr), clip_threshold=thr,
-                                      tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp, blind_warp=blind_warp)
+                                      tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp, blind_warp=blind_warp,
+                                      blind_drc=blind_drc)
         op = P.TrackOperator(inner, layout)
         B = layout.num_windows
         sched_kw["per_clip_norm"] = False                                          # one loss, norms over all windows
@@ -585,6 +646,11 @@ def main(argv=None):
         true = true - true.mean(dim=1, keepdim=True) if blind.anchor == "mean" else true      # a constant delay is not identified
         err = torch.linalg.vector_norm(est - true, dim=1) / torch.linalg.vector_norm(true, dim=1).clamp_min(1e-30)
         print("delay curve estimate, relative error per clip (mean removed): " + " ".join(f"{e:.3f}" for e in err.tolist()))
+    if isinstance(blind, P.BlindDynamicRangeOperator) and blind.true_params is not None and blind.drc_estimate is not None:
+        t = blind.true_params                                                      # the synthetic measurement knows its compressor
+        print(f"compressor estimate per clip (threshold_db, ratio, makeup_db, attack_ms, release_ms); true {t['threshold_db']:g}, "
+              f"{t['ratio']:g}, {t['makeup_db']:g}, {t['attack_ms']:g}, {t['release_ms']:g}: "
+              + "; ".join(", ".join(f"{v:.3g}" for v in row) for row in blind.drc_estimate))
     ref = gt.cpu().numpy()
     print(f"wrote {B} clip(s) to {out}; LSD {LogSpectralDistance().score(ref, audio[:, :length]):.4f}  MSE {MeanSquaredError().score(ref, audio[:, :length]):.6f}")
 

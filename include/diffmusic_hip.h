@@ -36,7 +36,8 @@ extern "C" {
  * dmx_audio_tf_frames (time-frequency masking: a real gain on the STFT) and dmx_audio_tf_curve / dmx_audio_tf_wgrad /
  * dmx_audio_tf_wgrad_segments / dmx_audio_eq_update (blind equalisation: a fitted gain curve per clip) and dmx_drc_fwd / dmx_drc_bwd
  * (de-compression: a dynamic-range compressor and the transpose of its Jacobian) and dmx_warp_fwd / dmx_warp_bwd (wow and flutter: a clip
- * read along a delay curve, and the transpose) and dmx_warp_wgrad / dmx_warp_update (blind wow and flutter: the delay curve fitted) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * read along a delay curve, and the transpose) and dmx_warp_wgrad / dmx_warp_update (blind wow and flutter: the delay curve fitted) and dmx_drc_fwd_p / dmx_drc_bwd_p / dmx_drc_pgrad /
+ * dmx_drc_update (blind de-compression: the compressor's parameters per clip on the device, and fitted) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
  * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
@@ -281,6 +282,33 @@ int dmx_drc_fwd(const float* x, long long x_stride, float* y, long long y_stride
 int dmx_drc_bwd(const float* dy, long long dy_stride, const float* x, long long x_stride, const float* state, const unsigned char* tape,
                 float* work, float* dx, long long dx_stride, int batch, int L, int Lfull, float threshold_db, float slope, float knee_db,
                 float a_att, float a_rel, float makeup_db, void* stream);
+/* Blind de-compression (csrc/drc.hip, csrc/drc_fit.hip): the compressor above with one parameter row per clip on
+ * the device, and those rows fitted inside the guided loop.  theta (batch, 8) fp32 contiguous holds T, k, makeup, aA, aR, 1 - aA, 1 - aR,
+ * k / (2 knee_db) (0 when knee_db = 0), the derived entries computed in double and rounded once; knee_db stays a host scalar.
+ *   drc_fwd_p   dmx_drc_fwd with the parameters of clip b read from theta[b]: the same three launches and the same arithmetic, so a table
+ *               whose rows all hold the parameters of a dmx_drc_fwd call gives y, state and tape bit-equal to it.
+ *   drc_bwd_p   dmx_drc_bwd likewise (dx bit-equal on such a table); it keeps what the parameter gradient needs: work is (batch, 2, H), row 0
+ *               ds and row 1 dc, and bq0 (batch,) receives Bq[0] = sum_r dy[r] x[r] (1 - (r + 1) / 64) of each clip.
+ *               The table's values are operands only, never indices.  A row with a non-finite entry makes y, G, s and dx of that clip NaN
+ *               from block 0 on; other clips are untouched.
+ *   drc_pgrad   the gradient in phi = (T, k, makeup, ln aA, ln aR) of the loss whose cotangent dmx_drc_bwd_p was given, as partial rows
+ *               part (batch, ceil(H / 256), 5), one per segment of 256 blocks; the gradient is their sum over the segments.  A fixed
+ *               reduction order, no atomics: the same bits whatever the batch and the clip's place in it.
+ *   drc_update  adds a clip's partial rows in ascending order, takes one Adam step per parameter with the arithmetic of dmx_ir_update
+ *               (csrc/adam_step.h) and its own lr[q] (0 freezes parameter q: value, moments and table entries keep their bits), clamps to
+ *               [lo[q], hi[q]] and rewrites the clip's row of theta; phi, m, v (batch, 5) and theta are updated in place, k is the 1-based
+ *               count of updates.  A clip with a non-finite gradient or step keeps all four untouched (decided on the device).
+ * DMX_ERR_SHAPE, with nothing written, for what dmx_drc_fwd / dmx_drc_bwd refuse, a null table, knee_db outside [0, 200], k < 1, an lr
+ * that is negative or not finite, a beta outside [0, 1), eps < 0, or a box outside T, makeup in +-200, slope in [0, 1], ln a in [-80, 0]. */
+int dmx_drc_fwd_p(const float* x, long long x_stride, float* y, long long y_stride, float* state, unsigned char* tape, const float* theta,
+                  int batch, int L, float knee_db, void* stream);
+int dmx_drc_bwd_p(const float* dy, long long dy_stride, const float* x, long long x_stride, const float* state, const unsigned char* tape,
+                  const float* theta, float* work, float* bq0, float* dx, long long dx_stride, int batch, int L, int Lfull, float knee_db,
+                  void* stream);
+int dmx_drc_pgrad(const float* state, const unsigned char* tape, const float* work, const float* bq0, const float* theta, float* part,
+                  int batch, int L, float knee_db, void* stream);
+int dmx_drc_update(const float* part, float* phi, float* m, float* v, float* theta, int batch, int L, int k, const double* lr, double beta1,
+                   double beta2, double eps, float knee_db, const double* lo, const double* hi, void* stream);
 /* Wow and flutter on materialised waveforms (csrc/warp.hip): the clip, taken as zero outside [0, L), read at
  * n + delta(n), where delta is linear between the H + 1 knots of `delay` (fp32, in samples, one knot per 64 samples, H = ceil(L / 64));
  * four-point Catmull-Rom on the taps i - 1 .. i + 2, i = n + floor(delta), a tap outside the clip skipped.  delay_stride = 0: one curve for
