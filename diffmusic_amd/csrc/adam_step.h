@@ -1,5 +1,5 @@
-// One Adam step of one parameter in fp32, shared by the two blind operators' update kernels (fir_blind.hip: the taps of an impulse response;
-// tf_eq.hip: the bins of an equalisation curve): both include this header, so they run the same arithmetic in the same order.
+// One Adam step of one parameter in fp32, shared by the four blind operators' update kernels (fir_blind.hip: the taps of an impulse response;
+// tf_eq.hip: the bins of a curve; warp_fit.hip: delay knots; drc_fit.hip: compressor parameters): same arithmetic, same order, in all four.
 #pragma once
 #include <cmath>
 #include "dmx_common.h"

@@ -21,8 +21,6 @@ from ..torch_utils import randn_tensor
 from ..profiling import stage
 from ..inverse_problem.noise import step_sigma
 from ..inverse_problem.mixture import MixtureOperator
-from ..inverse_problem.operator import BlindDereverberationOperator, BlindDynamicRangeOperator, BlindEqualizationOperator, \
-    BlindTimeWarpOperator, TimeFrequencyMaskOperator, TimeWarpOperator
 from .. import parallel
 
 
@@ -449,54 +447,21 @@ class MusicLDMPipeline:
             restart()
 
     def _check_positional_state(self, shard, group, lanes):
-        """An operator that keeps per-clip state by batch position (the blind dereverberation's response estimates, the blind equalisation's curves) sees every clip of the
-        call in one batch, in call order: no clip lanes, no clip sharding."""
+        """An operator that keeps per-clip state by batch position (`BaseOperator.positional_state`: the estimates of a blind operator, per-clip
+        gains or delay curves) sees every clip of the call in one batch, in call order: no clip lanes, no clip sharding."""
         op = self.scheduler.operator
         while hasattr(op, "inner"):                              # the measurement operator inside a track, a mixture, or both
             op = op.inner
-        if isinstance(op, TimeFrequencyMaskOperator) and op.per_clip:     # (one shared grid has no per-position state)
-            if int(self.lanes if lanes is None else lanes) > 1:
-                raise ValueError("TimeFrequencyMaskOperator with per-clip gains cannot run as clip lanes (lanes > 1): its gains are indexed "
-                                 "by batch position, and a lane sees only its own clips")
-            if shard or group is not None:
-                raise ValueError("TimeFrequencyMaskOperator with per-clip gains cannot be sharded over ranks (shard / group): its gains are "
-                                 "indexed by batch position, and a rank sees only its own clips")
-        if isinstance(op, TimeWarpOperator) and op.per_clip:              # (one shared curve has no per-position state)
-            if int(self.lanes if lanes is None else lanes) > 1:
-                raise ValueError("TimeWarpOperator with per-clip delay curves cannot run as clip lanes (lanes > 1): its curves are indexed "
-                                 "by batch position, and a lane sees only its own clips")
-            if shard or group is not None:
-                raise ValueError("TimeWarpOperator with per-clip delay curves cannot be sharded over ranks (shard / group): its curves are "
-                                 "indexed by batch position, and a rank sees only its own clips")
-        if isinstance(op, BlindEqualizationOperator):
-            if int(self.lanes if lanes is None else lanes) > 1:
-                raise ValueError("BlindEqualizationOperator cannot run as clip lanes (lanes > 1): its curve estimates are indexed by batch "
-                                 "position, and a lane sees only its own clips")
-            if shard or group is not None:
-                raise ValueError("BlindEqualizationOperator cannot be sharded over ranks (shard / group): its curve estimates are indexed "
-                                 "by batch position, and a rank sees only its own clips")
-        if isinstance(op, BlindTimeWarpOperator):
-            if int(self.lanes if lanes is None else lanes) > 1:
-                raise ValueError("BlindTimeWarpOperator cannot run as clip lanes (lanes > 1): its delay-curve estimates are indexed by batch "
-                                 "position, and a lane sees only its own clips")
-            if shard or group is not None:
-                raise ValueError("BlindTimeWarpOperator cannot be sharded over ranks (shard / group): its delay-curve estimates are indexed "
-                                 "by batch position, and a rank sees only its own clips")
-        if isinstance(op, BlindDynamicRangeOperator):
-            if int(self.lanes if lanes is None else lanes) > 1:
-                raise ValueError("BlindDynamicRangeOperator cannot run as clip lanes (lanes > 1): its parameter estimates are indexed by batch "
-                                 "position, and a lane sees only its own clips")
-            if shard or group is not None:
-                raise ValueError("BlindDynamicRangeOperator cannot be sharded over ranks (shard / group): its parameter estimates are indexed "
-                                 "by batch position, and a rank sees only its own clips")
-        if not isinstance(op, BlindDereverberationOperator):
+        state = getattr(op, "positional_state", None)            # the operator says so itself; a stand-in without the attribute has none
+        if state is None:
             return
+        who, what = state
         if int(self.lanes if lanes is None else lanes) > 1:
-            raise ValueError("BlindDereverberationOperator cannot run as clip lanes (lanes > 1): its response estimates are indexed by batch "
-                             "position, and a lane sees only its own clips")
+            raise ValueError(f"{who} cannot run as clip lanes (lanes > 1): its {what} are indexed by batch position, and a lane sees only its "
+                             "own clips")
         if shard or group is not None:
-            raise ValueError("BlindDereverberationOperator cannot be sharded over ranks (shard / group): its response estimates are indexed "
-                             "by batch position, and a rank sees only its own clips")
+            raise ValueError(f"{who} cannot be sharded over ranks (shard / group): its {what} are indexed by batch position, and a rank sees "
+                             "only its own clips")
 
     # ---- track mode -------------------------------------------------------------------------
     def _check_track(self, track, B_all, length, shard, group, lanes):
