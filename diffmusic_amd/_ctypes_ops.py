@@ -455,6 +455,69 @@ def warp_update(part, coarse, m, v, fine, length, knot_stride, k, lr, beta1, bet
                                           float(beta1), float(beta2), float(eps), float(max_delay), 1 if mean else 0, _stream()), "warp_update")
 
 
+def _click_mask_stride(who, mask, like, B, L):
+    assert mask.is_cuda and mask.device == like.device and mask.dtype == torch.float32 and mask.is_contiguous() and \
+        tuple(mask.shape) in ((L,), (B, L)), (who, tuple(mask.shape), "expected", (L,), "or", (B, L))
+    return 0 if mask.dim() == 1 else L
+
+
+def click_detect(y, L, threshold, sigma_floor):
+    """y (B, >= L) with any row stride -> (a (B, F, 16), e (B, L), sigma (B, F), flags (B, L) uint8, r (B, F, 17)), F = ceil(L / 1024): the
+    autoregressive click detector of csrc/declick.hip, frame by frame -- autocorrelation, predictor, residual, robust scale, flags."""
+    if not y.is_cuda:
+        raise RuntimeError("click_detect: tensors must be on the GPU (no CPU fallback)")
+    assert y.dtype == torch.float32 and y.dim() == 2 and y.stride(1) == 1 and y.shape[1] >= L >= 1 and L <= 1 << 30, ("click_detect", y.shape, L)
+    B, F = y.shape[0], -(-L // 1024)
+    f32 = dict(dtype=torch.float32, device=y.device)
+    a, e, sigma, r = torch.empty(B, F, 16, **f32), torch.empty(B, L, **f32), torch.empty(B, F, **f32), torch.empty(B, F, 17, **f32)
+    flags = torch.empty(B, L, dtype=torch.uint8, device=y.device)
+    _lib.check(_lib.lib().dmx_click_detect(_p(y), y.stride(0), _p(a), _p(e), _p(sigma), _p(flags), _p(r), min(B, 65536), L, threshold, sigma_floor,
+                                           _stream()), "click_detect")
+    return a, e, sigma, flags, r
+
+
+def click_mask(flags, guard):
+    """flags (B, L) contiguous uint8 -> (mask (B, L) fp32: 0 within `guard` samples of a flag, else 1; masked (B) int32: the zeros per clip)."""
+    if not flags.is_cuda:
+        raise RuntimeError("click_mask: tensors must be on the GPU (no CPU fallback)")
+    assert flags.dtype == torch.uint8 and flags.dim() == 2 and flags.is_contiguous() and 1 <= flags.shape[1] <= 1 << 30, ("click_mask", flags.shape)
+    B, L = flags.shape
+    mask = torch.empty(B, L, dtype=torch.float32, device=flags.device)
+    masked = torch.empty(B, dtype=torch.int32, device=flags.device)
+    _lib.check(_lib.lib().dmx_click_mask(_p(flags), _p(mask), _p(masked), min(B, 65536), L, max(min(int(guard), 1 << 20), -1), _stream()),
+               "click_mask")
+    return mask, masked
+
+
+def mask_rows(x, mask, L, Ly):
+    """x (B, >= L) with any row stride, mask (L) for every clip or (B, L) contiguous -> (B, Ly): x[:, :L] * mask, zeros on [L, Ly)."""
+    if not x.is_cuda:
+        raise RuntimeError("mask_rows: tensors must be on the GPU (no CPU fallback)")
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] >= L >= 1 and L <= Ly <= 1 << 30, \
+        ("mask_rows", x.shape, L, Ly)
+    B = x.shape[0]
+    ms = _click_mask_stride("mask_rows", mask, x, B, L)
+    y = torch.empty(B, Ly, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_mask_rows(_p(x), x.stride(0), _p(mask), ms, _p(y), min(B, 65536), L, Ly, _stream()), "mask_rows")
+    return y
+
+
+def declick_blend(x, y, mask, L, fade):
+    """x (restored) and y (measurement) (B, >= L) with any row strides, mask (L) or (B, L) -> (B, L): y away from the mask's zeros, x on them,
+    a linear cross-fade over `fade` samples on each side."""
+    if not x.is_cuda:
+        raise RuntimeError("declick_blend: tensors must be on the GPU (no CPU fallback)")
+    for t in (x, y):
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[1] >= L >= 1 and L <= 1 << 30, ("declick_blend", t.shape, L)
+    assert y.shape[0] == x.shape[0] and y.device == x.device, (x.shape, y.shape)
+    B = x.shape[0]
+    ms = _click_mask_stride("declick_blend", mask, x, B, L)
+    out = torch.empty(B, L, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().dmx_declick_blend(_p(x), x.stride(0), _p(y), y.stride(0), _p(mask), ms, _p(out), min(B, 65536), L,
+                                            max(min(int(fade), 1 << 20), -1), _stream()), "declick_blend")
+    return out
+
+
 def tf_gain(audio, x, gain_t, L, Lfull, *, out=None):
     """x (B, >= L) with any row stride, gain_t (frames, 513) shared or (B, frames, 513), frames = ceil(L / 256) + 3 -> (B, Lfull): the
     time-frequency gain A(x[:, :L]) (csrc/tf_gain.hip), +0 past L.  A is symmetric: the same call is the transpose.

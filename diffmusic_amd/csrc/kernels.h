@@ -128,6 +128,13 @@ constexpr int DMX_WARP_BLOCK = 64;                       // samples per knot int
 // projection update of a coarse curve with its expansion into the fine one; one launch each).  No handle either: its launchers are the C
 // ABI's own dmx_warp_wgrad / dmx_warp_update; the position arithmetic is warp.hip's, from warp_common.h
 
+// ---- declick.hip (declicking: the autoregressive click detector, the dilation of its flags into a per-clip sample mask, the per-clip mask
+// product and the output blend; one launch each).  No handle: its launchers are the C ABI's own dmx_click_detect / dmx_click_mask /
+// dmx_mask_rows / dmx_declick_blend
+constexpr int DMX_CLICK_FRAME = 1024;                    // samples per frame; a (B, F, 16), sigma (B, F), F = ceil(L / 1024)
+constexpr int DMX_CLICK_ORDER = 16;                      // order of the autoregressive model
+constexpr int DMX_CLICK_MAX_GUARD = 64;                  // largest guard (click_mask) and fade (declick_blend)
+
 // ---- sched.hip
 int dmx_pred_x0(const float* x, const float* eps, float* x0, long long n, float sqrt_a, float sqrt_1ma, hipStream_t st);
 int dmx_pred_x0_ex(const float* x, const float* m, float* x0, long long n, float sqrt_a, float sqrt_1ma, int ptype, float clip_r, hipStream_t st);

@@ -54,6 +54,10 @@
 #pragma weak dmx_drc_bwd_p
 #pragma weak dmx_drc_pgrad
 #pragma weak dmx_drc_update
+#pragma weak dmx_click_detect
+#pragma weak dmx_click_mask
+#pragma weak dmx_mask_rows
+#pragma weak dmx_declick_blend
 
 namespace {
 
@@ -527,6 +531,57 @@ void warp_update(const at::Tensor& part, at::Tensor coarse, at::Tensor m, at::Te
   ok(dmx_warp_update(part.data_ptr<float>(), coarse.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), fine.data_ptr<float>(), (int)B,
                      (int)length, (int)knot_stride, (int)k, lr, beta1, beta2, eps, max_delay, mean ? 1 : 0, cur_stream()), "warp_update");
 }
+// declicking (include/diffmusic_hip.h dmx_click_detect / dmx_click_mask / dmx_mask_rows / dmx_declick_blend): y (B, >= L) -> a (B, F, 16),
+// e (B, L), sigma (B, F), flags (B, L) uint8, r (B, F, 17), F = ceil(L / 1024); flags -> mask (B, L) fp32 and masked (B) int32; the mask
+// is (L) for every clip or (B, L), contiguous
+static int64_t click_mask_stride(const at::Tensor& mask, int64_t B, int64_t L, const at::Tensor& like) {
+  f32_cuda(mask, "mask");
+  TORCH_CHECK(mask.device() == like.device() && ((mask.dim() == 1 && mask.size(0) == L) || (mask.dim() == 2 && mask.size(0) == B && mask.size(1) == L)),
+              "mask must be (", L, ") or (", B, ", ", L, ") on the clips' device");
+  return mask.dim() == 1 ? 0 : L;
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> click_detect(const at::Tensor& y, int64_t L, double threshold, double sigma_floor) {
+  rows_ok(y, L, "y");
+  TORCH_CHECK(L <= (int64_t(1) << 30), "L must be <= 2^30");
+  DMX_DEVICE_OF(y);
+  const int64_t B = y.size(0), F = (L + 1023) / 1024;
+  at::Tensor a = at::empty({B, F, 16}, y.options()), e = at::empty({B, L}, y.options()), sigma = at::empty({B, F}, y.options());
+  at::Tensor flags = at::empty({B, L}, y.options().dtype(at::kByte)), r = at::empty({B, F, 17}, y.options());
+  ok(dmx_click_detect(y.data_ptr<float>(), y.stride(0), a.data_ptr<float>(), e.data_ptr<float>(), sigma.data_ptr<float>(), flags.data_ptr<uint8_t>(),
+                      r.data_ptr<float>(), (int)std::min<int64_t>(B, 65536), (int)L, (float)threshold, (float)sigma_floor, cur_stream()), "click_detect");
+  return {a, e, sigma, flags, r};
+}
+std::tuple<at::Tensor, at::Tensor> click_mask(const at::Tensor& flags, int64_t guard) {
+  TORCH_CHECK(flags.is_cuda(), "flags must be a GPU tensor (the diffmusic_hip ops have no CPU fallback)");
+  TORCH_CHECK(flags.scalar_type() == at::kByte && flags.is_contiguous() && flags.dim() == 2 && flags.size(1) >= 1 && flags.size(1) <= (int64_t(1) << 30),
+              "flags must be contiguous uint8 (B, L), 1 <= L <= 2^30");
+  DMX_DEVICE_OF(flags);
+  const int64_t B = flags.size(0), L = flags.size(1);
+  at::Tensor mask = at::empty({B, L}, flags.options().dtype(at::kFloat)), masked = at::empty({B}, flags.options().dtype(at::kInt));
+  ok(dmx_click_mask(flags.data_ptr<uint8_t>(), mask.data_ptr<float>(), masked.data_ptr<int>(), (int)std::min<int64_t>(B, 65536), (int)L,
+                    (int)std::max<int64_t>(std::min<int64_t>(guard, 1 << 20), -1), cur_stream()), "click_mask");
+  return {mask, masked};
+}
+at::Tensor mask_rows(const at::Tensor& x, const at::Tensor& mask, int64_t L, int64_t Ly) {
+  rows_ok(x, L, "x");
+  TORCH_CHECK(Ly >= L && Ly <= (int64_t(1) << 30), "Ly must be in L .. 2^30");
+  const int64_t B = x.size(0), ms = click_mask_stride(mask, B, L, x);
+  DMX_DEVICE_OF(x);
+  at::Tensor y = at::empty({B, Ly}, x.options());
+  ok(dmx_mask_rows(x.data_ptr<float>(), x.stride(0), mask.data_ptr<float>(), ms, y.data_ptr<float>(), (int)std::min<int64_t>(B, 65536), (int)L, (int)Ly,
+                   cur_stream()), "mask_rows");
+  return y;
+}
+at::Tensor declick_blend(const at::Tensor& x, const at::Tensor& y, const at::Tensor& mask, int64_t L, int64_t fade) {
+  rows_ok(x, L, "x"); rows_ok(y, L, "y");
+  TORCH_CHECK(L <= (int64_t(1) << 30) && y.size(0) == x.size(0) && y.device() == x.device(), "y must hold x's clips, L <= 2^30");
+  const int64_t B = x.size(0), ms = click_mask_stride(mask, B, L, x);
+  DMX_DEVICE_OF(x);
+  at::Tensor out = at::empty({B, L}, x.options());
+  ok(dmx_declick_blend(x.data_ptr<float>(), x.stride(0), y.data_ptr<float>(), y.stride(0), mask.data_ptr<float>(), ms, out.data_ptr<float>(),
+                       (int)std::min<int64_t>(B, 65536), (int)L, (int)std::max<int64_t>(std::min<int64_t>(fade, 1 << 20), -1), cur_stream()), "declick_blend");
+  return out;
+}
 // time-frequency gain (include/diffmusic_hip.h dmx_audio_tf_gain): x (B, >= L), gain_t (frames, 513) shared or (B, frames, 513) -> (B, Lfull)
 // out: caller-owned (B, >= Lfull) fp32 with any row stride; only out[:, :Lfull] is written
 at::Tensor tf_gain(int64_t audio, const at::Tensor& x, const at::Tensor& gain_t, int64_t L, int64_t Lfull, const std::optional<at::Tensor>& out) {
@@ -877,10 +932,14 @@ TORCH_LIBRARY(diffmusic_hip, m) {
                                                          {"dmx_drc_fwd_p", (const void*)&dmx_drc_fwd_p},
                                                          {"dmx_drc_bwd_p", (const void*)&dmx_drc_bwd_p},
                                                          {"dmx_drc_pgrad", (const void*)&dmx_drc_pgrad},
-                                                         {"dmx_drc_update", (const void*)&dmx_drc_update}};
+                                                         {"dmx_drc_update", (const void*)&dmx_drc_update},
+                                                         {"dmx_click_detect", (const void*)&dmx_click_detect},
+                                                         {"dmx_click_mask", (const void*)&dmx_click_mask},
+                                                         {"dmx_mask_rows", (const void*)&dmx_mask_rows},
+                                                         {"dmx_declick_blend", (const void*)&dmx_declick_blend}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
-                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter / blind-wow-and-flutter / blind-de-compression entry points): rebuild with `python -m diffmusic_amd.build --force`");
+                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter / blind-wow-and-flutter / blind-de-compression / declicking entry points): rebuild with `python -m diffmusic_amd.build --force`");
   }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
@@ -925,6 +984,10 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("warp_wgrad(Tensor dy, Tensor x, Tensor delay, int length) -> Tensor", &warp_wgrad);
   m.def("warp_update(Tensor part, Tensor(a!) coarse, Tensor(b!) m, Tensor(c!) v, Tensor(d!) fine, int length, int knot_stride, int k, float lr, "
         "float beta1, float beta2, float eps, float max_delay, bool mean) -> ()", &warp_update);
+  m.def("click_detect(Tensor y, int L, float threshold, float sigma_floor) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", &click_detect);
+  m.def("click_mask(Tensor flags, int guard) -> (Tensor, Tensor)", &click_mask);
+  m.def("mask_rows(Tensor x, Tensor mask, int L, int Ly) -> Tensor", &mask_rows);
+  m.def("declick_blend(Tensor x, Tensor y, Tensor mask, int L, int fade) -> Tensor", &declick_blend);
   m.def("noise_add(Tensor y, Tensor noise, float sigma) -> Tensor", &noise_add);
   m.def("tf_gain(int audio, Tensor x, Tensor gain_t, int L, int Lfull, *, Tensor(a!)? out=None) -> Tensor", &tf_gain);
   m.def("tf_curve(int audio, Tensor x, Tensor curve, int L, int Lfull) -> Tensor", &tf_curve);

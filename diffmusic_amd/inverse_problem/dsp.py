@@ -294,3 +294,59 @@ def wow_curve(length, sample_rate, components=(), speed_percent=0.0):
         w = 2.0 * math.pi * rate
         delta = delta + depth / 100.0 * (np.sin(w * t + phase) - math.sin(phase)) / w
     return check_warp_curve((sample_rate * delta).astype(np.float32), "wow_curve")
+
+
+# ---- declicking (DeclickOperator, csrc/declick.hip)
+CLICK_FRAME, CLICK_ORDER, CLICK_MAX_GUARD = 1024, 16, 64
+
+
+def check_declick(threshold, sigma_floor, guard):
+    """-> (threshold, sigma_floor, guard) as the kernels take them (fp32-rounded floats, an int), or a ValueError naming the argument."""
+    try:
+        t = float(np.float32(threshold))
+    except (TypeError, ValueError):
+        t = float("nan")
+    if not (math.isfinite(t) and t > 0):
+        raise ValueError(f"threshold = {threshold!r}: a finite number > 0 (the multiple of the robust scale above which a residual is a click)")
+    try:
+        f = float(np.float32(sigma_floor))
+    except (TypeError, ValueError):
+        f = float("nan")
+    if not (math.isfinite(f) and f >= 0):
+        raise ValueError(f"sigma_floor = {sigma_floor!r}: a finite number >= 0 (the smallest robust scale a frame is given)")
+    if isinstance(guard, bool) or not isinstance(guard, (int, np.integer)) or not 0 <= int(guard) <= CLICK_MAX_GUARD:
+        raise ValueError(f"guard = {guard!r}: an integer in 0 .. {CLICK_MAX_GUARD} (samples hidden on each side of a flagged one)")
+    return t, f, int(guard)
+
+
+def check_declick_fade(fade):
+    if isinstance(fade, bool) or not isinstance(fade, (int, np.integer)) or not 0 <= int(fade) <= CLICK_MAX_GUARD:
+        raise ValueError(f"fade = {fade!r}: an integer in 0 .. {CLICK_MAX_GUARD} (samples of cross-fade on each side of a masked run)")
+    return int(fade)
+
+
+def click_train(length, sample_rate, rate_hz, amplitude=(0.3, 0.6), max_width=3, seed=0, batch=1):
+    """-> (batch, length) fp32 tensor of seeded sparse clicks for synthetic measurements: per clip round(rate_hz * length / sample_rate)
+    clicks at uniform random positions, each with a random sign, an amplitude uniform in [lo, hi] and a width of 1 .. max_width samples
+    (cut at the clip's end).  The same arguments give the same tensor; clip b depends on (seed, b) only."""
+    lo, hi = (float(amplitude[0]), float(amplitude[1]))
+    if not (isinstance(length, (int, np.integer)) and length >= 1 and isinstance(batch, (int, np.integer)) and batch >= 1):
+        raise ValueError(f"length = {length!r}, batch = {batch!r}: positive integers")
+    if not (math.isfinite(float(sample_rate)) and float(sample_rate) > 0 and math.isfinite(float(rate_hz)) and float(rate_hz) >= 0):
+        raise ValueError(f"sample_rate = {sample_rate!r}, rate_hz = {rate_hz!r}: a positive rate and a click rate >= 0")
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0 <= lo <= hi):
+        raise ValueError(f"amplitude = {amplitude!r}: (lo, hi) with 0 <= lo <= hi")
+    if not (isinstance(max_width, (int, np.integer)) and max_width >= 1):
+        raise ValueError(f"max_width = {max_width!r}: an integer >= 1")
+    count = int(round(float(rate_hz) * length / float(sample_rate)))
+    out = np.zeros((int(batch), int(length)), dtype=np.float32)
+    for b in range(int(batch)):
+        rng = np.random.default_rng([int(seed), b])
+        pos = rng.integers(0, length, size=count)
+        sign = rng.integers(0, 2, size=count) * 2 - 1
+        amp = rng.uniform(lo, hi, size=count)
+        width = rng.integers(1, int(max_width) + 1, size=count)
+        for p, s, a, w in zip(pos, sign, amp, width):
+            out[b, p:min(p + w, length)] = np.float32(s * a)
+    import torch
+    return torch.from_numpy(out)

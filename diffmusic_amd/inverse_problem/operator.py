@@ -798,6 +798,151 @@ class TimeWarpOperator(_MelOperator):
         return ops.hip.warp_fwd(x, d, int(length)), adjoint
 
 
+class DeclickOperator(_MelOperator):
+    """Declicking (extension): impulsive noise -- clicks, crackle, ticks, digital dropouts -- of a vinyl, tape or cassette transfer.  The
+    model is y = x + sigma z + clicks with clicks nobody knows: the damaged samples are FOUND, by the autoregressive detector of
+    csrc/declick.hip (a click is a sample the recent past cannot predict), and hidden from the loss by a 0/1 mask m
+    with one row per clip.  The mask is a weight of the loss, not part of the degradation, so both sides carry it:
+
+        wav_form          || m (x^ + sigma z - y) ||
+        mel_spectrogram   || T(m y) - T(m (x^ + sigma z)) ||      T = clamp(wav2mel, -80, 80) like the IdentityOperator's
+
+    The step's noise is added BEFORE the mask.  A is materialised (`_on_load` is None): a guided step is the identity's plus two `mask_rows`
+    launches.  `forward(data, clicks=None)` = noiser(data + clicks) makes a synthetic measurement (`dsp.click_train` draws the clicks).
+
+    The mask: with mask=None it is detected from the measurement on its first use and kept WITH the reference transform -- one entry of
+    `BaseOperator._ref`'s cache holds both, so the rule is the same (keyed by the measurement tensor and its version, four entries,
+    `cache_reference=False` re-detects every step).  It is a function of the measurement's rows alone: no positional state, so clip lanes
+    and sharding work, and inside a TrackOperator detection runs on the (1, T) track.  `mask=` pins one instead: (L,) for every clip or
+    (B, L), values 0 / 1, checked here by name; a (B, L) one is indexed by batch position (`positional_state`).  `last_masked_fraction` is
+    the share of zeros of the last detection: one host read per detection, never per step.
+
+    Limits: percussive onsets can be flagged (`threshold` is the knob); detection happens once, from y alone; bursts much longer than the
+    model order (16 samples) are a job for the inpainting or time-frequency-mask operators.  `dead_span` is None."""
+
+    def __init__(self, sample_rate=16000, threshold=5.0, sigma_floor=1e-5, guard=3, mask=None, noiser=None):
+        if not (math.isfinite(float(sample_rate)) and float(sample_rate) > 0):
+            raise ValueError(f"sample_rate = {sample_rate!r}: a positive finite rate")
+        self.threshold, self.sigma_floor, self.guard = dsp.check_declick(threshold, sigma_floor, guard)
+        self.sample_rate, self.noiser = sample_rate, noiser
+        self.mask = None
+        if mask is not None:
+            m = torch.as_tensor(mask).detach().to(device="cpu")
+            if m.dim() not in (1, 2) or m.numel() < 1:
+                raise ValueError(f"mask has shape {tuple(m.shape)}: (L,) for every clip or (B, L)")
+            if not bool(((m == 0) | (m == 1)).all()):
+                raise ValueError("mask: values 0 (hidden from the loss) or 1 (kept)")
+            self.mask = m.to(torch.float32).contiguous().clone()      # host copy
+        self._mask_dev = None
+        self.last_masked_fraction = None
+        self._init_mel(sample_rate, lazy=True)
+
+    @property
+    def positional_state(self):                               # a detected or shared mask has no per-position state
+        return ("DeclickOperator with a per-clip mask", "mask rows") if self.mask is not None and self.mask.dim() == 2 else None
+
+    def forward(self, data, clicks=None, **kwargs):
+        data = _as_f32_cuda(data)
+        if clicks is not None:
+            data = data + torch.as_tensor(clicks).to(device=data.device, dtype=torch.float32)
+        return self._measure(data)
+
+    def detect(self, measurement):
+        """measurement (B, L) (or (B, 1, L)) on the GPU -> the (B, L) fp32 mask, 0 within `guard` samples of a detected click; sets
+        `last_masked_fraction` (one host read)."""
+        y = _as_f32_cuda(measurement)
+        y = y.reshape(y.shape[0], -1)
+        flags = ops.hip.click_detect(y, y.shape[1], self.threshold, self.sigma_floor)[3]
+        mask, masked = ops.hip.click_mask(flags, self.guard)
+        self.last_masked_fraction = float(masked.sum().item()) / float(mask.numel())
+        return mask
+
+    def _pinned(self, batch, length, device):
+        m = self.mask
+        if m.shape[-1] != length or (m.dim() == 2 and m.shape[0] != batch):
+            raise ValueError(f"DeclickOperator holds a mask of shape {tuple(m.shape)}; {batch} clip(s) of {length} samples need ({length},) "
+                             f"or ({batch}, {length})")
+        if self._mask_dev is None or self._mask_dev.device != device:
+            self._mask_dev = m.to(device)
+        return self._mask_dev
+
+    def mask_of(self, measurement):
+        """The pinned mask on the measurement's device, or a fresh detection (no cache)."""
+        y = measurement.reshape(measurement.shape[0], -1)
+        return self._pinned(y.shape[0], y.shape[1], y.device) if self.mask is not None else self.detect(y)
+
+    def _entry(self, measurement, space, fn):
+        """One cache entry per measurement and space: (mask, fn(mask * measurement))."""
+        def make(y):
+            y = y.reshape(y.shape[0], -1)
+            m = self.mask_of(y)
+            return m, fn(ops.hip.mask_rows(y, m, y.shape[1], y.shape[1]))
+        return BaseOperator._ref(self, measurement, space, make)
+
+    _step_entry = None                                       # (measurement, space, entry) while `guidance` runs: one detection per step
+
+    def _ref(self, measurement, space, fn):
+        held = self._step_entry
+        if held is not None and held[0] is measurement and held[1] == space:
+            return held[2][1]
+        return self._entry(measurement, space, fn)[1]
+
+    def guidance(self, wav, length, measurement, supervised_space, **kw):
+        if supervised_space not in ("wav_form", "mel_spectrogram"):
+            raise ValueError("supervised_space should be either 'wav_form' or 'mel_spectrogram")
+        fn = _flat_rows if supervised_space == "wav_form" else (lambda m: self._mel(m).clone())
+        entry = self._entry(measurement, supervised_space, fn)
+        m = entry[0]
+        if m.shape[-1] != length or (m.dim() == 2 and m.shape[0] != wav.shape[0]):
+            raise ValueError(f"the click mask has shape {tuple(m.shape)}, the batch {wav.shape[0]} clip(s) of {length} samples")
+        self._step_entry = (measurement, supervised_space, entry)      # with cache_reference=False too, the step detects once
+        try:
+            return super().guidance(wav, length, measurement, supervised_space, mask=m, **kw)
+        finally:
+            self._step_entry = None
+
+    def apply(self, x, length, mask=None, **kw):
+        """y = mask * x[:, :length]; `mask` (L,) or (B, L) on x's device -- `guidance` hands over the measurement's."""
+        if mask is None:
+            if self.mask is None:
+                raise ValueError("DeclickOperator.apply: mask= is needed (the detected mask belongs to a measurement; `guidance` passes it)")
+            mask = self._pinned(x.shape[0], int(length), x.device)
+
+        def adjoint(dy, full):                                # a per-sample mask is its own transpose
+            return ops.hip.mask_rows(dy, mask, int(length), int(full))
+        return ops.hip.mask_rows(x, mask, int(length), int(length)), adjoint
+
+    def _noisy_apply(self, wav, length, noise, step, generator, **apply_kw):
+        """The step's noise enters BEFORE the mask: y = mask * (wav[:, :length] + sigma z); the transpose is unchanged."""
+        z, sigma = self._step_noise((wav.shape[0], int(length)), wav.device, noise, step, generator)
+        if z is not None:
+            wav = ops.hip.noise_add(ops.hip.mask_mul(wav, None, int(length), int(length)), z, sigma)
+        return self.apply(wav, length, **apply_kw)
+
+    def project(self, audio, measurement, fade=16):
+        """The optional output stage -> (B, L), L the measurement's length: the measurement's own samples, bit for bit, away from the
+        mask's zeros; the restored `audio` on them; a linear cross-fade over `fade` samples (0 .. 64) on each side.  Meaningful after
+        `wav_form` guidance only: mel guidance does not fix the phase, so a restored stretch need not line up with its surroundings."""
+        fade = dsp.check_declick_fade(fade)
+        y = _as_f32_cuda(measurement)
+        y = y.reshape(y.shape[0], -1)
+        x = _as_f32_cuda(torch.as_tensor(audio).to(y.device))
+        x = x.reshape(x.shape[0], -1)
+        if x.shape[0] != y.shape[0] or x.shape[1] < y.shape[1]:
+            raise ValueError(f"project: restored audio {tuple(x.shape)} does not cover the measurement {tuple(y.shape)}")
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        m = None
+        if self.mask is None and self.cache_reference:        # the mask this trajectory used, when it is still cached
+            for c in self._ref_cache or []:
+                if c[0] is measurement and c[1] == measurement._version:
+                    m = c[3][0]
+                    break
+        if m is None:
+            m = self.mask_of(y)
+        return ops.hip.declick_blend(x, y, m, y.shape[1], fade)
+
+
 class StyleGuidanceOperator(BaseOperator):               # operator.py:253-271 (unrunnable in the reference: run.py:213-214)
     """Style guidance with BUILD-DEFINED semantics (the reference's `clap_model.get_gram_matrix`
     does not exist anywhere): `forward(x) = noiser(x)` (identity, operator.py:270-271) and

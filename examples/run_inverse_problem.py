@@ -16,6 +16,7 @@ embedding file (`--prompt_embeds x.npy`, (B, 512) CLAP text embeddings for Music
     python examples/run_inverse_problem.py -c dps -t music_blind_equalization --eq_lowpass 3000,4      # the EQ curve is fitted, not given
     python examples/run_inverse_problem.py -c dps -t music_decompression --drc_threshold_db -30 --drc_ratio inf      # undo a limiter
     python examples/run_inverse_problem.py -c dps -t music_wow_flutter --wow 0.5,1 --wow 9,0.2 --speed_pct 0.5      # wow, flutter and a drift
+    python examples/run_inverse_problem.py -c dps -t music_declicking --clicks_per_s 20 --supervised_space wav_form --project   # a crackly side
 
 `--track_overlap_s S` restores a recording longer than the model window whole (track mode, inverse_problem/track.py): the first `--wav`
 (or a synthetic 2.5-window signal) becomes overlapping windows under one loss and one stitched file is written.  Without the flag a
@@ -38,6 +39,11 @@ given takes its value from configs/inverse_problem/music_decompression.yaml.
 `--wow RATE_HZ,DEPTH_PCT[,PHASE_DEG]` (repeatable: one speed-modulation component each) and `--speed_pct P` (a constant speed error);
 a flag that is not given takes its value from configs/inverse_problem/music_wow_flutter.yaml.  The curve is built for the clip's length,
 in track mode for the track's.
+
+`-t music_declicking` restores a recording with impulsive noise (DeclickOperator: clicks are detected from the measurement and hidden from
+the loss): `--clicks_per_s R` and `--click_amp LO,HI` shape the synthetic measurement's clicks, `--declick_threshold K` and `--declick_guard G`
+the detector; a flag that is not given takes its value from configs/inverse_problem/music_declicking.yaml.  `--project` keeps the
+measurement's own samples away from the detected clicks (meaningful with `--supervised_space wav_form`); the masked fraction is printed.
 
 `-t music_blind_wow_flutter` measures through the same kind of curve, which the restoration does not know (BlindTimeWarpOperator fits it
 inside the guided loop): `--wow` / `--speed_pct` build the TRUE curve of the synthetic measurement, `--warp_knot_stride S` (fine knots
@@ -73,7 +79,7 @@ from diffmusic_amd.schedulers import get_scheduler                              
 
 TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation", "music_declipping",
          "music_blind_dereverberation", "music_source_separation", "music_spectral_inpainting", "music_blind_equalization", "music_decompression",
-         "music_wow_flutter", "music_blind_wow_flutter", "music_blind_decompression")
+         "music_wow_flutter", "music_blind_wow_flutter", "music_blind_decompression", "music_declicking")
 SEPARATION = "music_source_separation"
 SPECTRAL = "music_spectral_inpainting"
 BLIND_EQ = "music_blind_equalization"
@@ -81,12 +87,13 @@ DECOMPRESSION = "music_decompression"
 WOW_FLUTTER = "music_wow_flutter"
 BLIND_WOW = "music_blind_wow_flutter"
 BLIND_DRC = "music_blind_decompression"
+DECLICK = "music_declicking"
 DRC_INIT_FLAGS = ("threshold_db", "ratio", "attack_ms", "release_ms", "makeup_db")
 DRC_FLAGS = ("threshold_db", "ratio", "knee_db", "attack_ms", "release_ms", "makeup_db")
 
 
 def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None, tf_boxes=None, eq_true=None, drc=None, warp=None,
-                   blind_warp=None, blind_drc=None):
+                   blind_warp=None, blind_drc=None, declick=None):
     """run.py:157-212: one operator per task, constructor arguments from the data / model config.  `audio_length_in_s`: the length the
     operator acts on when it is not the model window (a track).  `clip_threshold`: music_declipping's threshold(s), a float or one value
     per clip (`threshold_for_sdr` of the clean clips).  `tf_boxes`: music_spectral_inpainting's boxes (`spectral_boxes`).  `eq_true`:
@@ -152,9 +159,52 @@ def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=
             raise ValueError("music_blind_decompression needs blind_drc (blind_drc_params(args, cfg))")
         op = P.BlindDynamicRangeOperator(sample_rate=d.sample_rate, noiser=noiser, **blind_drc["operator"])
         op.true_params = dict(blind_drc["true"])
+    elif task == DECLICK:
+        if declick is None:
+            raise ValueError("music_declicking needs declick (declick_params(args, cfg))")
+        op = P.DeclickOperator(sample_rate=d.sample_rate, noiser=noiser, **declick["operator"])
+        op.click_recipe = dict(declick["clicks"])              # the synthetic measurement's clicks (`synthetic_clicks`)
     else:
         raise ValueError(f"Unknown task: {task}")
     return op, scale
+
+
+def declick_params(args, cfg):
+    """The argument rules of -t music_declicking -> {"operator": the DeclickOperator's `threshold`, `sigma_floor` and `guard`, "clicks":
+    the `rate_hz`, `amplitude`, `max_width` and `seed` of `dsp.click_train`}: --declick_threshold, --declick_guard, --clicks_per_s and
+    --click_amp LO,HI, else the task's config.  The operator's own refusals come before any GPU work.  Any other task refuses the flags."""
+    flags = dict(clicks_per_s=args.clicks_per_s, click_amp=args.click_amp, declick_threshold=args.declick_threshold, declick_guard=args.declick_guard)
+    if args.task != DECLICK:
+        for name, v in flags.items():
+            if v is not None:
+                raise SystemExit(f"--{name} belongs to -t {DECLICK}")
+        return None
+    ip = cfg.inverse_problem
+    c = dict(ip.get("clicks") or {})
+    amp = tuple(float(v) for v in (c.get("amplitude") or (0.3, 0.6)))
+    if args.click_amp is not None:
+        try:
+            amp = tuple(float(v) for v in args.click_amp.split(","))
+        except ValueError:
+            amp = ()
+        if len(amp) != 2:
+            raise SystemExit(f"--click_amp {args.click_amp!r}: LO,HI")
+    out = {"operator": dict(threshold=float(args.declick_threshold if args.declick_threshold is not None else ip.get("threshold", 5.0)),
+                            sigma_floor=float(ip.get("sigma_floor", 1e-5)),
+                            guard=int(args.declick_guard if args.declick_guard is not None else ip.get("guard", 3))),
+           "clicks": dict(rate_hz=float(args.clicks_per_s if args.clicks_per_s is not None else c.get("rate_hz", 20.0)), amplitude=amp,
+                          max_width=int(c.get("max_width", 3)), seed=int(c.get("seed", 0)))}
+    try:
+        P.DeclickOperator(**out["operator"])
+        P.click_train(16, cfg.data.sample_rate, **out["clicks"])
+    except ValueError as e:
+        raise SystemExit(f"-t {DECLICK}: {e}")
+    return out
+
+
+def synthetic_clicks(op, gt, sample_rate):
+    """The clicks of a synthetic declicking measurement, shaped like `gt`, from the recipe `build_operator` left on the operator."""
+    return P.click_train(gt.shape[1], sample_rate, batch=gt.shape[0], **op.click_recipe).to(gt.device)
 
 
 # why the measurement of a task cannot seed a warm start (the encoder takes a full-rate waveform of the clip's length)
@@ -241,6 +291,12 @@ def parse_args(argv=None):
     for flag in DRC_INIT_FLAGS:
         ap.add_argument(f"--drc_init_{flag}", type=float, default=None,
                         help=f"music_blind_decompression: where the fit of {flag} starts (default: the task's config)")
+    ap.add_argument("--clicks_per_s", type=float, default=None, help="music_declicking: clicks per second of the synthetic measurement (default: the task's config)")
+    ap.add_argument("--click_amp", default=None, metavar="LO,HI", help="music_declicking: the clicks' amplitude range (default: the task's config)")
+    ap.add_argument("--declick_threshold", type=float, default=None,
+                    help="music_declicking: a residual above this multiple of the frame's robust scale is a click (default: the task's config)")
+    ap.add_argument("--declick_guard", type=int, default=None,
+                    help="music_declicking: samples hidden on each side of a detected one, 0 .. 64 (default: the task's config)")
     ap.add_argument("--wow", action="append", default=None, metavar="RATE_HZ,DEPTH_PCT[,PHASE_DEG]",
                     help="music_wow_flutter: one speed-modulation component (repeatable; default: the task's config)")
     ap.add_argument("--speed_pct", type=float, default=None, help="music_wow_flutter: constant speed error in percent (default: the task's config)")
@@ -555,11 +611,11 @@ def main(argv=None):
     args = parse_args(argv)
     overrides = [f"data={args.data}", f"model={args.model}"]
     if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL, BLIND_EQ, DECOMPRESSION, WOW_FLUTTER, BLIND_WOW,
-                     BLIND_DRC):
+                     BLIND_DRC, DECLICK):
         overrides.append(f"inverse_problem={args.task}")
     stems = separation_stems(args)
-    if args.project and args.task not in ("music_declipping", SEPARATION):
-        raise SystemExit("--project is the output stage of -t music_declipping and -t music_source_separation")
+    if args.project and args.task not in ("music_declipping", SEPARATION, DECLICK):
+        raise SystemExit("--project is the output stage of -t music_declipping, -t music_source_separation and -t music_declicking")
     cfg = compose(args.config_name, overrides=overrides)
     tf_boxes = spectral_boxes(args, cfg)
     eq_true = equalization_curve(args, cfg)
@@ -567,6 +623,7 @@ def main(argv=None):
     warp = warp_params(args, cfg, length=int(cfg.model.pipe.audio_length_in_s * cfg.data.sample_rate), sample_rate=cfg.data.sample_rate)
     blind_warp = blind_warp_params(args, cfg)
     blind_drc = blind_drc_params(args, cfg)
+    declick = declick_params(args, cfg)
     if stems is not None:
         if args.model != "musicldm":
             raise SystemExit("this driver feeds MusicLDM's class-embedding conditioning; AudioLDM2 needs its T5 / GPT-2 states (see bench.py --workload)")
@@ -584,7 +641,7 @@ def main(argv=None):
         gt = load_clips(args.wav, args.batch, sr, length, args.seed).to(device)
         thr = P.threshold_for_sdr(gt, args.clip_sdr_db) if args.task == "music_declipping" else None
         op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr, tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp,
-                                   blind_warp=blind_warp, blind_drc=blind_drc)
+                                   blind_warp=blind_warp, blind_drc=blind_drc, declick=declick)
         B = gt.shape[0]
     else:
         if args.task == "music_generation":
@@ -595,14 +652,17 @@ def main(argv=None):
         thr = float(P.threshold_for_sdr(gt, args.clip_sdr_db)[0]) if args.task == "music_declipping" else None
         inner, scale = build_operator(args.task, cfg, args.mask_type, audio_length_in_s=P.seconds_for_samples(T, sr), clip_threshold=thr,
                                       tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp, blind_warp=blind_warp,
-                                      blind_drc=blind_drc)
+                                      blind_drc=blind_drc, declick=declick)
         op = P.TrackOperator(inner, layout)
         B = layout.num_windows
         sched_kw["per_clip_norm"] = False                                          # one loss, norms over all windows
         print(f"track mode: {T / sr:.2f} s as {B} windows of {length / sr:.2f} s, starts (s) {[round(s / sr, 2) for s in layout.starts]}")
     pipe = get_pipeline(cfg.model.name).from_pretrained(args.weights, seed=args.seed).to(device)
     pipe.scheduler = get_scheduler(cfg.name)(operator=op, **sched_kw)
-    measurement = op.forward(gt)                                                   # run.py:290-300: degrade the ground truth once
+    if args.task == DECLICK:                                                       # clean + clicks (+ noise): the clicks are not part of A
+        measurement = op.forward(gt, clicks=synthetic_clicks(op.inner if layout is not None else op, gt, sr))
+    else:
+        measurement = op.forward(gt)                                               # run.py:290-300: degrade the ground truth once
     if args.prompt_embeds:
         pe = torch.from_numpy(np.load(args.prompt_embeds)).float()
     else:
@@ -633,6 +693,9 @@ def main(argv=None):
         mel = to_mel.transform(torch.from_numpy(audio[i:i + 1]).to(device))[0].T      # (frames, 64)
         pipe.save_mel_spectrogram(mel[: length * 100 // sr], out / "mel_recon" / f"{name}.png")
     blind = op.inner if layout is not None else op
+    if isinstance(blind, P.DeclickOperator) and blind.last_masked_fraction is not None:
+        print(f"click mask: {100.0 * blind.last_masked_fraction:.3f} % of the samples hidden from the loss"
+              + (" (--project: meaningful after --supervised_space wav_form only)" if args.project and args.supervised_space != "wav_form" else ""))
     if isinstance(blind, P.BlindDereverberationOperator) and blind.true_ir is not None and blind.ir_estimate is not None:
         est, true = blind.ir_estimate.cpu(), blind.true_ir                         # the synthetic measurement knows its response
         err = torch.linalg.vector_norm(est - true, dim=1) / torch.linalg.vector_norm(true, dim=1)

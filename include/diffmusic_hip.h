@@ -37,7 +37,8 @@ extern "C" {
  * dmx_audio_tf_wgrad_segments / dmx_audio_eq_update (blind equalisation: a fitted gain curve per clip) and dmx_drc_fwd / dmx_drc_bwd
  * (de-compression: a dynamic-range compressor and the transpose of its Jacobian) and dmx_warp_fwd / dmx_warp_bwd (wow and flutter: a clip
  * read along a delay curve, and the transpose) and dmx_warp_wgrad / dmx_warp_update (blind wow and flutter: the delay curve fitted) and dmx_drc_fwd_p / dmx_drc_bwd_p / dmx_drc_pgrad /
- * dmx_drc_update (blind de-compression: the compressor's parameters per clip on the device, and fitted) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * dmx_drc_update (blind de-compression: the compressor's parameters per clip on the device, and fitted) and dmx_click_detect /
+ * dmx_click_mask / dmx_mask_rows / dmx_declick_blend (declicking: a click detector and per-clip sample masks) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
  * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
@@ -344,6 +345,32 @@ int dmx_warp_wgrad(const float* dy, const float* x, long long x_stride, const fl
                    int L, void* stream);
 int dmx_warp_update(const float* part, float* coarse, float* m, float* v, float* fine, int batch, int L, int knot_stride, int k, double lr,
                     double beta1, double beta2, double eps, double max_delay, int anchor, void* stream);
+/* Declicking (csrc/declick.hip): impulsive noise found by an autoregressive detector and hidden from the loss by a
+ * mask with one row per clip.  Per clip, y zero outside [0, L); frames of N = 1024 samples, F = ceil(L / 1024), model order 16.
+ *   click_detect   per frame j: the autocorrelation r[0 .. 16] of the 2048 samples from j N - 512 under the periodic Hann window; a = 0
+ *                  unless r[0] is a finite positive number, else Levinson-Durbin on (r[0] (1 + 1e-3), r[1], ..); the residual
+ *                  e[n] = y[n] - sum_i a[i] y[n - i] of the frame's live samples; sigma = med / 0.6745f, med the |e| of rank ceil(c / 2) of
+ *                  the c live samples, ordered by the bit pattern; flags[n] = |e[n]| > threshold * (sigma > sigma_floor ? sigma :
+ *                  sigma_floor), strict, a NaN never flagged.  a (batch, F, 16), e (batch, L), sigma (batch, F), flags (batch, L) bytes
+ *                  0 / 1, r null or (batch, F, 17), all contiguous.  One workgroup per (frame, clip), fixed-order reductions, no atomics.
+ *   click_mask     mask[b, n] = 0 where a flagged q has |q - n| <= guard, else 1; masked[b] = the number of zeros.  flags and mask
+ *                  (batch, L) contiguous.
+ *   mask_rows      y[b, n] = x[b, n] * mask[b, n] (one rounded product), n < L, +0 on [L, Ly); y (batch, Ly) contiguous.  mask_stride 0:
+ *                  one (L) mask for every clip; otherwise >= L floats between the clips' rows.  Its own transpose (Ly = full).
+ *   declick_blend  out[b, n] = y where no mask zero lies within `fade` samples of n, x where mask[b, n] = 0, else
+ *                  fl(fl(w y) + fl(fl(1 - w) x)), w = fl(d / (fade + 1)), d the distance to the nearest zero.  out (batch, L) contiguous.
+ * Bit-reproducible and independent of the batch and the batch position; any bits in y are safe (a non-finite sample reaches only the
+ * frames whose window holds it, which get a = 0).  DMX_ERR_SHAPE, with nothing written and the offending argument named, for
+ * threshold <= 0 or not finite, sigma_floor < 0 or not finite, guard or fade outside 0 .. 64; and for a null pointer, batch outside
+ * 1 .. 65535, a length outside 1 .. 2^30, Ly < L, a row stride < L (with batch > 1; one row uses no stride), a mask stride that is neither
+ * 0 nor at least L. */
+int dmx_click_detect(const float* y, long long y_stride, float* a, float* e, float* sigma, unsigned char* flags, float* r, int batch, int L,
+                     float threshold, float sigma_floor, void* stream);
+int dmx_click_mask(const unsigned char* flags, float* mask, int* masked, int batch, int L, int guard, void* stream);
+int dmx_mask_rows(const float* x, long long x_stride, const float* mask, long long mask_stride, float* y, int batch, int L, int Ly,
+                  void* stream);
+int dmx_declick_blend(const float* x, long long x_stride, const float* y, long long y_stride, const float* mask, long long mask_stride,
+                      float* out, int batch, int L, int fade, void* stream);
 /* out[i] = y[i] + scale * z[i], i < n (the noiser on a materialised measurement A(x): super-resolution, dereverberation, wav_form) */
 int dmx_noise_add(const float* y, const float* z, float* out, long long n, float scale, void* stream);
 /* PhaseRetrievalOperator.forward: |torch.stft(wav)| as (B, n_fft/2+1, frames) fp32 */
