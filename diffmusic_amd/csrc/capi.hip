@@ -182,6 +182,12 @@ int dmx_unet_fwd_ctx(dmx_model* m, const float* x, const float* t, const float* 
   return dmx_unet_fwd_impl(m->impl, x, t, class_labels, eps, batch, h, w, ws, ws_bytes, ST(stream), ctx0, n0, ctx1, n1, bias1);
 }
 
+// host arithmetic only: 1 when the tap-stationary tile (tile_cfg 20 ... 22) can take the launch `desc` describes, 0 when not
+int dmx_gemm_slab_eligible(const void* desc, size_t desc_bytes) {
+  if (!desc || desc_bytes != sizeof(GemmDesc)) { dmx_set_error("GemmDesc size mismatch: %zu vs %zu", desc_bytes, sizeof(GemmDesc)); return DMX_ERR_SHAPE; }
+  return dmx_gemm_slab_ok(*reinterpret_cast<const GemmDesc*>(desc)) ? 1 : 0;
+}
+int dmx_gemm_last_cfg_raw(void) { return dmx_gemm_last_cfg(); }
 // test hook pair: dmx_gemm_last_tile_rows_raw() returns the slot rows that this thread's most recent dmx_gemm_raw launch reported
 static thread_local int g_raw_gn_rows = 0;
 int dmx_gemm_raw(const void* desc, size_t desc_bytes, void* stream) {

@@ -173,3 +173,5 @@ int dmx_gemm_launch_ln(int cfg, const GemmDesc& d, hipStream_t stream);
 int dmx_gemm_launch_rowstats(int cfg, const GemmDesc& d, hipStream_t stream);      // EPI_ROWSTATS producers (same file)
 int dmx_gemm_launch_gnstats(int cfg, const GemmDesc& d, hipStream_t stream, int* gn_rows);       // EPI_GNSTATS producers (gemm_gn.hip)
 bool dmx_prof_is_active();
+bool dmx_gemm_slab_ok(const GemmDesc& d);      // the tap-stationary 320 x 256 tile (cfg 20 ... 22) can take this launch (host arithmetic only)
+int dmx_gemm_last_cfg();                       // tile configuration of the most recent dispatch

@@ -24,6 +24,13 @@ int launch_glds(const GemmDesc& d, hipStream_t stream) {
                                                 : launch_glds_t<BM, BN, WM, WN, NSTAGE, 0>(d, stream);
 }
 
+// the tap-stationary 320 x 256 tile (gemm_tile.h, SLAB): S slab pieces per wave and K step
+template <int S>
+int launch_slab(const GemmDesc& d, hipStream_t stream) {
+  return (d.flags & (EPI_MASKBITS | EPI_BITS2)) ? launch_glds_t<320, 256, 2, 4, 2, 1, false, S>(d, stream)
+                                                : launch_glds_t<320, 256, 2, 4, 2, 0, false, S>(d, stream);
+}
+
 template <int BM, int BN, int WM, int WN>
 int launch_cfg(const GemmDesc& d, hipStream_t stream) {
   if (d.flags & EPI_SOFTBWD) return DMX_ERR_SHAPE;
@@ -46,7 +53,8 @@ struct ProfRec { hipEvent_t a, b; double flops, bytes; int M, N, K, Z, taps, fla
 int g_last_cfg = 0;   // tile configuration chosen by the most recent dispatch (profiling only)
 bool g_prof = false;
 std::vector<ProfRec> g_prof_recs;
-// tile configurations: 1 = LDS-DMA 256x256, 2 = LDS-DMA 256x128, 3 = 128x128, 4 = 128x64, 5 = 128x32, 6 = 64x64
+// tile configurations: 1 = LDS-DMA 256x256, 2 = LDS-DMA 256x128, 3 = 128x128, 4 = 128x64, 5 = 128x32, 6 = 64x64, 7 ... 19 below,
+// 20 / 21 / 22 = the 320x256 tile with the tap-stationary slab loop at 2 / 1 / 3 slab pieces per wave and K step
 struct TileEntry { int M, N, K, Z, cfg; };
 static const TileEntry g_tile_table[] = {
 #include "tile_table.inc"
@@ -61,8 +69,47 @@ bool glds_ok(const GemmDesc& d) {
   return in_elems < (1ll << 29) && (long long)d.M * d.lda < (1ll << 29) && ((long long)d.N + 512) * d.ldw < (1ll << 29) &&
          (d.sy == 1 || strided_ok);
 }
+}  // namespace
+
+// Launches the slab loop can take (it is a second K loop of cfg 7, same results bit for bit): 1-D stride-1 convolutions over whole
+// 64-channel groups whose taps span at most SLAB_HALO rows, N in whole 256-column tiles, the 16-bit LDS-staged epilogue, whole images
+// of Wq rows (its M tiles restart at every image), no split-K and none of the epilogues that have instantiations of their own.
+bool dmx_gemm_slab_ok(const GemmDesc& d) {
+  if (d.Hi != 1 || d.Hq != 1 || d.sx != 1 || d.ntaps < 2 || d.ntaps > DMX_MAX_TAPS || (d.Ci & 63) || d.Ci <= 0 || d.N <= 0 || (d.N & 255)) return false;
+  if (d.Wq <= 0 || d.M % d.Wq != 0 || d.ksplit > 1) return false;
+  int lo = 127, hi = -128;
+  for (int t = 0; t < d.ntaps; ++t) {
+    if (d.tdy[t] != 0) return false;
+    lo = d.tdx[t] < lo ? d.tdx[t] : lo;
+    hi = d.tdx[t] > hi ? d.tdx[t] : hi;
+  }
+  if (hi - lo > SLAB_HALO) return false;
+  if (d.flags & (EPI_F32OUT | EPI_SOFTBWD | EPI_GEGLU | EPI_LNFOLD | EPI_ROWSTATS | EPI_GNSTATS | EPI_GNBWD)) return false;
+  if ((d.ldc | d.ldr | d.ldx | d.ldc2) & 7) return false;
+  return glds_ok(d);
+}
+int dmx_gemm_last_cfg() { return g_last_cfg; }
+
+namespace {
+// slab pieces per wave and K step for k taps: a wave's 6 pieces of the next group's slab must fit the k steps of this one
+inline int slab_cfg(int ntaps) { return ntaps >= 6 ? 21 : (ntaps >= 3 ? 20 : 22); }
+// A launch the dispatcher would give to cfg 7 goes to the slab loop for the (N, k) where the isolated launch measured faster (the
+// resblock convolutions of HiFi-GAN's C = 512 and C = 256 stages: 6-9 % at every k, profiles/slab_conv_isolated.txt), as long as
+// tiling M per image costs no extra round of workgroups over the 256 CUs.  DMX_NO_SLAB=1 keeps cfg 7 (same-binary A/B runs).
+int slab_adopt(const GemmDesc& d) {
+  static const bool no_slab = getenv("DMX_NO_SLAB") != nullptr;
+  if (no_slab || !(d.N == 256 || d.N == 512) || !(d.ntaps == 3 || d.ntaps == 7 || d.ntaps == 11) || d.Z != 1 || !dmx_gemm_slab_ok(d)) return 7;
+  const long long flat = (long long)cdiv(d.M, 320) * (d.N / 256), per_image = (long long)(d.M / d.Wq) * cdiv(d.Wq, 320) * (d.N / 256);
+  return (per_image + 255) / 256 <= (flat + 255) / 256 ? slab_cfg(d.ntaps) : 7;
+}
+
 int launch_by_cfg(int cfg, const GemmDesc& d, hipStream_t stream, int* gn_rows = nullptr) {
   g_last_cfg = cfg;
+  if (cfg >= 20 && cfg <= 22) {
+    const int S = cfg == 20 ? 2 : (cfg == 21 ? 1 : 3);
+    if (!dmx_gemm_slab_ok(d) || d.ntaps * S < 6) return DMX_ERR_SHAPE;
+    return S == 2 ? launch_slab<2>(d, stream) : (S == 1 ? launch_slab<1>(d, stream) : launch_slab<3>(d, stream));
+  }
   if (d.flags & EPI_LNFOLD) return dmx_gemm_launch_ln(cfg, d, stream);       // (gemm_ln.hip: the same tiles with the LayerNorm correction ahead of the epilogue)
   if (d.flags & EPI_ROWSTATS) return dmx_gemm_launch_rowstats(cfg, d, stream);   // (... and with the row-statistics epilogue)
   if (d.flags & (EPI_GNSTATS | EPI_GNBWD)) return dmx_gemm_launch_gnstats(cfg, d, stream, gn_rows);     // (gemm_gn.hip: GroupNorm partial sums of the stored tile)
@@ -94,7 +141,7 @@ int launch_by_cfg(int cfg, const GemmDesc& d, hipStream_t stream, int* gn_rows =
 int launch_dispatch(const GemmDesc& d, hipStream_t stream, int* gn_rows) {
   const bool gl = glds_ok(d);
   if (d.flags & EPI_SOFTBWD) return gl ? launch_by_cfg(1, d, stream, gn_rows) : DMX_ERR_SHAPE;   // (its one caller checks the span up front: vae.hip)
-  if (d.tile_cfg >= 1 && d.tile_cfg <= 19 && ((d.tile_cfg > 2 && d.tile_cfg < 7) || gl)) return launch_by_cfg(d.tile_cfg, d, stream, gn_rows);
+  if (d.tile_cfg >= 1 && d.tile_cfg <= 22 && ((d.tile_cfg > 2 && d.tile_cfg < 7) || gl)) return launch_by_cfg(d.tile_cfg, d, stream, gn_rows);
   {  // tuning hook: DMX_CFG_OVERRIDE="N:cfg,N:cfg" forces a tile configuration for large-M launches with that N
     static int ovN[8], ovC[8], nov = -1;
     if (nov < 0) {
@@ -114,7 +161,8 @@ int launch_dispatch(const GemmDesc& d, hipStream_t stream, int* gn_rows) {
   // measured best configuration for the shapes of the shipped benchmark configs (scripts/dev/tune_tiles.py)
   for (const TileEntry* e = g_tile_table; e->cfg; ++e)
     if (e->M == d.M && e->N == d.N && e->K == d.K && e->Z == d.Z) {
-      const int c = e->cfg % 100;                  // (hundreds = a split-K plan, taken by splitk_plan when the launch allows it)
+      int c = e->cfg % 100;                        // (hundreds = a split-K plan, taken by splitk_plan when the launch allows it)
+      if (c == 7) c = slab_adopt(d);
       if ((c > 2 && c < 7) || gl) return launch_by_cfg(c, d, stream, gn_rows);
     }
   if (gl && d.M >= 2048 && d.N % 128 == 0) {
@@ -140,6 +188,7 @@ int launch_dispatch(const GemmDesc& d, hipStream_t stream, int* gn_rows) {
       const double v = cost(c.bm, c.bn, c.slots, c.eff);
       if (v < bc) { bc = v; best = c.cfg; }
     }
+    if (best == 7) best = slab_adopt(d);
     if (best && best != 3) return launch_by_cfg(best, d, stream, gn_rows);
   }
   // small problems: 64x64 tiles so that at least ~1 block per CU exists (U-Net levels with 1k-4k pixels)
@@ -189,7 +238,7 @@ extern "C" int dmx_prof_end(double* total_ms, double* total_flops) {
     float t = 0.f;
     if (hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) ms += t;
     if (csv) fprintf(csv, "%d,%d,%d,%d,%d,%d,%d,%.4f,%.1f\n", r.M, r.N, r.K, r.Z, r.taps, r.flags, r.cfg, t, t > 0 ? r.flops / t / 1e9 : 0.0);
-    const bool dma = r.cfg == 1 || r.cfg == 2 || (r.cfg >= 7 && r.cfg <= 10) || r.cfg == 19;   // gemm_glds_kernel, 8-wave tiles (192 ... 512 rows)
+    const bool dma = r.cfg == 1 || r.cfg == 2 || (r.cfg >= 7 && r.cfg <= 10) || (r.cfg >= 19 && r.cfg <= 22);   // gemm_glds_kernel, 8-wave tiles (192 ... 512 rows)
     if (dma) { g_dma_ms += t; g_dma_fl += r.flops; g_dma_by += r.bytes; ++g_dma_n; }
     fl += r.flops;
     (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b);

@@ -270,18 +270,32 @@ __device__ unsigned long long g_gemm_stamps[8192 * 6];
 #define DMX_GSTAMP(i) do { } while (0)
 #endif
 
-template <int BM, int BN, int WM, int WN, int NSTAGE, int EM, bool LNF = false>
+// ---- tap-stationary ("slab") K loop, SLAB > 0: 1-D stride-1 convolutions whose taps span at most SLAB_HALO rows (dmx_gemm_slab_ok).
+// The taps of such a convolution are the same input rows shifted by tdx, yet the stock loop pulls the BM x 64-channel panel from L2
+// once per tap.  Here LDS holds, per 64-channel group, ONE slab of BM + SLAB_HALO input rows (row s = input column q0 + min tdx + s of the
+// tile's clip, same 1-KiB pieces and source-chunk swizzle as an A stage, so s & 7 is still the fetching lane's row) and every tap reads
+// its fragments from the slab at a row shift: the swizzle key becomes the low three bits of the SHIFTED row, the 2048-B fragment offsets
+// stay immediates.  Two slabs (group g is consumed while g + 1 arrives, SLAB pieces per wave and K step over the group's taps; a wave owns
+// SLAB_ISS = 6 of a slab's 48 pieces, so SLAB x ntaps >= 6) and two weight stages fill the 160 KiB.  The K order (groups outermost, taps
+// innermost) and every MFMA are those of the stock loop's tap-inner walk: results are bit-identical.  A slab holds rows of one clip, so
+// these instantiations tile M per image; a slab row outside [0, Wi) is fetched out of range (zeros) -- decided per slab row, not per tap.
+constexpr int SLAB_HALO = 64;
+
+template <int BM, int BN, int WM, int WN, int NSTAGE, int EM, bool LNF = false, int SLAB = 0>
 __device__ __forceinline__ void glds_tile(const GemmDesc& p, char* smem, const int m0, const int tn, const int mlim) {
   // mlim: first GEMM row this tile does NOT own (p.M, or the end of the tile's image under the image-aligned tiling of the
-  // GroupNorm-statistics instantiations): rows from there on are neither fetched nor stored
+  // GroupNorm-statistics and slab instantiations): rows from there on are neither fetched nor stored
   constexpr int NW = WM * WN;
   constexpr int TM = BM / WM, TN = BN / WN;
   constexpr int FM = TM / 16, FN = TN / 16;
   constexpr int A_ISS = BM / 8 / NW, B_ISS = BN / 8 / NW;
   constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;
   static_assert(A_ISS >= 1 && B_ISS >= 1, "tile too small");
+  constexpr int SLAB_BYTES = (BM + SLAB_HALO) * 128, SLAB_ISS = (BM + SLAB_HALO) / 8 / NW;     // one slab; its 1-KiB pieces per wave
+  constexpr int W_OFF = SLAB > 0 ? 2 * SLAB_BYTES : A_BYTES, W_STAGE = SLAB > 0 ? B_BYTES : STAGE;   // weight stage s: smem + W_OFF + s * W_STAGE
+  static_assert(SLAB == 0 || (NSTAGE == 2 && !LNF && (BM + SLAB_HALO) % (8 * NW) == 0 && TM % 8 == 0), "slab loop: two stages, whole pieces per wave");
 
-  constexpr int PER = A_ISS + B_ISS;              // LDS-DMA instructions per thread per stage
+  constexpr int PER = SLAB > 0 ? B_ISS + SLAB : A_ISS + B_ISS;     // LDS-DMA instructions per thread per K step
   constexpr int KEEP = (NSTAGE - 2) * PER;        // loads allowed in flight when the next tile must have landed
 
   const int tid = threadIdx.x;
@@ -316,7 +330,21 @@ __device__ __forceinline__ void glds_tile(const GemmDesc& p, char* smem, const i
   // input for this row (conv zero padding, rows past M: mask 0) -- two masks per register.  The K loop then needs one bit test
   // per row and step instead of two coordinate adds and two range compares, and 3 instead of 10 registers for A_ISS = 5.
   unsigned a_lin[A_ISS], a_mask2[(A_ISS + 1) / 2];
-  {
+  // slab loop instead: input column of this lane's row of slab piece 0 (the wave's piece j lies j * NW * 8 rows further), that row's
+  // byte offset, and the smallest tap shift
+  int s_ix0 = 0, s_lo = 0;
+  unsigned s_lin0 = 0u;
+  if constexpr (SLAB > 0) {
+    s_lo = 127;
+    for (int t = 0; t < p.ntaps; ++t) {
+      const int dx = (int)(signed char)((__builtin_amdgcn_readlane(tapreg, t) >> 8) & 0xff);
+      s_lo = dx < s_lo ? dx : s_lo;
+    }
+    const int b = m0 / HqWq;
+    s_ix0 = m0 - b * HqWq + s_lo + wave * 8 + lrow;
+    // (mod 2^32: exact wherever the column is inside the image, and only those are fetched)
+    s_lin0 = ((unsigned)b * (unsigned)p.Wi + (unsigned)s_ix0) * lda2 + ((unsigned)cc << 4);
+  } else {
     int r_iy[A_ISS], r_ix[A_ISS];            // prologue only: the K loop keeps a_lin and the masks
     unsigned r_mask[A_ISS];
 #pragma unroll
@@ -372,7 +400,31 @@ __device__ __forceinline__ void glds_tile(const GemmDesc& p, char* smem, const i
   int q_tp = 0;                 // tap of this lane's chunk (wave-uniform on the tap-inner walk)
   unsigned q_adel = 0, q_wdel = 0;   // byte deltas added to the per-row A offsets / weight-row offsets
   char* q_base = nullptr;
+  // slab loop: (tap, channel group) of the step being CONSUMED; during it the wave sends pieces c_tp * SLAB ... of group c_cg + 1's slab
+  int c_tp = 0, c_cg = 0;
+  int q_pi0 = 0;
+  bool q_sval = false;
+  unsigned q_sdel = 0;
+  char* q_sbase = nullptr;
+  auto slab_piece = [&](int pi, char* base, unsigned del) {     // piece pi (wave-uniform) of this wave: slab rows (pi * NW + wave) * 8 ...
+    const int ix = s_ix0 + pi * (NW * 8);
+    const unsigned voff = (unsigned)ix < (unsigned)p.Wi ? s_lin0 + (unsigned)(pi * (NW * 8)) * lda2 + del : OOB;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)(base + (pi * NW + wave) * 1024), 16, voff, 0, 0, 0);
+  };
   auto issue_begin = [&](int ksl, int stage) {
+    if constexpr (SLAB > 0) {
+      const int tp = __builtin_amdgcn_readfirstlane(i_tp), cgi = __builtin_amdgcn_readfirstlane(i_cg);
+      q_base = smem + W_OFF + stage * W_STAGE;
+      q_kval = cgi < cgroups;
+      q_wdel = (unsigned)(tp * cpt + cgi * 8 + cc) << 4;
+      if (++i_tp == p.ntaps) { i_tp = 0; ++i_cg; }
+      const int ctp = __builtin_amdgcn_readfirstlane(c_tp), ccg = __builtin_amdgcn_readfirstlane(c_cg);
+      q_pi0 = ctp * SLAB;
+      q_sval = ccg + 1 < cgroups;
+      q_sdel = (unsigned)(ccg + 1) << 7;
+      q_sbase = smem + ((ccg + 1) & 1) * SLAB_BYTES;
+      return;
+    }
     q_base = smem + stage * STAGE;
     if (tap_inner) {
       // everything that depends on the K step is wave-uniform here: one readlane for the tap, one scalar byte delta for all rows
@@ -398,7 +450,13 @@ __device__ __forceinline__ void glds_tile(const GemmDesc& p, char* smem, const i
   };
   auto issue_one = [&](auto I) {
     constexpr int i = decltype(I)::value;
-    if constexpr (i < A_ISS) {
+    if constexpr (SLAB > 0 && i >= B_ISS) {          // slab loop: the weight pieces go first, then SLAB slots of the next group's slab
+      const int pi = q_pi0 + (i - B_ISS);
+      if (pi < SLAB_ISS && q_sval) slab_piece(pi, q_sbase, q_sdel);     // (wave-uniform: slots past the slab's end issue nothing)
+    } else if constexpr (SLAB > 0) {
+      const unsigned voff = q_kval ? w_row + (unsigned)i * w_step + q_wdel : OOB;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)(q_base + (i * NW + wave) * 1024), 16, voff, 0, 0, 0);
+    } else if constexpr (i < A_ISS) {
       const bool ok = q_kval && ((a_mask2[i >> 1] >> ((i & 1) * 16 + q_tp)) & 1u);
       const unsigned voff = ok ? a_lin[i] + q_adel : OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)(q_base + (i * NW + wave) * 1024), 16, voff, 0, 0, 0);
@@ -439,8 +497,14 @@ __device__ __forceinline__ void glds_tile(const GemmDesc& p, char* smem, const i
   // exactly one stage (past the end the offsets are out of range -> zero fill, no memory traffic), so the vmcnt
   // counts are compile-time constants; the raw s_barrier keeps the younger loads in flight across it.
   const int nk = ks1 > ks0 ? ks1 - ks0 : 0;
+  if constexpr (SLAB > 0) {          // group 0's whole slab and the first step's weights
+    static_for<0, SLAB_ISS>([&](auto PI) { slab_piece(decltype(PI)::value, smem, 0u); });
+    issue_begin(0, 0);
+    static_for<0, B_ISS>(issue_one);
+  } else {
 #pragma unroll
-  for (int s = 0; s < NSTAGE - 1; ++s) issue(s, s);
+    for (int s = 0; s < NSTAGE - 1; ++s) issue(s, s);
+  }
   float2* s_ln = reinterpret_cast<float2*>(smem + NSTAGE * STAGE);                   // LNF: behind the ring (launch_glds_t sizes it)
   float* s_cs = reinterpret_cast<float*>(smem + NSTAGE * STAGE + BM * 8);
   if constexpr (LNF) ln_prologue<BM, BN, NW * 64>(p, m0, tn * BN, s_ln, s_cs);       // (under the latency of the ring's first tiles)
@@ -471,6 +535,7 @@ __device__ __forceinline__ void glds_tile(const GemmDesc& p, char* smem, const i
   constexpr int DEF = ROOMY ? FM : (DMX_DEF_BIG > 0 ? (DMX_DEF_BIG < FM ? DMX_DEF_BIG : FM) : 1);
   constexpr int LOWN = NS - DEF;                               // steps of the current K step the lagging half runs before the barrier
   static_assert(DEF <= FM && DEF >= 1, "carried steps must all be kk = 1 steps");
+  static_assert(SLAB == 0 || !STAGGER, "the slab loop exists for the unstaggered 320-row tile");
   frag8_t wf0[FN], wf1[FN], af[NS];
 #define DMX_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
   auto kloop = [&](auto LAGT) {
@@ -484,12 +549,26 @@ __device__ __forceinline__ void glds_tile(const GemmDesc& p, char* smem, const i
       __builtin_amdgcn_sched_barrier(0);
     };
     for (int ks = 0; ks < nk; ++ks) {
-      const char* sa = smem + cur * STAGE + (wm * TM + lr) * 128;
-      const char* sb = smem + cur * STAGE + A_BYTES + (wn * TN + lr) * 128;
-      const unsigned a0 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)(sa);
-      const unsigned b0 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)(sb);
-      const unsigned sw0 = ((0 * 4 + lq) ^ (lr & 7)) << 4, sw1 = ((1 * 4 + lq) ^ (lr & 7)) << 4;
-      const unsigned aA0 = a0 + sw0, aA1 = a0 + sw1, aB0 = b0 + sw0, aB1 = b0 + sw1;
+      unsigned aA0, aA1, aB0, aB1;           // LDS byte addresses of the lane's first A / W fragment, kk = 0 and 1
+      if constexpr (SLAB > 0) {
+        // this tap's view of the group's slab: the lane's rows shifted by tdx - min tdx, swizzle key from the shifted row
+        const int tp = __builtin_amdgcn_readfirstlane(c_tp), cg = __builtin_amdgcn_readfirstlane(c_cg);
+        const int dx = (int)(signed char)((__builtin_amdgcn_readlane(tapreg, tp) >> 8) & 0xff);
+        const int row = wm * TM + lr + (dx - s_lo);
+        const char* sa = smem + (cg & 1) * SLAB_BYTES + row * 128;
+        const char* sb = smem + W_OFF + cur * W_STAGE + (wn * TN + lr) * 128;
+        const unsigned a0 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)(sa);
+        const unsigned b0 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)(sb);
+        aA0 = a0 + (((0 * 4 + lq) ^ (row & 7)) << 4); aA1 = a0 + (((1 * 4 + lq) ^ (row & 7)) << 4);
+        aB0 = b0 + (((0 * 4 + lq) ^ (lr & 7)) << 4); aB1 = b0 + (((1 * 4 + lq) ^ (lr & 7)) << 4);
+      } else {
+        const char* sa = smem + cur * STAGE + (wm * TM + lr) * 128;
+        const char* sb = smem + cur * STAGE + A_BYTES + (wn * TN + lr) * 128;
+        const unsigned a0 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)(sa);
+        const unsigned b0 = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)(sb);
+        const unsigned sw0 = ((0 * 4 + lq) ^ (lr & 7)) << 4, sw1 = ((1 * 4 + lq) ^ (lr & 7)) << 4;
+        aA0 = a0 + sw0; aA1 = a0 + sw1; aB0 = b0 + sw0; aB1 = b0 + sw1;
+      }
       __builtin_amdgcn_sched_barrier(0);
       // (register-bound tiles: the lagging half reads its first fragments only AFTER the carried MFMAs, whose operands then die first)
       constexpr bool P0_LATE = LAG && DEF < FM;
@@ -570,6 +649,7 @@ __device__ __forceinline__ void glds_tile(const GemmDesc& p, char* smem, const i
       __builtin_amdgcn_s_barrier();
       cur = cur + 1 == NSTAGE ? 0 : cur + 1;
       nxt = nxt + 1 == NSTAGE ? 0 : nxt + 1;
+      if constexpr (SLAB > 0) { if (++c_tp == p.ntaps) { c_tp = 0; ++c_cg; } }
     }
     if constexpr (LAG) {
       __builtin_amdgcn_sched_barrier(0);
@@ -619,7 +699,7 @@ __device__ __forceinline__ int xcd_remap(int bid) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
 }
 
-template <int BM, int BN, int WM, int WN, int NSTAGE, int EM, bool LNF = false>
+template <int BM, int BN, int WM, int WN, int NSTAGE, int EM, bool LNF = false, int SLAB = 0>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const GemmDesc p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tiles_n = (p.N + BN - 1) / BN;
@@ -636,17 +716,23 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_glds_kernel(const GemmDesc p
       mlim = (b + 1) * P;
     }
   }
-  glds_tile<BM, BN, WM, WN, NSTAGE, EM, LNF>(p, smem, m0, bid % tiles_n, mlim);
+  if constexpr (SLAB > 0) {        // a slab holds input rows of one clip: the M tiles restart at every image (Hq == 1: P = Wq rows each)
+    const int P = p.Wq, tpi = (P + BM - 1) / BM, tm = bid / tiles_n, b = tm / tpi;
+    m0 = b * P + (tm - b * tpi) * BM;
+    mlim = (b + 1) * P;
+  }
+  glds_tile<BM, BN, WM, WN, NSTAGE, EM, LNF, SLAB>(p, smem, m0, bid % tiles_n, mlim);
 }
 
-template <int BM, int BN, int WM, int WN, int NSTAGE, int EM, bool LNF = false>
+template <int BM, int BN, int WM, int WN, int NSTAGE, int EM, bool LNF = false, int SLAB = 0>
 int launch_glds_t(const GemmDesc& d, hipStream_t stream) {
   constexpr int NT = WM * WN * 64;
-  constexpr int SMEM = NSTAGE * (BM + BN) * 128 + (LNF ? BM * 8 + BN * 8 : 0);       // (the tap table of this kernel lives in a register, not in LDS)
+  // (the tap table of this kernel lives in a register, not in LDS; slab loop: two slabs of BM + SLAB_HALO rows and two weight stages)
+  constexpr int SMEM = SLAB > 0 ? 2 * (BM + SLAB_HALO + BN) * 128 : NSTAGE * (BM + BN) * 128 + (LNF ? BM * 8 + BN * 8 : 0);
   static_assert(SMEM <= 160 * 1024, "tile ring exceeds the 160 KiB of LDS");
   static bool attr_set = false;
   if (!attr_set) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<BM, BN, WM, WN, NSTAGE, EM, LNF>),
+    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<BM, BN, WM, WN, NSTAGE, EM, LNF, SLAB>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     attr_set = true;
   }
@@ -655,16 +741,17 @@ int launch_glds_t(const GemmDesc& d, hipStream_t stream) {
     const int P = d.Hq * d.Wq;
     if (P % (BM / WM) != 0) tiles = (long long)(d.M / P) * cdiv(P, BM) * cdiv(d.N, BN);
   }
+  if constexpr (SLAB > 0) tiles = (long long)(d.M / d.Wq) * cdiv(d.Wq, BM) * cdiv(d.N, BN);
   dim3 grid((unsigned)tiles, (unsigned)d.Z, (unsigned)(d.ksplit > 1 ? d.ksplit : 1));
   static const bool bias_init = getenv("DMX_NO_BIAS_INIT") == nullptr;
   if (bias_init && (d.flags & EPI_BIAS) && d.bias && !(d.flags & (EPI_MASK | EPI_MASKBITS | EPI_SOFTBWD | EPI_LNFOLD))) {
     // nothing precedes the bias in the epilogue's order (mask -> bias -> residual -> alpha ...): start the accumulators at it instead
     GemmDesc q = d;
     q.flags = (q.flags & ~EPI_BIAS) | EPI_BIASINIT;
-    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NSTAGE, EM, LNF>), grid, dim3(NT), SMEM, stream, q);
+    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NSTAGE, EM, LNF, SLAB>), grid, dim3(NT), SMEM, stream, q);
     return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NSTAGE, EM, LNF>), grid, dim3(NT), SMEM, stream, d);
+  hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NSTAGE, EM, LNF, SLAB>), grid, dim3(NT), SMEM, stream, d);
   return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
 }
 template <int BM, int BN, int WM, int WN, int EM, bool LNF = false>

@@ -524,6 +524,10 @@ int dmx_prof_dominant(double* ms, double* flops, double* bytes);
 
 /* ---- low-level test hook: one implicit-GEMM launch described by the internal descriptor --------*/
 int dmx_gemm_raw(const void* desc, size_t desc_bytes, void* stream);
+/* Host arithmetic (no GPU): 1 when the tap-stationary 320 x 256 tile (tile_cfg 20 / 21 / 22) can take the launch the descriptor
+ * describes, 0 when not.  dmx_gemm_last_cfg_raw(): the tile configuration the most recent dmx_gemm_raw launch was dispatched to. */
+int dmx_gemm_slab_eligible(const void* desc, size_t desc_bytes);
+int dmx_gemm_last_cfg_raw(void);
 /* test hook for the fused forward attention of the U-Net (diffusers Attention inside UNet2DConditionModel,
  * pipeline_musicldm.py:696-703): q (B,Nq,C), k (B,Nk,C), v (B,Nk,ldv) fp16 channels-last (ldv = 0: C), o (B,Nq,C); colbias optional
  * (B,Nk) fp32 additive key bias. */
