@@ -155,13 +155,66 @@ size_t dmx_htsat_tape_raw(dmx_model* m, int stage, int block, int which, void* d
   if (n && dst && dst_elems >= n) (void)hipMemcpyAsync(dst, p, n * sizeof(act_t), hipMemcpyDeviceToDevice, ST(stream));
   return n;
 }
+// test hooks of the tower's own kernels (htsat.hip): each runs the launcher the tower calls, with that launcher's parameters
+int dmx_htsat_ln_rows_fwd_raw(const void* x, void* y, const float* gamma, const float* beta, long long rows, int C, int merge, int H, int W,
+                              float eps, int out_fp32, void* stream) {
+  const int rc = dmx_htsat_ln_fwd_impl((const act_t*)x, y, gamma, beta, rows, C, merge, H, W, eps, out_fp32, ST(stream));
+  if (rc == DMX_ERR_SHAPE)
+    dmx_set_error("htsat layernorm rows: rows %lld (>= 1), C %d (a multiple of 8), row width %d (<= 1536) or merge grid %d x %d (even) unsupported",
+                  rows, C, merge ? 4 * C : C, H, W);
+  return rc;
+}
+int dmx_htsat_ln_rows_bwd_raw(const void* x, const void* dy, const void* add, void* dx, const float* gamma, long long rows, int C, int merge,
+                              int H, int W, float eps, int dy_fp32, void* stream) {
+  const int rc = dmx_htsat_ln_bwd_impl((const act_t*)x, dy, (const act_t*)add, (act_t*)dx, gamma, rows, C, merge, H, W, eps, dy_fp32, ST(stream));
+  if (rc == DMX_ERR_SHAPE)
+    dmx_set_error("htsat layernorm rows backward: rows %lld (>= 1), C %d (a multiple of 8), row width %d (<= 1536), merge grid %d x %d (even) "
+                  "or merge with add unsupported", rows, C, merge ? 4 * C : C, H, W);
+  return rc;
+}
+int dmx_htsat_gelu_fwd_raw(const void* u, void* y, long long n8, void* stream) {
+  const int rc = dmx_htsat_gelu_fwd_impl((const act_t*)u, (act_t*)y, n8, ST(stream));
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("htsat gelu: n8 %lld must be at least 1", n8);
+  return rc;
+}
+int dmx_htsat_gelu_bwd_raw(const void* u, const void* dy, void* du, long long n8, void* stream) {
+  const int rc = dmx_htsat_gelu_bwd_impl((const act_t*)u, (const act_t*)dy, (act_t*)du, n8, ST(stream));
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("htsat gelu: n8 %lld must be at least 1", n8);
+  return rc;
+}
+int dmx_htsat_win_attn_fwd_raw(const void* qkv, void* out, const float* bias_table, int B, int H, int W, int C, int heads, int shift, void* stream) {
+  const int rc = dmx_htsat_win_attn_fwd_impl((const act_t*)qkv, (act_t*)out, bias_table, B, H, W, C, heads, shift, ST(stream));
+  if (rc == DMX_ERR_SHAPE)
+    dmx_set_error("htsat window attention: grid %d x %d (multiples of 8), C %d (= heads %d x 24), shift %d (0 .. 7) or batch %d unsupported", H, W, C, heads, shift, B);
+  return rc;
+}
+int dmx_htsat_win_attn_bwd_raw(const void* qkv, const void* dout, void* dqkv, const float* bias_table, int B, int H, int W, int C, int heads,
+                               int shift, void* stream) {
+  const int rc = dmx_htsat_win_attn_bwd_impl((const act_t*)qkv, (const act_t*)dout, (act_t*)dqkv, bias_table, B, H, W, C, heads, shift, ST(stream));
+  if (rc == DMX_ERR_SHAPE)
+    dmx_set_error("htsat window attention: grid %d x %d (multiples of 8), C %d (= heads %d x 24), shift %d (0 .. 7) or batch %d unsupported", H, W, C, heads, shift, B);
+  return rc;
+}
+int dmx_htsat_embed_fwd_raw(dmx_model* m, const float* mel, int batch, int frames, void* tokens, void* stream) {
+  int rc = check(m, DMX_MODEL_HTSAT);
+  if (rc) return rc;
+  return dmx_htsat_embed_fwd_impl(m->impl, mel, batch, frames, (act_t*)tokens, ST(stream));
+}
+int dmx_htsat_embed_bwd_raw(dmx_model* m, const float* mel, int batch, int frames, const void* dtok, const float* scale, float* dimg, float* dmel,
+                            void* stream) {
+  int rc = check(m, DMX_MODEL_HTSAT);
+  if (rc) return rc;
+  return dmx_htsat_embed_bwd_impl(m->impl, mel, batch, frames, (const act_t*)dtok, scale, dimg, dmel, ST(stream));
+}
 int dmx_gram_fwd(const float* F, float* G, int batch, int tokens, int channels, void* stream) {
   const int rc = dmx_gram_fwd_impl(F, G, batch, tokens, channels, ST(stream));
   if (rc == DMX_ERR_SHAPE) dmx_set_error("gram: 1 <= tokens <= 96");
   return rc;
 }
 int dmx_gram_bwd(const float* F, const float* dG, float* dF, int batch, int tokens, int channels, void* stream) {
-  return dmx_gram_bwd_impl(F, dG, dF, batch, tokens, channels, ST(stream));
+  const int rc = dmx_gram_bwd_impl(F, dG, dF, batch, tokens, channels, ST(stream));
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("gram backward: batch, tokens and channels must be at least 1");
+  return rc;
 }
 
 size_t dmx_unet_workspace_bytes(dmx_model* m, int batch, int h, int w) { return dmx_unet_ws_impl(m->impl, batch, h, w, 0, 0); }

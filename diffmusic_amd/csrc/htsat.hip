@@ -166,10 +166,14 @@ int ln_tpr(int Cw) {
   while (tpr < nch && tpr < 64) tpr <<= 1;
   return tpr;
 }
+// rows of whole 8-channel chunks; a patch merging gathers 2 x 2 tokens of an even grid
+bool ln_rows_ok(const RowSrc& s, long long rows) {
+  return rows >= 1 && rows <= 0x7fffffffLL && s.C >= 8 && !(s.C & 7) && (!s.merge || (s.H >= 2 && s.W >= 2 && !((s.H | s.W) & 1)));
+}
 template <typename OutT>
 int ln_rows_fwd(const RowSrc& s, const float* gamma, const float* beta, OutT* y, long long rows, float eps, hipStream_t st) {
   const int Cw = s.merge ? 4 * s.C : s.C;
-  if ((s.C & 7) || Cw > 64 * LN_MAXCH * 8) return DMX_ERR_SHAPE;
+  if (!ln_rows_ok(s, rows) || Cw > 64 * LN_MAXCH * 8) return DMX_ERR_SHAPE;
   const int tpr = ln_tpr(Cw), rpb = 256 / tpr;
   hipLaunchKernelGGL(ln_rows_fwd_kernel<OutT>, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, st, s, gamma, beta, y, rows, Cw, tpr, eps);
   return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
@@ -177,7 +181,7 @@ int ln_rows_fwd(const RowSrc& s, const float* gamma, const float* beta, OutT* y,
 template <typename DyT>
 int ln_rows_bwd(const RowSrc& s, const float* gamma, const DyT* dy, const act_t* add, act_t* dx, long long rows, float eps, hipStream_t st) {
   const int Cw = s.merge ? 4 * s.C : s.C;
-  if ((s.C & 7) || Cw > 64 * LN_MAXCH * 8 || (s.merge && add)) return DMX_ERR_SHAPE;
+  if (!ln_rows_ok(s, rows) || Cw > 64 * LN_MAXCH * 8 || (s.merge && add)) return DMX_ERR_SHAPE;
   const int tpr = ln_tpr(Cw), rpb = 256 / tpr;
   hipLaunchKernelGGL(ln_rows_bwd_kernel<DyT>, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, st, s, gamma, dy, add, dx, rows, Cw, tpr, eps);
   return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
@@ -206,6 +210,17 @@ __global__ void gelu_bwd_kernel(const act_t* __restrict__ u, const act_t* __rest
 #pragma unroll
   for (int e = 0; e < 8; ++e) d[e] *= gelu_df(f[e]);
   reinterpret_cast<uint4*>(du)[i] = pack8(d);
+}
+// n8 groups of 8 values; du may be dy (the tower's backward runs in place)
+int gelu_fwd(const act_t* u, act_t* y, long long n8, hipStream_t st) {
+  if (n8 < 1) return DMX_ERR_SHAPE;
+  hipLaunchKernelGGL(gelu_fwd_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, u, y, n8);
+  return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
+}
+int gelu_bwd(const act_t* u, const act_t* dy, act_t* du, long long n8, hipStream_t st) {
+  if (n8 < 1) return DMX_ERR_SHAPE;
+  hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, u, dy, du, n8);
+  return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
 }
 
 // ------------------------------------------------------------------------------------------------ window attention
@@ -383,6 +398,20 @@ __global__ __launch_bounds__(64) void win_attn_bwd_kernel(const act_t* __restric
   store_head(drow + g.C, dk);
   store_head(drow + 2 * g.C, dv);
 }
+// what the two kernels can take: a grid of whole windows, heads of HD channels, a shift inside the window
+bool win_geom_ok(const WinGeom& g) {
+  return g.B >= 1 && g.H >= WS && g.W >= WS && g.H % WS == 0 && g.W % WS == 0 && g.heads >= 1 && g.C == g.heads * HD && g.shift >= 0 && g.shift < WS;
+}
+int win_attn_fwd(const act_t* qkv, act_t* out, const float* bias_table, const WinGeom& g, hipStream_t st) {
+  if (!win_geom_ok(g)) return DMX_ERR_SHAPE;
+  hipLaunchKernelGGL(win_attn_fwd_kernel, dim3((unsigned)(g.B * (g.H / WS) * (g.W / WS)), (unsigned)g.heads), dim3(64), 0, st, qkv, out, bias_table, g);
+  return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
+}
+int win_attn_bwd(const act_t* qkv, const act_t* dout, act_t* dqkv, const float* bias_table, const WinGeom& g, hipStream_t st) {
+  if (!win_geom_ok(g)) return DMX_ERR_SHAPE;
+  hipLaunchKernelGGL(win_attn_bwd_kernel, dim3((unsigned)(g.B * (g.H / WS) * (g.W / WS)), (unsigned)g.heads), dim3(64), 0, st, qkv, dout, dqkv, bias_table, g);
+  return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
+}
 
 // ------------------------------------------------------------------------------------------------ input stage
 // mel (B, frames, 64) fp32 log-mel -> BatchNorm2d over the mel bins (eval) -> bicubic stretch of the time axis to 1024 frames
@@ -502,11 +531,12 @@ __global__ __launch_bounds__(128) void embed_bwd_kernel(const EmbedParams p, con
   const int cpb = p.bins / 4;
   const int c = ty / cpb, f0 = (ty - c * cpb) * 4;
   const int T = p.grid * 4;
+  const int Tout = (T / p.bins) * T;                        // stretched frames per clip: spec_size / bins time chunks of spec_size columns
   const float4 ba = *reinterpret_cast<const float4*>(p.bn_a + f0);
 #pragma unroll
   for (int dx = 0; dx < 4; ++dx) {
     const int tt = c * T + tx * 4 + dx;
-    float* dst = dimg + ((long long)b * (4 * T) + tt) * p.bins + f0;
+    float* dst = dimg + ((long long)b * Tout + tt) * p.bins + f0;
     *reinterpret_cast<float4*>(dst) = make_float4(ba.x * dp[0 * 4 + dx], ba.y * dp[1 * 4 + dx], ba.z * dp[2 * 4 + dx], ba.w * dp[3 * 4 + dx]);
   }
 }
@@ -747,12 +777,47 @@ struct Htsat : Model {
     return DMX_OK;
   }
 
-  EmbedParams embed_params(const float* mel, const InterpTables& T) const {
+  EmbedParams embed_params(const float* mel, const InterpTables& T, int B_, int frames_) const {
     EmbedParams p;
     p.mel = mel; p.tidx = T.tidx; p.tw = T.tw; p.bn_a = bn_a; p.bn_b = bn_c;
     p.Wp = ps.dev(pe_w); p.bp = ps.dev(pe_b); p.ln_g = ps.dev(pe_g); p.ln_b = ps.dev(pe_bb);
-    p.B = B; p.frames = frames; p.E = cfg.embed_dim; p.bins = cfg.num_mel_bins; p.grid = grid0; p.eps = cfg.ln_eps;
+    p.B = B_; p.frames = frames_; p.E = cfg.embed_dim; p.bins = cfg.num_mel_bins; p.grid = grid0; p.eps = cfg.ln_eps;
     return p;
+  }
+  // the input stage and its transpose (the tower's first and last launches; also the test hooks dmx_htsat_embed_*_raw)
+  void embed_fwd(const float* mel, const InterpTables& T, int B_, int frames_, act_t* tokens, hipStream_t st) const {
+    const EmbedParams p = embed_params(mel, T, B_, frames_);
+    const unsigned nb = (unsigned)(((long long)B_ * grid0 * grid0 + 127) / 128);
+    hipLaunchKernelGGL(embed_fwd_kernel, dim3(nb), dim3(128), 0, st, p, tokens);
+  }
+  // dtok (B, grid0^2, E) -> dimg (B, Tout, bins) fp32 scratch -> dmel (B, frames, bins) (times scale[b] when given)
+  void embed_bwd(const float* mel, const InterpTables& T, int B_, int frames_, const act_t* dtok, const float* scale, float* dimg, float* dmel,
+                 hipStream_t st) const {
+    const int Tout = cfg.spec_size * (cfg.spec_size / cfg.num_mel_bins);
+    const EmbedParams p = embed_params(mel, T, B_, frames_);
+    const long long ntok = (long long)B_ * grid0 * grid0;
+    const unsigned nb = (unsigned)((ntok + 127) / 128);
+    hipLaunchKernelGGL(embed_bwd_kernel, dim3(nb), dim3(128), 0, st, p, dtok, dimg);
+    const long long n = (long long)B_ * frames_ * cfg.num_mel_bins;
+    hipLaunchKernelGGL(interp_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dimg, T.kstart, T.kt, T.kw, scale, dmel, B_, frames_,
+                       cfg.num_mel_bins, Tout);
+  }
+  // test hooks: the two launchers alone, on the handle's parameters and tables; the tape of a kept forward is left as it is
+  int embed_fwd_raw(const float* mel, int B_, int frames_, act_t* tokens, hipStream_t st) {
+    CTRY(check_shape(B_, frames_));
+    if (!bn_a) { dmx_set_error("htsat: parameters are not loaded"); return DMX_ERR_STATE; }
+    InterpTables* T = nullptr;
+    CTRY(get_tables(frames_, &T));
+    embed_fwd(mel, *T, B_, frames_, tokens, st);
+    return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
+  }
+  int embed_bwd_raw(const float* mel, int B_, int frames_, const act_t* dtok, const float* scale, float* dimg, float* dmel, hipStream_t st) {
+    CTRY(check_shape(B_, frames_));
+    if (!bn_a) { dmx_set_error("htsat: parameters are not loaded"); return DMX_ERR_STATE; }
+    InterpTables* T = nullptr;
+    CTRY(get_tables(frames_, &T));
+    embed_bwd(mel, *T, B_, frames_, dtok, scale, dimg, dmel, st);
+    return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
   }
 
   int check_shape(int B_, int frames_) const {
@@ -774,11 +839,7 @@ struct Htsat : Model {
     const int E = cfg.embed_dim;
     long long N = (long long)grid0 * grid0;
     act_t* cur = A.bf((size_t)B * N * E);
-    if (!dry) {
-      const EmbedParams p = embed_params(mel, *T);
-      const unsigned nb = (unsigned)(((long long)B * N + 127) / 128);
-      hipLaunchKernelGGL(embed_fwd_kernel, dim3(nb), dim3(128), 0, st, p, cur);
-    }
+    if (!dry) embed_fwd(mel, *T, B, frames, cur, st);
     tape.assign(stages.size(), {});
     t_stage_out.assign(stages.size(), nullptr);
     for (size_t s = 0; s < stages.size(); ++s) {
@@ -802,18 +863,12 @@ struct Htsat : Model {
         CRUN(ln_rows_fwd<act_t>(RowSrc{cur, C, 0, S.H, S.W}, ps.dev(b.ln1_g), ps.dev(b.ln1_b), y, rows, cfg.ln_eps, st));
         Epi e0;
         CRUN(linear_fwd(b.qkv, y, C, t.qkv, 3 * C, rows, e0, st));
-        if (!dry) {
-          const WinGeom g{B, S.H, S.W, C, b.heads, b.shift};
-          hipLaunchKernelGGL(win_attn_fwd_kernel, dim3((unsigned)(B * (S.H / WS) * (S.W / WS)), (unsigned)b.heads), dim3(64), 0, st, t.qkv, ao, ps.dev(b.rpb), g);
-        }
+        CRUN(win_attn_fwd(t.qkv, ao, ps.dev(b.rpb), WinGeom{B, S.H, S.W, C, b.heads, b.shift}, st));
         Epi er; er.flags = EPI_RESID; er.R = cur;
         CRUN(linear_fwd(b.proj, ao, C, t.x_mid, C, rows, er, st));
         CRUN(ln_rows_fwd<act_t>(RowSrc{t.x_mid, C, 0, S.H, S.W}, ps.dev(b.ln2_g), ps.dev(b.ln2_b), y, rows, cfg.ln_eps, st));
         CRUN(linear_fwd(b.fc1, y, C, t.u, 4 * C, rows, e0, st));
-        if (!dry) {
-          const long long n8 = rows * 4 * C / 8;
-          hipLaunchKernelGGL(gelu_fwd_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, t.u, gl, n8);
-        }
+        CRUN(gelu_fwd(t.u, gl, rows * 4 * C / 8, st));
         Epi er2; er2.flags = EPI_RESID; er2.R = t.x_mid;
         CRUN(linear_fwd(b.fc2, gl, 4 * C, x_out, C, rows, er2, st));
         A.release(mk);
@@ -875,17 +930,11 @@ struct Htsat : Model {
         act_t* dqkv = A.bf((size_t)rows * 3 * C);
         Epi e0;
         CRUN(linear_bwd(b.fc2, d, C, dg, 4 * C, rows, e0, st));
-        {
-          const long long n8 = rows * 4 * C / 8;
-          hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, t.u, dg, dg, n8);
-        }
+        CRUN(gelu_bwd(t.u, dg, dg, rows * 4 * C / 8, st));
         CRUN(linear_bwd(b.fc1, dg, 4 * C, dy, C, rows, e0, st));
         CRUN(ln_rows_bwd<act_t>(RowSrc{t.x_mid, C, 0, S.H, S.W}, ps.dev(b.ln2_g), dy, d, dmid, rows, cfg.ln_eps, st));
         CRUN(linear_bwd(b.proj, dmid, C, dy, C, rows, e0, st));                 // d attention output
-        {
-          const WinGeom g{B, S.H, S.W, C, b.heads, b.shift};
-          hipLaunchKernelGGL(win_attn_bwd_kernel, dim3((unsigned)(B * (S.H / WS) * (S.W / WS)), (unsigned)b.heads), dim3(64), 0, st, t.qkv, dy, dqkv, ps.dev(b.rpb), g);
-        }
+        CRUN(win_attn_bwd(t.qkv, dy, dqkv, ps.dev(b.rpb), WinGeom{B, S.H, S.W, C, b.heads, b.shift}, st));
         CRUN(linear_bwd(b.qkv, dqkv, 3 * C, dy, C, rows, e0, st));
         CRUN(ln_rows_bwd<act_t>(RowSrc{t.x_in, C, 0, S.H, S.W}, ps.dev(b.ln1_g), dy, dmid, din, rows, cfg.ln_eps, st));
         A.release(mk);
@@ -895,15 +944,7 @@ struct Htsat : Model {
     // input stage
     const int Tout = cfg.spec_size * (cfg.spec_size / cfg.num_mel_bins);
     float* dimg = A.f32((size_t)B * Tout * cfg.num_mel_bins);
-    {
-      const EmbedParams p = embed_params(t_mel, *T);
-      const long long ntok = (long long)B * grid0 * grid0;
-      const unsigned nb = (unsigned)((ntok + 127) / 128);
-      hipLaunchKernelGGL(embed_bwd_kernel, dim3(nb), dim3(128), 0, st, p, d, dimg);
-      const long long n = (long long)B * frames * cfg.num_mel_bins;
-      hipLaunchKernelGGL(interp_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dimg, T->kstart, T->kt, T->kw, scale, dmel, B, frames,
-                         cfg.num_mel_bins, Tout);
-    }
+    embed_bwd(t_mel, *T, B, frames, d, scale, dimg, dmel, st);
     const bool over = A.overflow;
     A.release(mk_all);
     if (over) { dmx_set_error("htsat backward: workspace too small (size it with dmx_htsat_workspace_bytes)"); return DMX_ERR_WORKSPACE; }
@@ -949,9 +990,10 @@ struct Htsat : Model {
 };
 
 Model* dmx_make_htsat(const dmx_htsat_config* c) {
-  if (c->num_stages < 1 || c->num_stages > 4 || c->window_size != WS || c->patch_size != 4 || (c->embed_dim % 8 || c->embed_dim < 8 || c->embed_dim > EMB_MAX) ||
+  // (no stage at all: the input stage and the final LayerNorm alone -- what the tests of the input stage build, at any embed width)
+  if (c->num_stages < 0 || c->num_stages > 4 || c->window_size != WS || c->patch_size != 4 || (c->embed_dim % 8 || c->embed_dim < 8 || c->embed_dim > EMB_MAX) ||
       c->num_mel_bins % 4 || c->spec_size % c->num_mel_bins || c->spec_size % (4 * WS)) {
-    dmx_set_error("htsat: unsupported configuration (window 8, patch 4, embed width a multiple of 8 up to 128, <= 4 stages)");
+    dmx_set_error("htsat: unsupported configuration (window 8, patch 4, embed width a multiple of 8 up to 128, 0 .. 4 stages)");
     return nullptr;
   }
   int C = c->embed_dim, side = c->spec_size / 4;
@@ -983,8 +1025,38 @@ void dmx_htsat_dims_impl(Model* m, int* tokens, int* channels) {
   *tokens = h->Tfinal; *channels = h->Cfinal;
 }
 
+// test hooks: the launchers the tower calls, one at a time (capi.hip dmx_htsat_*_raw)
+int dmx_htsat_ln_fwd_impl(const act_t* x, void* y, const float* gamma, const float* beta, long long rows, int C, int merge, int H, int W,
+                          float eps, int out_fp32, hipStream_t st) {
+  const RowSrc s{x, C, merge ? 1 : 0, H, W};
+  return out_fp32 ? ln_rows_fwd<float>(s, gamma, beta, (float*)y, rows, eps, st) : ln_rows_fwd<act_t>(s, gamma, beta, (act_t*)y, rows, eps, st);
+}
+int dmx_htsat_ln_bwd_impl(const act_t* x, const void* dy, const act_t* add, act_t* dx, const float* gamma, long long rows, int C, int merge,
+                          int H, int W, float eps, int dy_fp32, hipStream_t st) {
+  const RowSrc s{x, C, merge ? 1 : 0, H, W};
+  return dy_fp32 ? ln_rows_bwd<float>(s, gamma, (const float*)dy, add, dx, rows, eps, st)
+                 : ln_rows_bwd<act_t>(s, gamma, (const act_t*)dy, add, dx, rows, eps, st);
+}
+int dmx_htsat_gelu_fwd_impl(const act_t* u, act_t* y, long long n8, hipStream_t st) { return gelu_fwd(u, y, n8, st); }
+int dmx_htsat_gelu_bwd_impl(const act_t* u, const act_t* dy, act_t* du, long long n8, hipStream_t st) { return gelu_bwd(u, dy, du, n8, st); }
+int dmx_htsat_win_attn_fwd_impl(const act_t* qkv, act_t* out, const float* bias_table, int B, int H, int W, int C, int heads, int shift,
+                                hipStream_t st) {
+  return win_attn_fwd(qkv, out, bias_table, WinGeom{B, H, W, C, heads, shift}, st);
+}
+int dmx_htsat_win_attn_bwd_impl(const act_t* qkv, const act_t* dout, act_t* dqkv, const float* bias_table, int B, int H, int W, int C,
+                                int heads, int shift, hipStream_t st) {
+  return win_attn_bwd(qkv, dout, dqkv, bias_table, WinGeom{B, H, W, C, heads, shift}, st);
+}
+int dmx_htsat_embed_fwd_impl(Model* m, const float* mel, int B, int frames, act_t* tokens, hipStream_t st) {
+  return static_cast<Htsat*>(m)->embed_fwd_raw(mel, B, frames, tokens, st);
+}
+int dmx_htsat_embed_bwd_impl(Model* m, const float* mel, int B, int frames, const act_t* dtok, const float* scale, float* dimg, float* dmel,
+                             hipStream_t st) {
+  return static_cast<Htsat*>(m)->embed_bwd_raw(mel, B, frames, dtok, scale, dimg, dmel, st);
+}
+
 int dmx_gram_fwd_impl(const float* F, float* G, int B, int T, int C, hipStream_t st) {
-  if (T < 1 || T > 96 || C < 1) return DMX_ERR_SHAPE;
+  if (B < 1 || T < 1 || T > 96 || C < 1) return DMX_ERR_SHAPE;
   const size_t smem = (size_t)T * 128 * sizeof(float);
   static bool attr = false;
   if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 128 * 4); attr = true; }
@@ -992,7 +1064,7 @@ int dmx_gram_fwd_impl(const float* F, float* G, int B, int T, int C, hipStream_t
   return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
 }
 int dmx_gram_bwd_impl(const float* F, const float* dG, float* dF, int B, int T, int C, hipStream_t st) {
-  if (T < 1 || C < 1) return DMX_ERR_SHAPE;
+  if (B < 1 || T < 1 || C < 1) return DMX_ERR_SHAPE;
   hipLaunchKernelGGL(gram_bwd_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)((T + 63) / 64), (unsigned)B), dim3(256), 0, st, F, dG, dF, T, C);
   return hipGetLastError() == hipSuccess ? DMX_OK : DMX_ERR_LAUNCH;
 }

@@ -54,5 +54,18 @@ int dmx_htsat_fwd_impl(Model* m, const float* mel, int B, int frames, float* fea
 int dmx_htsat_bwd_impl(Model* m, const float* dfeat, const float* scale, float* dmel, hipStream_t st);
 void dmx_htsat_dims_impl(Model* m, int* tokens, int* channels);
 size_t dmx_htsat_tape_impl(Model* m, int stage, int block, int which, const act_t** p);
+int dmx_htsat_ln_fwd_impl(const act_t* x, void* y, const float* gamma, const float* beta, long long rows, int C, int merge, int H, int W,
+                          float eps, int out_fp32, hipStream_t st);
+int dmx_htsat_ln_bwd_impl(const act_t* x, const void* dy, const act_t* add, act_t* dx, const float* gamma, long long rows, int C, int merge,
+                          int H, int W, float eps, int dy_fp32, hipStream_t st);
+int dmx_htsat_gelu_fwd_impl(const act_t* u, act_t* y, long long n8, hipStream_t st);
+int dmx_htsat_gelu_bwd_impl(const act_t* u, const act_t* dy, act_t* du, long long n8, hipStream_t st);
+int dmx_htsat_win_attn_fwd_impl(const act_t* qkv, act_t* out, const float* bias_table, int B, int H, int W, int C, int heads, int shift,
+                                hipStream_t st);
+int dmx_htsat_win_attn_bwd_impl(const act_t* qkv, const act_t* dout, act_t* dqkv, const float* bias_table, int B, int H, int W, int C,
+                                int heads, int shift, hipStream_t st);
+int dmx_htsat_embed_fwd_impl(Model* m, const float* mel, int B, int frames, act_t* tokens, hipStream_t st);
+int dmx_htsat_embed_bwd_impl(Model* m, const float* mel, int B, int frames, const act_t* dtok, const float* scale, float* dimg, float* dmel,
+                             hipStream_t st);
 int dmx_gram_fwd_impl(const float* F, float* G, int B, int T, int C, hipStream_t st);
 int dmx_gram_bwd_impl(const float* F, const float* dG, float* dF, int B, int T, int C, hipStream_t st);

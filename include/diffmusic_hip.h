@@ -174,7 +174,7 @@ typedef struct dmx_htsat_config {
   int patch_size;     /* 4 (= stride) */
   int embed_dim;      /* 96 */
   int window_size;    /* 8 */
-  int num_stages;     /* 4 */
+  int num_stages;     /* 4 (0: the input stage and the final LayerNorm alone, for tests of the input stage) */
   int depths[4];      /* 2, 2, 6, 2 */
   int num_heads[4];   /* 4, 8, 16, 32 (head dim 24 in every stage) */
   float ln_eps;       /* 1e-5 */
@@ -593,6 +593,32 @@ int dmx_conv2d_raw(const float* w_host, const float* b_host, const void* x, void
 int dmx_groupnorm_bwd_raw(const void* x, const void* dy, const void* add, void* dx, const float* stats, const float* scale, const float* shift,
                           float* k0, float* k1, float* partial, int B, int P, int C, int G, int silu, int nreg, float* const* part,
                           const int* geom, void* stream);
+/* test hooks: the kernels of the CLAP HTS-AT tower (csrc/htsat.hip) one at a time, each through the launcher the tower itself calls.
+ * 16-bit tensors are activations (dmx_act_dtype), token-major; gamma / beta / bias tables / mel / dimg / dmel fp32.
+ * ln_rows: LayerNorm over `rows` rows of C channels (merge = 0) or of the 4C channels of the 2 x 2 tokens a patch merging gathers from an
+ *   H x W grid (merge = 1, row r = image r / (H/2 W/2), cell r mod (H/2 W/2); parts (2oy, 2ox) | (2oy + 1, 2ox) | (2oy, 2ox + 1) |
+ *   (2oy + 1, 2ox + 1)); y (rows, row width) 16-bit or fp32 (out_fp32).  Backward: dy (rows, row width) 16-bit or fp32 (dy_fp32), dx written
+ *   at the rows' source positions in x's layout, `add` (optional, x's layout, merge = 0 only) added.  C % 8 == 0, row width <= 1536.
+ * gelu: erf-GELU over n8 groups of 8 values; the backward's du may be dy.
+ * win_attn: window-8 attention of q|k|v rows (B, H W, 3C), heads of 24 channels, relative position bias table (225, heads), cyclic shift
+ *   (0 .. 7) with -100 between shift regions; out (B, H W, C); backward: dout (B, H W, C) -> dqkv (B, H W, 3C).  H, W multiples of 8.
+ * embed: the fused input stage of handle m (BatchNorm, bicubic stretch, image fold, patch convolution, LayerNorm): mel (batch, frames,
+ *   num_mel_bins) -> tokens (batch, (spec_size / 4)^2, embed_dim); backward from mel and dtok: dimg (batch, Tout, num_mel_bins) is the gradient
+ *   of the stretched, BatchNorm'ed image (Tout = spec_size^2 / num_mel_bins), dmel (batch, frames, num_mel_bins) its pull-back through the
+ *   stretch times scale[b] (scale may be NULL).  2 <= frames <= Tout.  Neither touches the tape of a kept forward. */
+int dmx_htsat_ln_rows_fwd_raw(const void* x, void* y, const float* gamma, const float* beta, long long rows, int C, int merge, int H, int W,
+                              float eps, int out_fp32, void* stream);
+int dmx_htsat_ln_rows_bwd_raw(const void* x, const void* dy, const void* add, void* dx, const float* gamma, long long rows, int C, int merge,
+                              int H, int W, float eps, int dy_fp32, void* stream);
+int dmx_htsat_gelu_fwd_raw(const void* u, void* y, long long n8, void* stream);
+int dmx_htsat_gelu_bwd_raw(const void* u, const void* dy, void* du, long long n8, void* stream);
+int dmx_htsat_win_attn_fwd_raw(const void* qkv, void* out, const float* bias_table, int B, int H, int W, int C, int heads, int shift,
+                               void* stream);
+int dmx_htsat_win_attn_bwd_raw(const void* qkv, const void* dout, void* dqkv, const float* bias_table, int B, int H, int W, int C, int heads,
+                               int shift, void* stream);
+int dmx_htsat_embed_fwd_raw(dmx_model* m, const float* mel, int batch, int frames, void* tokens, void* stream);
+int dmx_htsat_embed_bwd_raw(dmx_model* m, const float* mel, int batch, int frames, const void* dtok, const float* scale, float* dimg,
+                            float* dmel, void* stream);
 
 #ifdef __cplusplus
 }
