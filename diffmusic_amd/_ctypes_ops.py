@@ -537,6 +537,49 @@ def tf_gain(audio, x, gain_t, L, Lfull, *, out=None):
     return out
 
 
+def _mdct_step(who, x, step_t, L, Lfull):
+    _rows(who, x, L)
+    B, T = x.shape[0], _lib.lib().dmx_mdct_frames(L)
+    assert Lfull >= L, (L, Lfull)
+    assert step_t.is_cuda and step_t.dtype == torch.float32 and step_t.is_contiguous() and step_t.device == x.device and \
+        tuple(step_t.shape) in ((T, 512), (B, T, 512)), (who, tuple(step_t.shape), (B, T, 512))
+    return B, T
+
+
+def _mdct_out(who, out, x, B, Lfull):
+    if out is None:
+        return torch.empty(B, Lfull, dtype=torch.float32, device=x.device)
+    _rows(who, out, Lfull)
+    assert out.shape[0] == B and out.device == x.device, (out.shape, B)
+    return out
+
+
+def mdct_quant(audio, x, step_t, L, Lfull, *, passthrough=False, want_codes=False, out=None):
+    """x (B, >= L) with any row stride, step_t (frames, 512) shared or (B, frames, 512), frames = ceil(L / 512) + 1 -> (y (B, Lfull), codes):
+    the MDCT quantiser Phi^T Q(Phi x[:, :L]) (csrc/mdct_quant.hip), +0 past L; codes (B, frames, 512) int32 with `want_codes`, else None.
+    passthrough: the straight-through transpose Phi^T K Phi instead (K = 0 where the step is +inf, else 1), which codes nothing.
+    out: caller-owned (B, >= Lfull) fp32 with any row stride; only out[:, :Lfull] is written."""
+    B, T = _mdct_step("mdct_quant", x, step_t, L, Lfull)
+    assert not (passthrough and want_codes), "mdct_quant: the pass-through form codes nothing (want_codes goes with the quantiser)"
+    out = _mdct_out("mdct_quant", out, x, B, Lfull)
+    codes = torch.empty(B, T, 512, dtype=torch.int32, device=x.device) if want_codes else None
+    _lib.check(_lib.lib().dmx_mdct_quant(audio, _p(x), x.stride(0), _p(step_t), T * 512 if step_t.dim() == 3 else 0, _p(codes), _p(out),
+                                         out.stride(0), B, L, Lfull, 1 if passthrough else 0, _stream()), "mdct_quant")
+    return out, codes
+
+
+def mdct_project(audio, x, step_t, codes, L, Lfull, *, out=None):
+    """x (B, >= L), step_t as in `mdct_quant`, codes (B, frames, 512) int32 of `mdct_quant` -> (B, Lfull): the coefficients of x clamped into
+    the cells [(q - 1/2) D, (q + 1/2) D] of the codes on whole frames (1 <= t <= L // 512 - 1) where 0 < D < inf and q is coded, resynthesised."""
+    B, T = _mdct_step("mdct_project", x, step_t, L, Lfull)
+    assert codes.is_cuda and codes.device == x.device and codes.dtype == torch.int32 and codes.is_contiguous() and \
+        tuple(codes.shape) == (B, T, 512), ("mdct_project", tuple(codes.shape), (B, T, 512))
+    out = _mdct_out("mdct_project", out, x, B, Lfull)
+    _lib.check(_lib.lib().dmx_mdct_project(audio, _p(x), x.stride(0), _p(step_t), T * 512 if step_t.dim() == 3 else 0, _p(codes), _p(out),
+                                           out.stride(0), B, L, Lfull, _stream()), "mdct_project")
+    return out
+
+
 def tf_curve(audio, x, curve, L, Lfull):
     """x (B, >= L) with any row stride, curve (513,) shared or (B, 513) -> (B, Lfull): `tf_gain` with a gain constant in time, every frame
     reading the clip's one row (csrc/tf_gain.hip, frame stride 0), +0 past L.  Symmetric: the same call is the transpose."""

@@ -207,6 +207,11 @@ _SIGS = {
     "dmx_audio_tf_wgrad_segments": (C.c_int, [C.c_int]),
     "dmx_audio_tf_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dmx_audio_eq_update": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_void_p]),
+    "dmx_mdct_frames": (C.c_int, [C.c_int]),
+    "dmx_mdct_quant": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int,
+                                 C.c_int, C.c_int, C.c_void_p]),
+    "dmx_mdct_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int,
+                                   C.c_int, C.c_int, C.c_void_p]),
     "dmx_audio_melscale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
     "dmx_mask_apply": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dmx_l2_loss": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_void_p]),
@@ -240,7 +245,8 @@ ADDED_IN_V4 = ("dmx_vae_encoder_create", "dmx_vae_encoder_workspace_bytes", "dmx
                "dmx_stem_mix_fwd", "dmx_stem_mix_bwd", "dmx_stem_project", "dmx_audio_tf_gain", "dmx_audio_tf_frames",
                "dmx_audio_tf_curve", "dmx_audio_tf_wgrad_segments", "dmx_audio_tf_wgrad", "dmx_audio_eq_update", "dmx_drc_fwd", "dmx_drc_bwd",
                "dmx_warp_fwd", "dmx_warp_bwd", "dmx_warp_wgrad", "dmx_warp_update", "dmx_drc_fwd_p", "dmx_drc_bwd_p", "dmx_drc_pgrad",
-               "dmx_drc_update", "dmx_click_detect", "dmx_click_mask", "dmx_mask_rows", "dmx_declick_blend")
+               "dmx_drc_update", "dmx_click_detect", "dmx_click_mask", "dmx_mask_rows", "dmx_declick_blend", "dmx_mdct_frames",
+               "dmx_mdct_quant", "dmx_mdct_project")
 
 _lib = None
 
@@ -250,7 +256,7 @@ def check_symbols(h, path=LIB_PATH):
     for name in ADDED_IN_V4:
         if not hasattr(h, name):
             raise RuntimeError(f"{path} reports ABI version {ABI_VERSION} but does not export `{name}` (a build from before the VAE "
-                               "encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter / blind-wow-and-flutter / blind-de-compression / declicking entry points): rebuild it (python -m diffmusic_amd.build --force)")
+                               "encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter / blind-wow-and-flutter / blind-de-compression / declicking / codec-restoration entry points): rebuild it (python -m diffmusic_amd.build --force)")
 
 
 def lib():

@@ -13,6 +13,7 @@ struct dmx_audio {
   bool fused = false;
   void* fused_mem = nullptr;
   DmxStftMelTables ft;
+  DmxMdctTables mt = {nullptr, nullptr, nullptr, nullptr};   // mdct_quant.hip: in the same allocation as the fused tables
 };
 
 // twiddles, window and the two compacted views of the (bins x 64) filterbank for stft_mel.hip, in ONE device allocation
@@ -32,29 +33,39 @@ static bool build_fused_tables(dmx_audio* a, const float* fb) {
     if (lo >= 0) { mlo[k] = lo; mlen[k] = hi - lo + 1; if (mlen[k] > mmax) mmax = mlen[k]; }
   }
   std::vector<float> fbc((size_t)kmax * NMv, 0.f), fbr((size_t)mmax * NBP, 0.f), win(N), tw(2 * (size_t)N);
+  std::vector<float> mpre(2 * (size_t)N), mpost((size_t)N), mwin(N);         // the MDCT's twiddles and sine window: double, rounded once
   for (int m = 0; m < NMv; ++m) for (int i = 0; i < klen[m]; ++i) fbc[(size_t)i * NMv + m] = fb[(size_t)(klo[m] + i) * NMv + m];
   for (int k = 0; k < NBv; ++k) for (int i = 0; i < mlen[k]; ++i) fbr[(size_t)i * NBP + k] = fb[(size_t)k * NMv + mlo[k] + i];
   const double two_pi = 6.283185307179586476925286766559;
   for (int n = 0; n < N; ++n) {
     win[n] = a->hann ? (float)(0.5 - 0.5 * cos(two_pi * n / N)) : 1.f;       // periodic Hann (torch.hann_window default) / rectangular
     tw[2 * n] = (float)cos(two_pi * n / N); tw[2 * n + 1] = (float)(-sin(two_pi * n / N));
+    mpre[2 * n] = (float)cos(two_pi * n / (2 * N)); mpre[2 * n + 1] = (float)(-sin(two_pi * n / (2 * N)));
+    mwin[n] = (float)sin(two_pi * (n + 0.5) / (2 * N));
+  }
+  for (int k = 0; k < N / 2; ++k) {
+    const double ph = two_pi * (N / 4 + 0.5) * (k + 0.5) / N;               // pi n0 (k + 1/2) / 512, n0 = 256.5
+    mpost[2 * k] = (float)cos(ph); mpost[2 * k + 1] = (float)(-sin(ph));
   }
   size_t off = 0;
   auto place = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
   const size_t o_tw = place(tw.size() * 4), o_win = place(win.size() * 4), o_klo = place(NMv * 4), o_klen = place(NMv * 4),
-               o_mlo = place(NBP * 4), o_mlen = place(NBP * 4), o_fbc = place(fbc.size() * 4), o_fbr = place(fbr.size() * 4);
+               o_mlo = place(NBP * 4), o_mlen = place(NBP * 4), o_fbc = place(fbc.size() * 4), o_fbr = place(fbr.size() * 4),
+               o_mpre = place(mpre.size() * 4), o_mpost = place(mpost.size() * 4), o_mwin = place(mwin.size() * 4);
   char* d = nullptr;
   if (hipMalloc(&d, off) != hipSuccess) return false;
   // every table upload is checked: a failed copy returns false and the dense-DFT path is used (a half-filled table must never be read)
   const struct { size_t off; const void* src; size_t bytes; } ups[] = {
       {o_tw, tw.data(), tw.size() * 4}, {o_win, win.data(), win.size() * 4}, {o_klo, klo.data(), (size_t)NMv * 4}, {o_klen, klen.data(), (size_t)NMv * 4},
-      {o_mlo, mlo.data(), (size_t)NBP * 4}, {o_mlen, mlen.data(), (size_t)NBP * 4}, {o_fbc, fbc.data(), fbc.size() * 4}, {o_fbr, fbr.data(), fbr.size() * 4}};
+      {o_mlo, mlo.data(), (size_t)NBP * 4}, {o_mlen, mlen.data(), (size_t)NBP * 4}, {o_fbc, fbc.data(), fbc.size() * 4}, {o_fbr, fbr.data(), fbr.size() * 4},
+      {o_mpre, mpre.data(), mpre.size() * 4}, {o_mpost, mpost.data(), mpost.size() * 4}, {o_mwin, mwin.data(), mwin.size() * 4}};
   for (const auto& u : ups)
     if (hipMemcpy(d + u.off, u.src, u.bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return false; }
   a->fused_mem = d;
   a->ft.tw = (const float2*)(d + o_tw); a->ft.win = (const float*)(d + o_win);
   a->ft.klo = (const int*)(d + o_klo); a->ft.klen = (const int*)(d + o_klen); a->ft.fbc = (const float*)(d + o_fbc); a->ft.kmax = kmax;
   a->ft.mlo = (const int*)(d + o_mlo); a->ft.mlen = (const int*)(d + o_mlen); a->ft.fbr = (const float*)(d + o_fbr); a->ft.mmax = mmax;
+  a->mt.tw = a->ft.tw; a->mt.pre = (const float2*)(d + o_mpre); a->mt.post = (const float2*)(d + o_mpost); a->mt.win = (const float*)(d + o_mwin);
   return true;
 }
 // state layout of the fused path: [waveform kept for transform_bwd: B x L][per-workgroup partial sums of the loss: B x parts]
@@ -236,6 +247,31 @@ int dmx_audio_tf_wgrad(dmx_audio* a, const float* x, long long x_stride, const f
   const int rc = dmx_tf_wgrad(a->ft, x, x_stride, dy, dy_stride, partials, batch, L, ST(stream));
   if (rc == DMX_ERR_SHAPE) dmx_set_error("tf_wgrad: clip too long");
   return rc;
+}
+int dmx_mdct_frames(int L) { return L < 1 ? 0 : dmx_mdct_num_frames(L); }
+static int mdct_entry(const char* who, dmx_audio* a, const float* x, long long x_stride, const float* step, long long step_clip_stride, int* codes,
+                      float* out, long long out_stride, int batch, int L, int full, int mode, void* stream) {
+  if (!a || !x || !step || !out || (mode == DMX_MDCT_PROJECT && !codes)) { dmx_set_error("%s: null handle or pointer", who); return DMX_ERR_SHAPE; }
+  if (a->n_fft != 1024 || !a->fused) { dmx_set_error("%s needs a handle with n_fft = 1024 (its FFT tables)", who); return DMX_ERR_SHAPE; }
+  if (batch < 1 || batch > 65535 || L < 1 || full < L || x_stride < L || out_stride < full ||
+      (step_clip_stride != 0 && step_clip_stride < (long long)dmx_mdct_num_frames(L) * 512)) {
+    dmx_set_error("%s: x (batch, >= L), out (batch, full) with row strides >= L and >= full, 1 <= L <= full, step (frames, 512) per clip with clip "
+                  "stride 0 (shared) or >= frames * 512, frames = ceil(L / 512) + 1, 1 <= batch <= 65535", who);
+    return DMX_ERR_SHAPE;
+  }
+  const int rc = dmx_mdct_run(a->mt, x, x_stride, step, step_clip_stride, codes, out, out_stride, batch, L, full, mode, ST(stream));
+  if (rc == DMX_ERR_SHAPE) dmx_set_error("%s: clip too long", who);
+  return rc;
+}
+int dmx_mdct_quant(dmx_audio* a, const float* x, long long x_stride, const float* step, long long step_clip_stride, int* codes, float* out,
+                   long long out_stride, int batch, int L, int full, int pass, void* stream) {
+  return mdct_entry("mdct_quant", a, x, x_stride, step, step_clip_stride, pass ? nullptr : codes, out, out_stride, batch, L, full,
+                    pass ? DMX_MDCT_PASS : DMX_MDCT_QUANT, stream);
+}
+int dmx_mdct_project(dmx_audio* a, const float* x, long long x_stride, const float* step, long long step_clip_stride, const int* codes, float* out,
+                     long long out_stride, int batch, int L, int full, void* stream) {
+  return mdct_entry("mdct_project", a, x, x_stride, step, step_clip_stride, const_cast<int*>(codes), out, out_stride, batch, L, full,
+                    DMX_MDCT_PROJECT, stream);
 }
 int dmx_audio_melscale(dmx_audio* a, const float* mag, float* mel_out, int batch, int T, float lo, float hi, void* stream) {
   return dmx_melscale(mag, a->fb, mel_out, batch, T, a->bins, a->n_mels, lo, hi, ST(stream));

@@ -104,6 +104,20 @@ int dmx_tf_gain_frames(int L);                           // ceil(L / 256) + 3
 int dmx_tf_gain(const DmxStftMelTables& t, const float* x, long long x_stride, const float* gain, long long gain_clip_stride,
                 long long gain_frame_stride, float* out, long long out_stride, int B, int L, int full, hipStream_t st);
 
+// ---- mdct_quant.hip (codec restoration: MDCT at N = 512 with zero extension and the sine window, a per-coefficient map, the transpose)
+struct DmxMdctTables {
+  const float2* tw;     // exp(-2 pi i m / 1024), the FFT's (the table of DmxStftMelTables)
+  const float2* pre;    // exp(-i pi n / 1024), n = 0 .. 1023
+  const float2* post;   // exp(-i pi 256.5 (k + 1/2) / 512), k = 0 .. 511
+  const float* win;     // sin(pi (n + 1/2) / 1024)
+};
+constexpr int DMX_MDCT_QUANT = 0, DMX_MDCT_PASS = 1, DMX_MDCT_PROJECT = 2;
+int dmx_mdct_num_frames(int L);                          // ceil(L / 512) + 1
+// out[b, 0:L] = Phi^T f(Phi x[b, 0:L]), +0 on [L, full); step (T, 512) rows per clip, clip stride 0 = one grid for every clip;
+// codes (B, T, 512) int32: QUANT writes them when given, PROJECT reads them, PASS ignores them
+int dmx_mdct_run(const DmxMdctTables& t, const float* x, long long x_stride, const float* step, long long step_clip_stride, int* codes, float* out,
+                 long long out_stride, int B, int L, int full, int mode, hipStream_t st);
+
 // ---- tf_eq.hip (blind equalisation: the gradient of a loss in a time-invariant gain curve g[513], and its Adam + projection update)
 int dmx_tf_wgrad_segments(int L);                        // ceil(frames / 16)
 // part[b, seg, 0:513] = the terms of frames [16 seg, 16 seg + 16) of dg[b, k] = (h_k / 1536) sum_t Re(X[k, t] conj(U[k, t])); uses t.tw, t.win

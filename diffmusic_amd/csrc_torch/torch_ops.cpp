@@ -58,6 +58,9 @@
 #pragma weak dmx_click_mask
 #pragma weak dmx_mask_rows
 #pragma weak dmx_declick_blend
+#pragma weak dmx_mdct_frames
+#pragma weak dmx_mdct_quant
+#pragma weak dmx_mdct_project
 
 namespace {
 
@@ -598,6 +601,43 @@ at::Tensor tf_gain(int64_t audio, const at::Tensor& x, const at::Tensor& gain_t,
                        y.data_ptr<float>(), y.stride(0), (int)B, (int)L, (int)Lfull, cur_stream()), "tf_gain");
   return y;
 }
+// codec restoration (include/diffmusic_hip.h dmx_mdct_quant / dmx_mdct_project): x (B, >= L), step_t (frames, 512) shared or (B, frames, 512),
+// frames = ceil(L / 512) + 1 -> (B, Lfull).  out: caller-owned (B, >= Lfull) fp32 with any row stride; only out[:, :Lfull] is written
+inline int64_t mdct_step_ok(const at::Tensor& x, const at::Tensor& step_t, int64_t L, int64_t Lfull) {
+  rows_ok(x, L, "x");
+  TORCH_CHECK(Lfull >= L, "Lfull must be >= L");
+  f32_cuda(step_t, "step_t");
+  const int64_t B = x.size(0), T = dmx_mdct_frames((int)L);
+  TORCH_CHECK(step_t.device() == x.device() && ((step_t.dim() == 2 && step_t.size(0) == T && step_t.size(1) == 512) ||
+              (step_t.dim() == 3 && step_t.size(0) == B && step_t.size(1) == T && step_t.size(2) == 512)),
+              "step_t must be (", T, ", 512) or (", B, ", ", T, ", 512) on x's device");
+  return T;
+}
+// -> (y, codes): codes (B, frames, 512) int32 with want_codes (the quantiser only), else None; passthrough: the straight-through transpose
+std::tuple<at::Tensor, std::optional<at::Tensor>> mdct_quant(int64_t audio, const at::Tensor& x, const at::Tensor& step_t, int64_t L, int64_t Lfull,
+                                                             bool passthrough, bool want_codes, const std::optional<at::Tensor>& out) {
+  const int64_t T = mdct_step_ok(x, step_t, L, Lfull), B = x.size(0);
+  TORCH_CHECK(!(passthrough && want_codes), "mdct_quant: the pass-through form codes nothing (want_codes goes with the quantiser)");
+  DMX_DEVICE_OF(x);
+  at::Tensor y = rows_out(out, x, Lfull, Lfull, false, "out");
+  std::optional<at::Tensor> codes;
+  if (want_codes) codes = at::empty({B, T, 512}, x.options().dtype(at::kInt));
+  ok(dmx_mdct_quant((dmx_audio*)audio, x.data_ptr<float>(), x.stride(0), step_t.data_ptr<float>(), step_t.dim() == 3 ? T * 512 : 0,
+                    codes ? codes->data_ptr<int>() : nullptr, y.data_ptr<float>(), y.stride(0), (int)B, (int)L, (int)Lfull, passthrough ? 1 : 0,
+                    cur_stream()), "mdct_quant");
+  return {y, codes};
+}
+at::Tensor mdct_project(int64_t audio, const at::Tensor& x, const at::Tensor& step_t, const at::Tensor& codes, int64_t L, int64_t Lfull,
+                        const std::optional<at::Tensor>& out) {
+  const int64_t T = mdct_step_ok(x, step_t, L, Lfull), B = x.size(0);
+  TORCH_CHECK(codes.is_cuda() && codes.device() == x.device() && codes.scalar_type() == at::kInt && codes.is_contiguous() && codes.dim() == 3 &&
+              codes.size(0) == B && codes.size(1) == T && codes.size(2) == 512, "codes must be contiguous int32 (", B, ", ", T, ", 512) on x's device");
+  DMX_DEVICE_OF(x);
+  at::Tensor y = rows_out(out, x, Lfull, Lfull, false, "out");
+  ok(dmx_mdct_project((dmx_audio*)audio, x.data_ptr<float>(), x.stride(0), step_t.data_ptr<float>(), step_t.dim() == 3 ? T * 512 : 0,
+                      codes.data_ptr<int>(), y.data_ptr<float>(), y.stride(0), (int)B, (int)L, (int)Lfull, cur_stream()), "mdct_project");
+  return y;
+}
 // blind equalisation (include/diffmusic_hip.h dmx_audio_tf_curve / dmx_audio_tf_wgrad / dmx_audio_eq_update): one gain curve per clip
 at::Tensor tf_curve(int64_t audio, const at::Tensor& x, const at::Tensor& curve, int64_t L, int64_t Lfull) {
   rows_ok(x, L, "x");
@@ -936,10 +976,13 @@ TORCH_LIBRARY(diffmusic_hip, m) {
                                                          {"dmx_click_detect", (const void*)&dmx_click_detect},
                                                          {"dmx_click_mask", (const void*)&dmx_click_mask},
                                                          {"dmx_mask_rows", (const void*)&dmx_mask_rows},
-                                                         {"dmx_declick_blend", (const void*)&dmx_declick_blend}};
+                                                         {"dmx_declick_blend", (const void*)&dmx_declick_blend},
+                                                         {"dmx_mdct_frames", (const void*)&dmx_mdct_frames},
+                                                         {"dmx_mdct_quant", (const void*)&dmx_mdct_quant},
+                                                         {"dmx_mdct_project", (const void*)&dmx_mdct_project}};
     for (const auto& s : added)
       TORCH_CHECK(s.second != nullptr, "the loaded libdiffmusic_hip.so reports C-ABI version ", DMX_ABI_VERSION, " but does not export `", s.first,
-                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter / blind-wow-and-flutter / blind-de-compression / declicking entry points): rebuild with `python -m diffmusic_amd.build --force`");
+                  "` (a build from before the VAE encoder / track-mode / declipping / blind-dereverberation / source-separation / time-frequency-masking / blind-equalisation / de-compression / wow-and-flutter / blind-wow-and-flutter / blind-de-compression / declicking / codec-restoration entry points): rebuild with `python -m diffmusic_amd.build --force`");
   }
   m.def("abi_version() -> int", &abi_version);
   // Schemas: ops that write into a caller-owned tensor besides their outputs declare it (a!): `state` of the measurement front end
@@ -990,6 +1033,9 @@ TORCH_LIBRARY(diffmusic_hip, m) {
   m.def("declick_blend(Tensor x, Tensor y, Tensor mask, int L, int fade) -> Tensor", &declick_blend);
   m.def("noise_add(Tensor y, Tensor noise, float sigma) -> Tensor", &noise_add);
   m.def("tf_gain(int audio, Tensor x, Tensor gain_t, int L, int Lfull, *, Tensor(a!)? out=None) -> Tensor", &tf_gain);
+  m.def("mdct_quant(int audio, Tensor x, Tensor step_t, int L, int Lfull, *, bool passthrough=False, bool want_codes=False, "
+        "Tensor(a!)? out=None) -> (Tensor, Tensor?)", &mdct_quant);
+  m.def("mdct_project(int audio, Tensor x, Tensor step_t, Tensor codes, int L, int Lfull, *, Tensor(a!)? out=None) -> Tensor", &mdct_project);
   m.def("tf_curve(int audio, Tensor x, Tensor curve, int L, int Lfull) -> Tensor", &tf_curve);
   m.def("tf_wgrad(int audio, Tensor dy, Tensor x, int L) -> Tensor", &tf_wgrad);
   m.def("eq_update(Tensor partials, Tensor(a!) g, Tensor(b!) m, Tensor(c!) v, int k, float lr, float beta1, float beta2, float eps, bool peak) "

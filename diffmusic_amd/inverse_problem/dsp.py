@@ -112,6 +112,112 @@ def hum_boxes(f0_hz, harmonics=1, width_hz=32.0, gain=0.0):
     return [(m * f0_hz - 0.5 * width_hz, m * f0_hz + 0.5 * width_hz, None, None, float(gain)) for m in range(1, harmonics + 1)]
 
 
+# ---- codec restoration (CodecOperator; csrc/mdct_quant.hip): MDCT with N = 512 coefficients per frame, frame length 1024, hop 512, sine
+# window, frame t starts at sample (t - 1) * 512; coefficient k sits at (k + 1/2) * sample_rate / 1024
+MDCT_N = 512
+
+
+def mdct_frames(length):
+    """Frames of the MDCT of a clip of `length` samples: T = ceil(length / 512) + 1."""
+    length = int(length)
+    if length < 1:
+        raise ValueError(f"length = {length!r}: at least one sample")
+    return -(-length // MDCT_N) + 1
+
+
+def _mdct_basis():
+    """(1024, 512) float64: sqrt(2 / N) w[n] cos(pi / N (n + 1/2 + N / 2)(k + 1/2)), the windowed, scaled MDCT basis of one frame."""
+    n, k = np.arange(2 * MDCT_N, dtype=np.float64)[:, None], np.arange(MDCT_N, dtype=np.float64)[None]
+    w = np.sin(np.pi * (n + 0.5) / (2 * MDCT_N))
+    return math.sqrt(2.0 / MDCT_N) * w * np.cos(np.pi / MDCT_N * (n + 0.5 + MDCT_N / 2) * (k + 0.5))
+
+
+def mdct(audio):
+    """audio (..., L) -> (..., 512, T) float64 MDCT coefficients from the definition, the clip zero outside [0, L) (host; not on the step path)."""
+    x = np.asarray(audio, dtype=np.float64)
+    L = x.shape[-1]
+    T = mdct_frames(L)
+    pad = np.zeros(x.shape[:-1] + ((T + 1) * MDCT_N,))
+    pad[..., MDCT_N:MDCT_N + L] = x                                    # frame t starts at (t - 1) 512: shift by one hop
+    fr = np.stack([pad[..., t * MDCT_N:t * MDCT_N + 2 * MDCT_N] for t in range(T)], axis=-2)      # (..., T, 1024)
+    return np.swapaxes(fr @ _mdct_basis(), -1, -2)
+
+
+def imdct(coeffs, length):
+    """coeffs (..., 512, T) -> (..., length) float64: the transpose of `mdct` (the same cosines, the window, overlap-add, cropped to the clip);
+    with T = mdct_frames(length), imdct(mdct(x), L) = x."""
+    c = np.asarray(coeffs, dtype=np.float64)
+    T = mdct_frames(length)
+    if c.shape[-2:] != (MDCT_N, T):
+        raise ValueError(f"coeffs have shape {c.shape}: (..., {MDCT_N}, {T}) for a clip of {length} samples")
+    fr = np.swapaxes(c, -1, -2) @ _mdct_basis().T                      # (..., T, 1024)
+    out = np.zeros(c.shape[:-2] + ((T + 1) * MDCT_N,))
+    for t in range(T):
+        out[..., t * MDCT_N:t * MDCT_N + 2 * MDCT_N] += fr[..., t, :]
+    return out[..., MDCT_N:MDCT_N + int(length)]
+
+
+def codec_bands(sample_rate, n=21):
+    """n + 1 increasing band edges over the 512 coefficients (edge[0] = 0, edge[n] = 512) on a Bark-like scale: equal steps of
+    z(f) = 13 atan(0.00076 f) + 3.5 atan((f / 7500)^2) up to sample_rate / 2, every band at least one coefficient wide."""
+    n = int(n)
+    if not (math.isfinite(float(sample_rate)) and float(sample_rate) > 0) or not 1 <= n <= MDCT_N:
+        raise ValueError(f"codec_bands({sample_rate!r}, {n!r}): a positive rate and 1 .. {MDCT_N} bands")
+    f = (np.arange(MDCT_N + 1, dtype=np.float64)) * float(sample_rate) / (2 * MDCT_N)
+    z = 13.0 * np.arctan(0.00076 * f) + 3.5 * np.arctan((f / 7500.0) ** 2)
+    edges = np.searchsorted(z, np.linspace(0.0, z[-1], n + 1)).astype(np.int64)
+    edges[0], edges[-1] = 0, MDCT_N
+    for i in range(1, n + 1):                                          # at least one coefficient per band, from the low end
+        edges[i] = max(edges[i], edges[i - 1] + 1)
+    for i in range(n - 1, -1, -1):                                     # and without running past 512 at the high end
+        edges[i] = min(edges[i], edges[i + 1] - 1)
+    return edges
+
+
+def _codec_cutoff(sample_rate, cutoff_hz):
+    """First discarded coefficient: those whose centre (k + 1/2) sample_rate / 1024 lies above the cut-off (None: none)."""
+    if cutoff_hz is None:
+        return MDCT_N
+    cutoff_hz = float(cutoff_hz)
+    if not (math.isfinite(cutoff_hz) and cutoff_hz > 0):
+        raise ValueError(f"cutoff_hz = {cutoff_hz!r}: a positive finite frequency, or None")
+    centre = (np.arange(MDCT_N, dtype=np.float64) + 0.5) * float(sample_rate) / (2 * MDCT_N)
+    return int(np.searchsorted(centre, cutoff_hz, side="right"))
+
+
+def codec_step_grid(length, sample_rate, step_db, cutoff_hz=None, tilt_db_per_octave=0.0):
+    """(512, T) fp32 step grid, the same in every frame: D = 10^(step_db / 20) at 1 kHz, tilted by `tilt_db_per_octave` (coarser towards the
+    top when positive), +inf for the coefficients above `cutoff_hz`."""
+    T = mdct_frames(length)
+    step_db, tilt = float(step_db), float(tilt_db_per_octave)
+    if not (math.isfinite(step_db) and abs(step_db) <= 200 and math.isfinite(tilt) and abs(tilt) <= 48):
+        raise ValueError(f"codec_step_grid: step_db = {step_db!r} (finite, at most 200 in magnitude), tilt_db_per_octave = {tilt!r} (at most 48)")
+    centre = (np.arange(MDCT_N, dtype=np.float64) + 0.5) * float(sample_rate) / (2 * MDCT_N)
+    col = 10.0 ** ((step_db + tilt * np.log2(centre / 1000.0)) / 20.0)
+    col[_codec_cutoff(sample_rate, cutoff_hz):] = np.inf
+    return np.repeat(col.astype(np.float32)[:, None], T, axis=1)
+
+
+def codec_steps_for_nmr(audio, sample_rate, nmr_db, cutoff_hz=None, bands=21, floor=1e-10):
+    """(512, T) or (B, 512, T) fp32 step grid for audio (L,) or (B, L), the one a codec's rate loop would choose: per band of `codec_bands`
+    and frame D = sqrt(12 E 10^(-nmr_db / 10)), E the band's mean coefficient power in that frame (floored), so that the quantisation noise
+    D^2 / 12 of a uniform quantiser sits `nmr_db` below the band; +inf above `cutoff_hz`."""
+    nmr_db = float(nmr_db)
+    if not (math.isfinite(nmr_db) and abs(nmr_db) <= 200):
+        raise ValueError(f"nmr_db = {nmr_db!r}: a finite number, at most 200 in magnitude")
+    x = np.asarray(audio, dtype=np.float64)
+    if x.ndim not in (1, 2) or not np.isfinite(x).all():
+        raise ValueError(f"audio has shape {x.shape}: (L,) or (B, L), finite")
+    C = mdct(x)
+    edges = codec_bands(sample_rate, bands)
+    D = np.empty_like(C)
+    for lo, hi in zip(edges[:-1], edges[1:]):
+        E = np.maximum((C[..., lo:hi, :] ** 2).mean(axis=-2, keepdims=True), float(floor))
+        D[..., lo:hi, :] = np.sqrt(12.0 * E * 10.0 ** (-nmr_db / 10.0))
+    D[..., _codec_cutoff(sample_rate, cutoff_hz):, :] = np.inf
+    return D.astype(np.float32)
+
+
 # ---- blind equalisation (BlindEqualizationOperator; csrc/tf_eq.hip): a gain per bin, constant in time; bin k sits at k * sample_rate / 1024
 def eq_curve(sample_rate, points):
     """(513,) fp32 gain curve through (frequency_hz, gain_db) breakpoints: linear in dB over log-frequency between them, flat beyond the

@@ -675,6 +675,142 @@ class TimeFrequencyMaskOperator(_MelOperator):
         return ops.hip.tf_gain(h, x, g, int(length), int(length)), adjoint
 
 
+class CodecOperator(_MelOperator):
+    """Codec restoration (extension; the first nonlinearity in a TRANSFORM domain, with a gate on every coefficient): the measurement of a
+    lossy codec -- MP3, AAC, Vorbis -- is an MDCT of the signal whose coefficients were quantised, one step per band and frame, everything
+    above a cut-off thrown away.  Per clip, x zero outside [0, L) (csrc/mdct_quant.hip):
+
+        A = Phi^T Q Phi      Phi: MDCT, N = 512 coefficients per frame, frame length 1024, hop 512, window sin(pi (n + 1/2) / 1024),
+                             T = ceil(L / 512) + 1 = `dsp.mdct_frames(L)` frames, frame t at sample (t - 1) * 512; Phi^T Phi = I on the clip
+        Q(C) = rint(C / D) D round-half-even; D = 0 is transparent, D = +inf discards the coefficient (the codec's low-pass)
+
+    forward = noiser(A(x)), transform = clamp(wav2mel, -80, 80) like the IdentityOperator's.  A is materialised (`_on_load` is None): a guided
+    step is the identity's plus one `mdct_quant` launch, and a second one where a step is infinite.
+
+    STRAIGHT-THROUGH BACKWARD: Q is a staircase, its Jacobian is zero almost everywhere and useless for guidance.  `adjoint` replaces the
+    staircase by its mean slope -- 1 on a kept coefficient, 0 on a discarded one: adjoint(dy) = Phi^T K Phi dy, K[k, t] = [D[k, t] < inf].
+    It is symmetric, linear in dy and independent of x.  Where no step of the grid is infinite it is the identity on the clip: `adjoint` is
+    then the zero-padded copy and launches no transform.  The gradient `guidance` returns is therefore NOT the derivative of its loss.
+
+    step: (512, T) -- one grid for every clip -- or (B, 512, T), fp32, 0 <= D <= +inf, in the layout of the time-frequency gain (coefficients,
+    frames); `dsp.codec_step_grid` and `dsp.codec_steps_for_nmr` build one.  A negative or NaN step is refused by name.  The grid belongs to
+    ONE clip length: `apply`, `forward`, `guidance`, `encode` and `project` raise a ValueError naming the expected shape for any other (inside
+    a TrackOperator build it for the track's length).  With per-clip grids the batch must be B, and the pipelines refuse `lanes > 1` and
+    `shard=True` (the grids are indexed by batch position); a shared grid has no such state.
+
+    dead_span: frames t0 .. t1 whose steps are +inf in every coefficient, for every clip, leave the samples [512 t0, 512 t1) -- those that
+    only these frames cover -- exactly +0 in y and in the gradient; the longest such run is found on the host once.  `project` is the optional
+    output stage.  The front end and the device copy are made on first use, so the operator can be built without a GPU."""
+
+    def __init__(self, sample_rate=16000, step=None, noiser=None):
+        if step is None:
+            raise ValueError(f"step: a ({dsp.MDCT_N}, T) grid for every clip or (B, {dsp.MDCT_N}, T), T = ceil(L / 512) + 1 (dsp.codec_step_grid)")
+        d = torch.as_tensor(step).detach().to(device="cpu", dtype=torch.float32)
+        if d.dim() not in (2, 3) or d.shape[-2] != dsp.MDCT_N or d.shape[-1] < 2 or d.shape[0] < 1:
+            raise ValueError(f"step has shape {tuple(d.shape)}: ({dsp.MDCT_N}, T) for every clip or (B, {dsp.MDCT_N}, T), T = ceil(L / 512) + 1")
+        if bool(torch.isnan(d).any()) or bool((d < 0).any()):
+            raise ValueError("step: values in [0, +inf] (0 = transparent, +inf = the coefficient is discarded); negative or NaN steps are refused")
+        self.sample_rate, self.noiser = sample_rate, noiser
+        self.per_clip = d.dim() == 3
+        self.step = d.clone()                                 # host copy, public layout (coefficients, frames)
+        self._step_t = None                                   # device copy as the kernel reads it: (frames, coefficients) rows
+        self.lossless = not bool(torch.isinf(d).any())        # no coefficient is discarded: the straight-through transpose is the identity
+        self._dead = self._find_dead(d)
+        self._init_mel(sample_rate, lazy=True)
+
+    @property
+    def step_frames(self):
+        return self.step.shape[-1]
+
+    def frames(self, length):
+        return dsp.mdct_frames(length)
+
+    @property
+    def positional_state(self):                               # one shared grid has no per-position state
+        return ("CodecOperator with per-clip step grids", "step grids") if self.per_clip else None
+
+    @staticmethod
+    def _find_dead(d):
+        """Frames whose step is +inf in every coefficient of every clip -> the longest run t0 .. t1, t1 > t0, as samples [512 t0, 512 t1)."""
+        gone = torch.isinf(d).reshape(-1, d.shape[-2], d.shape[-1]).all(dim=1).all(dim=0)
+        run = longest_zero_run(torch.where(gone, 0.0, 1.0).numpy())
+        if run is None or run[1] - run[0] < 2:
+            return None
+        return dsp.MDCT_N * run[0], dsp.MDCT_N * (run[1] - 1)   # t1 = run[1] - 1 inclusive
+
+    def dead_span(self, length):
+        if self._dead is None or dsp.mdct_frames(length) != self.step_frames:
+            return None
+        s0, s1 = self._dead[0], min(self._dead[1], int(length))
+        return (s0, s1) if s1 > s0 else None
+
+    def _check(self, batch, length):
+        T = dsp.mdct_frames(length)
+        if self.step_frames != T:
+            raise ValueError(f"CodecOperator holds a step grid of shape {tuple(self.step.shape)}; a clip of {length} samples needs "
+                             f"({dsp.MDCT_N}, {T}) = (512, ceil({length} / 512) + 1)")
+        if self.per_clip and self.step.shape[0] != batch:
+            raise ValueError(f"CodecOperator holds {self.step.shape[0]} per-clip step grid(s) of shape ({dsp.MDCT_N}, {T}), the batch "
+                             f"has {batch} clip(s): expected ({batch}, {dsp.MDCT_N}, {T})")
+
+    def step_on(self, device):
+        """The step grid on `device` as the kernel reads it, (T, 512) or (B, T, 512) contiguous (one tensor, kept)."""
+        if self._step_t is None or self._step_t.device != device:
+            self._step_t = self.step.transpose(-1, -2).contiguous().to(device)
+        return self._step_t
+
+    def forward(self, data, **kwargs):
+        self._check(data.shape[0], data.shape[-1])            # before the tensor has to be on the GPU
+        return super().forward(data, **kwargs)
+
+    def guidance(self, wav, length, measurement, supervised_space, **kw):
+        self._check(wav.shape[0], length)
+        return super().guidance(wav, length, measurement, supervised_space, **kw)
+
+    def apply(self, x, length, **kw):
+        self._check(x.shape[0], length)
+        h, d = self.frontend._h.value, self.step_on(x.device)
+
+        def adjoint(dy, full):                                # straight-through: Phi^T K Phi, the zero-padded copy where K = 1 everywhere
+            if self.lossless:
+                return ops.hip.mask_mul(dy, None, int(length), int(full))
+            return ops.hip.mdct_quant(h, dy.contiguous(), d, int(length), int(full), passthrough=True)[0]
+        return ops.hip.mdct_quant(h, x, d, int(length), int(length))[0], adjoint
+
+    def _rows(self, audio):
+        """audio as (B, L) fp32 rows on the GPU, checked against the grid first"""
+        a = torch.as_tensor(audio)
+        a = a.reshape(a.shape[0], -1)
+        self._check(a.shape[0], a.shape[1])                   # before the tensor has to be on the GPU
+        a = _as_f32_cuda(a)
+        return a if a.stride(1) == 1 else a.contiguous()
+
+    def encode(self, audio):
+        """audio (B, L) -> the codes rint(Phi audio / D) as (B, T, 512) int32; INT32_MIN marks a coefficient that is not coded (D = 0, or a
+        quotient of 2^23 and more), a discarded one has code 0."""
+        a = self._rows(audio)
+        return ops.hip.mdct_quant(self.frontend._h.value, a, self.step_on(a.device), a.shape[1], a.shape[1], want_codes=True)[1]
+
+    def project(self, wav, measurement):
+        """The conventional output stage of codec restoration -> (B, L), L the measurement's length: the MDCT coefficients of the restored
+        audio are clamped into the quantiser cells [(q - 1/2) D, (q + 1/2) D] of the measurement's codes q = rint(Phi y / D), and
+        resynthesised.  Only on WHOLE frames (1 <= t <= L // 512 - 1: all 1024 samples inside the clip), where Phi Phi^T = I and the codes of
+        the measurement are the codec's own; the two edge frames, transparent, discarded and uncoded coefficients are left as they are.
+        Opt-in; refused with measurement noise, under which the codes of y are not the codec's."""
+        if step_sigma(self.noiser) > 0:
+            raise ValueError("project: the measurement carries additive noise (sigma > 0), so its codes are not the codec's")
+        y = self._rows(measurement)
+        wav = _as_f32_cuda(torch.as_tensor(wav).to(y.device))
+        wav = wav.reshape(wav.shape[0], -1)
+        if wav.shape[0] != y.shape[0] or wav.shape[1] < y.shape[1]:
+            raise ValueError(f"project: restored audio {tuple(wav.shape)} does not cover the measurement {tuple(y.shape)}")
+        if wav.stride(1) != 1:
+            wav = wav.contiguous()
+        h, d, L_ = self.frontend._h.value, self.step_on(y.device), y.shape[1]
+        codes = ops.hip.mdct_quant(h, y, d, L_, L_, want_codes=True)[1]
+        return ops.hip.mdct_project(h, wav, d, codes, L_, L_)
+
+
 class DynamicRangeOperator(_MelOperator):
     """De-compression (extension; the first operator that is nonlinear WITH MEMORY): a feed-forward, mono dynamic-range compressor or
     limiter -- over-mastered releases, broadcast AGC, bus compressors -- whose sidechain runs on blocks of 64 samples (4 ms at 16 kHz).

@@ -56,6 +56,13 @@ width both sides share: it is given, not fitted), `--drc_fit threshold,ratio,mak
 `--drc_init_threshold_db`, `--drc_init_ratio`, `--drc_init_attack_ms`, `--drc_init_release_ms`, `--drc_init_makeup_db` say where the fit
 starts; a flag that is not given takes its value from configs/inverse_problem/music_blind_decompression.yaml.
 
+`-t music_codec_restoration` measures through an MDCT quantiser (CodecOperator: the coefficients of a lossy codec, one step per band and
+frame, nothing above the cut-off): `--codec_nmr_db X` chooses the steps a codec's rate loop would, X dB of noise-to-mask ratio below every
+band of the clean clip, `--codec_step_db X` a fixed grid instead (the step at 1 kHz in dB re 1.0; the two exclude each other), and
+`--codec_cutoff_hz F` the low-pass; a flag that is not given takes its value from configs/inverse_problem/music_codec_restoration.yaml.
+The grid is built for the clip's length, in track mode for the track's.  `--project` clamps the result's coefficients into the quantiser
+cells of the measurement's own codes (meaningful with `--supervised_space wav_form`).
+
 `-t music_source_separation` restores K stems from their mixture under one loss (inverse_problem/mixture.py), one prompt embedding per
 stem: `--wav` names the stems whose gain-weighted sum (`--gains`) is the measurement (SI-SDR per stem is printed), `--mixture mix.wav
 --stems K` separates a real mixture.  One file per stem is written; `--project` makes the stems sum to the mixture exactly.
@@ -79,7 +86,7 @@ from diffmusic_amd.schedulers import get_scheduler                              
 
 TASKS = ("music_generation", "music_inpainting", "super_resolution", "phase_retrieval", "music_dereverberation", "music_declipping",
          "music_blind_dereverberation", "music_source_separation", "music_spectral_inpainting", "music_blind_equalization", "music_decompression",
-         "music_wow_flutter", "music_blind_wow_flutter", "music_blind_decompression", "music_declicking")
+         "music_wow_flutter", "music_blind_wow_flutter", "music_blind_decompression", "music_declicking", "music_codec_restoration")
 SEPARATION = "music_source_separation"
 SPECTRAL = "music_spectral_inpainting"
 BLIND_EQ = "music_blind_equalization"
@@ -88,12 +95,13 @@ WOW_FLUTTER = "music_wow_flutter"
 BLIND_WOW = "music_blind_wow_flutter"
 BLIND_DRC = "music_blind_decompression"
 DECLICK = "music_declicking"
+CODEC = "music_codec_restoration"
 DRC_INIT_FLAGS = ("threshold_db", "ratio", "attack_ms", "release_ms", "makeup_db")
 DRC_FLAGS = ("threshold_db", "ratio", "knee_db", "attack_ms", "release_ms", "makeup_db")
 
 
 def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=None, tf_boxes=None, eq_true=None, drc=None, warp=None,
-                   blind_warp=None, blind_drc=None, declick=None):
+                   blind_warp=None, blind_drc=None, declick=None, codec=None, codec_audio=None):
     """run.py:157-212: one operator per task, constructor arguments from the data / model config.  `audio_length_in_s`: the length the
     operator acts on when it is not the model window (a track).  `clip_threshold`: music_declipping's threshold(s), a float or one value
     per clip (`threshold_for_sdr` of the clean clips).  `tf_boxes`: music_spectral_inpainting's boxes (`spectral_boxes`).  `eq_true`:
@@ -101,7 +109,9 @@ def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=
     parameters (`compressor_params`).  `warp`: music_wow_flutter's speed components (`warp_params`); the delay curve is built here, for the
     length the operator acts on.  `blind_warp`: music_blind_wow_flutter's fit options (`blind_warp_params`); `warp` then describes the TRUE
     curve, kept on the operator for `forward`.  `blind_drc`: music_blind_decompression's `operator` keyword arguments and the `true`
-    parameters of the measurement (`blind_drc_params`), the latter kept on the operator for `forward`."""
+    parameters of the measurement (`blind_drc_params`), the latter kept on the operator for `forward`.  `codec`: music_codec_restoration's
+    grid recipe (`codec_params`); with `nmr_db` the steps follow `codec_audio`, the clean clips (B, L) or the one track (L,), and the grid
+    is built for their length."""
     noiser = P.get_noiser(**cfg.inverse_problem.noise)
     d, scale = cfg.data, 1
     seconds = cfg.model.pipe.audio_length_in_s if audio_length_in_s is None else audio_length_in_s
@@ -164,9 +174,54 @@ def build_operator(task, cfg, mask_type, audio_length_in_s=None, clip_threshold=
             raise ValueError("music_declicking needs declick (declick_params(args, cfg))")
         op = P.DeclickOperator(sample_rate=d.sample_rate, noiser=noiser, **declick["operator"])
         op.click_recipe = dict(declick["clicks"])              # the synthetic measurement's clicks (`synthetic_clicks`)
+    elif task == CODEC:
+        if codec is None:
+            raise ValueError("music_codec_restoration needs codec (codec_params(args, cfg))")
+        if codec.get("nmr_db") is not None:
+            if codec_audio is None:
+                raise ValueError("music_codec_restoration with nmr_db needs codec_audio, the clean audio the steps adapt to")
+            audio = torch.as_tensor(codec_audio).detach().cpu().numpy()
+            grid = P.codec_steps_for_nmr(audio, d.sample_rate, codec["nmr_db"], cutoff_hz=codec.get("cutoff_hz"))
+        else:
+            grid = P.codec_step_grid(int(seconds * d.sample_rate), d.sample_rate, codec["step_db"], cutoff_hz=codec.get("cutoff_hz"),
+                                     tilt_db_per_octave=codec.get("tilt_db_per_octave", 0.0))
+        op = P.CodecOperator(sample_rate=d.sample_rate, step=grid, noiser=noiser)
     else:
         raise ValueError(f"Unknown task: {task}")
     return op, scale
+
+
+def codec_params(args, cfg):
+    """The argument rules of -t music_codec_restoration -> {"nmr_db" or "step_db", "cutoff_hz", "tilt_db_per_octave"}: --codec_nmr_db and
+    --codec_step_db exclude each other and replace BOTH of the config's; --codec_cutoff_hz (0 or less: no cut-off) replaces the config's.
+    Exactly one of nmr_db / step_db must remain.  Any other task refuses the flags."""
+    flags = dict(codec_nmr_db=args.codec_nmr_db, codec_step_db=args.codec_step_db, codec_cutoff_hz=args.codec_cutoff_hz)
+    if args.task != CODEC:
+        for name, v in flags.items():
+            if v is not None:
+                raise SystemExit(f"--{name} belongs to -t {CODEC}")
+        return None
+    if args.codec_nmr_db is not None and args.codec_step_db is not None:
+        raise SystemExit("--codec_nmr_db (signal-adaptive steps) and --codec_step_db (a fixed grid) exclude each other")
+    ip = cfg.inverse_problem
+    nmr, step = ip.get("nmr_db"), ip.get("step_db")
+    if args.codec_nmr_db is not None:
+        nmr, step = args.codec_nmr_db, None
+    elif args.codec_step_db is not None:
+        nmr, step = None, args.codec_step_db
+    if (nmr is None) == (step is None):
+        raise SystemExit(f"-t {CODEC}: exactly one of nmr_db / step_db (--codec_nmr_db / --codec_step_db)")
+    cutoff = ip.get("cutoff_hz") if args.codec_cutoff_hz is None else (args.codec_cutoff_hz if args.codec_cutoff_hz > 0 else None)
+    out = dict(cutoff_hz=None if cutoff is None else float(cutoff), tilt_db_per_octave=float(ip.get("tilt_db_per_octave") or 0.0))
+    out["nmr_db" if nmr is not None else "step_db"] = float(nmr if nmr is not None else step)
+    try:
+        if nmr is not None:
+            P.codec_steps_for_nmr(np.zeros(16), cfg.data.sample_rate, out["nmr_db"], cutoff_hz=out["cutoff_hz"])
+        else:
+            P.codec_step_grid(16, cfg.data.sample_rate, out["step_db"], cutoff_hz=out["cutoff_hz"], tilt_db_per_octave=out["tilt_db_per_octave"])
+    except ValueError as e:
+        raise SystemExit(f"-t {CODEC}: {e}")
+    return out
 
 
 def declick_params(args, cfg):
@@ -297,6 +352,12 @@ def parse_args(argv=None):
                     help="music_declicking: a residual above this multiple of the frame's robust scale is a click (default: the task's config)")
     ap.add_argument("--declick_guard", type=int, default=None,
                     help="music_declicking: samples hidden on each side of a detected one, 0 .. 64 (default: the task's config)")
+    ap.add_argument("--codec_nmr_db", type=float, default=None,
+                    help="music_codec_restoration: signal-adaptive steps, the quantisation noise this many dB below each band (default: the task's config)")
+    ap.add_argument("--codec_step_db", type=float, default=None,
+                    help="music_codec_restoration: a fixed step grid instead, the step at 1 kHz in dB re 1.0 (default: the task's config)")
+    ap.add_argument("--codec_cutoff_hz", type=float, default=None,
+                    help="music_codec_restoration: coefficients above this frequency are discarded, 0 = none (default: the task's config)")
     ap.add_argument("--wow", action="append", default=None, metavar="RATE_HZ,DEPTH_PCT[,PHASE_DEG]",
                     help="music_wow_flutter: one speed-modulation component (repeatable; default: the task's config)")
     ap.add_argument("--speed_pct", type=float, default=None, help="music_wow_flutter: constant speed error in percent (default: the task's config)")
@@ -611,11 +672,12 @@ def main(argv=None):
     args = parse_args(argv)
     overrides = [f"data={args.data}", f"model={args.model}"]
     if args.task in ("music_declipping", "music_blind_dereverberation", SEPARATION, SPECTRAL, BLIND_EQ, DECOMPRESSION, WOW_FLUTTER, BLIND_WOW,
-                     BLIND_DRC, DECLICK):
+                     BLIND_DRC, DECLICK, CODEC):
         overrides.append(f"inverse_problem={args.task}")
     stems = separation_stems(args)
-    if args.project and args.task not in ("music_declipping", SEPARATION, DECLICK):
-        raise SystemExit("--project is the output stage of -t music_declipping, -t music_source_separation and -t music_declicking")
+    if args.project and args.task not in ("music_declipping", SEPARATION, DECLICK, CODEC):
+        raise SystemExit("--project is the output stage of -t music_declipping, -t music_source_separation, -t music_declicking and "
+                         "-t music_codec_restoration")
     cfg = compose(args.config_name, overrides=overrides)
     tf_boxes = spectral_boxes(args, cfg)
     eq_true = equalization_curve(args, cfg)
@@ -624,6 +686,7 @@ def main(argv=None):
     blind_warp = blind_warp_params(args, cfg)
     blind_drc = blind_drc_params(args, cfg)
     declick = declick_params(args, cfg)
+    codec = codec_params(args, cfg)
     if stems is not None:
         if args.model != "musicldm":
             raise SystemExit("this driver feeds MusicLDM's class-embedding conditioning; AudioLDM2 needs its T5 / GPT-2 states (see bench.py --workload)")
@@ -641,7 +704,7 @@ def main(argv=None):
         gt = load_clips(args.wav, args.batch, sr, length, args.seed).to(device)
         thr = P.threshold_for_sdr(gt, args.clip_sdr_db) if args.task == "music_declipping" else None
         op, scale = build_operator(args.task, cfg, args.mask_type, clip_threshold=thr, tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp,
-                                   blind_warp=blind_warp, blind_drc=blind_drc, declick=declick)
+                                   blind_warp=blind_warp, blind_drc=blind_drc, declick=declick, codec=codec, codec_audio=gt)
         B = gt.shape[0]
     else:
         if args.task == "music_generation":
@@ -652,7 +715,7 @@ def main(argv=None):
         thr = float(P.threshold_for_sdr(gt, args.clip_sdr_db)[0]) if args.task == "music_declipping" else None
         inner, scale = build_operator(args.task, cfg, args.mask_type, audio_length_in_s=P.seconds_for_samples(T, sr), clip_threshold=thr,
                                       tf_boxes=tf_boxes, eq_true=eq_true, drc=drc, warp=warp, blind_warp=blind_warp,
-                                      blind_drc=blind_drc, declick=declick)
+                                      blind_drc=blind_drc, declick=declick, codec=codec, codec_audio=gt[0])
         op = P.TrackOperator(inner, layout)
         B = layout.num_windows
         sched_kw["per_clip_norm"] = False                                          # one loss, norms over all windows

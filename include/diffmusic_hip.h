@@ -38,7 +38,8 @@ extern "C" {
  * (de-compression: a dynamic-range compressor and the transpose of its Jacobian) and dmx_warp_fwd / dmx_warp_bwd (wow and flutter: a clip
  * read along a delay curve, and the transpose) and dmx_warp_wgrad / dmx_warp_update (blind wow and flutter: the delay curve fitted) and dmx_drc_fwd_p / dmx_drc_bwd_p / dmx_drc_pgrad /
  * dmx_drc_update (blind de-compression: the compressor's parameters per clip on the device, and fitted) and dmx_click_detect /
- * dmx_click_mask / dmx_mask_rows / dmx_declick_blend (declicking: a click detector and per-clip sample masks) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
+ * dmx_click_mask / dmx_mask_rows / dmx_declick_blend (declicking: a click detector and per-clip sample masks) and dmx_mdct_frames / dmx_mdct_quant /
+ * dmx_mdct_project (codec restoration: an MDCT quantiser, its straight-through transpose and its cell projection) are new symbols, and every earlier entry point keeps its signature.  A binding that meets a version-4 library without them names the missing
  * symbol and asks for a rebuild. */
 #define DMX_ABI_VERSION 4   /* 4: dmx_htsat_* / dmx_gram_* (CLAP HTS-AT audio tower of the style-guidance operator).  Earlier:  2: dmx_flash_attn_raw takes row-major V (ld = ldv) instead of per-head V^T; GemmDesc grew.  3: GemmDesc grew (EPI_LNFOLD / EPI_ROWSTATS / EPI_GNSTATS / EPI_GNBWD: colsum, ln_eps, rowstats_in, rowstats_out, nslots, gn_part, gnb_*) */
 #define DMX_MAX_STAGES 8
@@ -415,6 +416,24 @@ int dmx_audio_tf_wgrad(dmx_audio* a, const float* x, long long x_stride, const f
                        void* stream);
 int dmx_audio_eq_update(const float* partials, int segments, float* g, float* m, float* v, int batch, int k, double lr, double beta1,
                         double beta2, double eps, int normalize, void* stream);
+/* Codec restoration (csrc/mdct_quant.hip): out[b, 0:L] = Phi^T f(Phi x[b, 0:L]) and +0 on [L, full).  Phi is the MDCT
+ * of the zero-extended clip: N = 512 coefficients per frame, frame length 1024, hop 512, window sin(pi (n + 1/2) / 1024), frames =
+ * dmx_mdct_frames(L) = ceil(L / 512) + 1 (0 for L < 1), frame t at sample (t - 1) * 512, scaled by sqrt(2 / N); Phi^T Phi = I on the clip.
+ * step: (frames, 512) fp32 rows per clip -- coefficients contiguous -- with step_clip_stride floats between clips, 0 = one grid for every clip.
+ *   mdct_quant    pass = 0: f = Q, q = rint(C / D) (round-half-even, correctly rounded division), Q(C) = q D; D = 0 is transparent, D = +inf
+ *                 discards the coefficient (value 0, code 0); |C / D| >= 2^23, a NaN quotient, a negative or NaN step pass C through.  codes,
+ *                 when not null, receives q as (batch, frames, 512) int32, INT32_MIN for every coefficient that was not coded.
+ *                 pass = 1: f(C) = C where D is not +inf, else 0 -- the straight-through transpose of the quantiser; codes is ignored.
+ *   mdct_project  f clamps C into [(q - 1/2) D, (q + 1/2) D], q read from codes (batch, frames, 512), on whole frames (1 <= t <= L / 512 - 1),
+ *                 where 0 < D < inf and q is not INT32_MIN; every other coefficient is left as it is.
+ * Uses the handle's FFT twiddles and its MDCT tables: the handle must have n_fft = 1024.  One launch, no workspace, no atomics: the same bits
+ * on every call, alone, in a batch and at another batch position.  DMX_ERR_SHAPE, with nothing written, for another handle, L < 1, full < L,
+ * x_stride < L, out_stride < full, a non-zero step_clip_stride < frames * 512, a null pointer (codes of mdct_project included), batch > 65535. */
+int dmx_mdct_frames(int L);
+int dmx_mdct_quant(dmx_audio* a, const float* x, long long x_stride, const float* step, long long step_clip_stride, int* codes, float* out,
+                   long long out_stride, int batch, int L, int full, int pass, void* stream);
+int dmx_mdct_project(dmx_audio* a, const float* x, long long x_stride, const float* step, long long step_clip_stride, const int* codes, float* out,
+                     long long out_stride, int batch, int L, int full, void* stream);
 /* PhaseRetrievalOperator.transform on a given magnitude (B, bins, frames) -> (B, frames, n_mels) */
 int dmx_audio_melscale(dmx_audio* a, const float* mag, float* mel_out, int batch, int frames, float lo, float hi, void* stream);
 /* MusicInpaintingOperator.forward (operator.py:132-133): y[b,t] = x[b,t]*mask[t] (t<L), 0 for L<=t<Ly; mask NULL = copy */
